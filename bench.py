@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: volumes/s of the MST-DINOv2 forward (DinoV2ClassifierSlice) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment) starts the N ranks itself, as fresh
@@ -12,17 +12,21 @@ Workload (BASELINE.json configs[1]): a batch of 4 synthetic 64 x 512 x 512 bf16 
 symmetrically zero-padded to 518 x 518 = 37 x 37 patches, DINOv2's native grid (stated in `config`).
 One step = one full forward (patch-embed -> 12 ViT blocks -> slice transformer -> logits) over the
 batch, inputs resident in HBM, weights = mst.synth random init of the reference architecture.
-Volume 0 of rank 0's batch is the input of the reference fixture tests/golden/c3_1x64x518.npz (same weights), so the
-logits of the TIMED batch are checked against what the reference itself produced (`parity_check` in the JSON line).
+Volume 0 of rank 0's batch is the input of the reference fixture tests/golden/c3_1x64x518.npz (same weights); with
+`--full` the logits of the TIMED batch are checked against what the reference itself produced (`parity_check`).
 
 N > 1: `--scaling weak` (default; the contract's definition): the global batch is 4N volumes; every volume's 64 slices
 are sharded across the N ranks (each rank encodes 64/N slices of all 4N volumes = the same 256 slices as at N = 1), ONE
 RCCL all-gather of the slice embeddings, then the Slice Transformer replicated.  `--scaling strong`
 (BASELINE configs[2]: one job, slices sharded): the global batch stays at --volumes and each rank encodes 64/N slices.
 
-The JSON line also carries `roofline` (dominant kernel, HIP events recorded by a caller-owned mst_profiler on every
-4th timed step) and, at N = 1, `cpu_baseline` (the CPU oracle = PyTorch-CPU restatement of the reference forward, timed
-on the host cores over one whole volume).
+A plain run sets up, warms up, times the K steps and prints the JSON line (`ms_per_step` = one timed step).
+`--dump-outputs DIR` then writes what the last timed step returned, the logits of the whole global batch, to
+DIR/logits.npy (float32); the inputs and weights are seeded, so the same arguments give the same inputs on every run.
+`--full` adds what takes runs or checks of its own: `parity_check` (above), `roofline` and `kernels` (dominant kernel,
+HIP events recorded by a caller-owned mst_profiler on every 4th timed step) and, at N = 1, `cpu_baseline` (the CPU
+oracle = PyTorch-CPU restatement of the reference forward, timed on the host cores over one whole volume).  Without
+`--full` those fields are null / empty.
 """
 from __future__ import annotations
 
@@ -82,7 +86,7 @@ def kernel_flops(kind: str, n_slices: int, N: int) -> float:
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32", "fp8"],
                     help="bf16 is the BASELINE metric's dtype; fp8 = e4m3 linear layers on a bf16 carrier (configs[4])")
@@ -97,13 +101,21 @@ def parse_args(argv=None):
                     help="weak: --volumes per GPU (global batch grows with N); strong: --volumes in total, 64/N slices per rank")
     ap.add_argument("--fp8-calibrate", action="store_true",
                     help="--dtype fp8 only: calibrate static activation scales on the bench batch first (untimed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step (whole global batch) to DIR/logits.npy as float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also the reference parity check, per-kernel timing / roofline and (N = 1) the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without per-kernel timing / roofline")
+    ap.add_argument("--no-parity-check", action="store_true",
+                    help="no reference fixture volume in the batch (weights seed 0) and no parity check")
     ap.add_argument("--prune-last-block", action="store_true",
                     help="NOT the headline configuration: the last block computes only what is read behind it (K/V of every "
                          "token, attention + MLP of the class tokens).  Same results; FLOPs are then counted as executed")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -219,7 +231,7 @@ def main():
         if args.dtype != "fp8":
             raise SystemExit("--fp8-calibrate needs --dtype fp8")
         model.calibrate_fp8(vol)
-    prof = None if args.no_kernel_timing else hip.Profiler()
+    prof = hip.Profiler() if args.full and not args.no_kernel_timing else None
     sampled_steps = 0
     with torch.no_grad():
         for _ in range(args.warmup):
@@ -237,8 +249,24 @@ def main():
     model.profiler = None
     assert bool(torch.isfinite(out).all()), "non-finite logits"
 
+    if args.dump_outputs:
+        logits = out.float()
+        if dp:                                           # every rank holds its own volumes: gather them in rank order
+            parts = [torch.empty_like(logits) for _ in range(world)]
+            if backend == "nccl":
+                dist.all_gather(parts, logits)
+            else:
+                parts = [t.cpu() for t in parts]
+                dist.all_gather(parts, logits.cpu())
+            logits = torch.cat([t.cpu() for t in parts])
+        if rank == 0:
+            import numpy as np
+            d = Path(args.dump_outputs)
+            d.mkdir(parents=True, exist_ok=True)
+            np.save(d / "logits.npy", logits.cpu().numpy())
+
     parity = None
-    if fixture and rank == 0:
+    if args.full and fixture and rank == 0:
         tol = {"bf16": 3e-2, "fp16": 5e-3, "fp32": 1e-4, "fp8": 2.5e-1}[args.dtype]   # tests/test_model_gpu.py TOL
         err = float((out[0].float().cpu() - fixture["logits"][0]).abs().max())
         parity = {"fixture": "tests/golden/c3_1x64x518.npz (reference output)", "what": "logits of volume 0 of the timed batch",
@@ -310,7 +338,7 @@ def main():
                     pass
 
     cpu_baseline = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         from oracle import mst_oracle as O          # the checker, timed as the CPU baseline (kind: port)
         sd = synth.synth_state_dict("s", wseed)
         try:

@@ -2,7 +2,8 @@
 (scripts/main_predict.py:23-30, scripts/main_train.py:13-19) must resolve with this build ahead of the reference --
 ``mst.models.{dino,resnet,base_model}`` from the build, ``mst.data`` / ``mst.utils`` / ``mst.models.utils.functions`` from
 the reference.  Third-party packages the image lacks (torchio, monai, torchvision, ...) are replaced by empty stand-ins:
-only name resolution is under test, nothing of them runs.  Needs the reference checkout (skipped on the GPU box)."""
+only name resolution is under test, nothing of them runs.  The reference checkout is a stand-in written by the
+``ref`` fixture: its package layout, the names the two scripts import and decoy ``mst.models`` modules that must lose."""
 import json
 import subprocess
 import sys
@@ -13,9 +14,80 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 BUILD = ROOT / "new-vit_amd"
-REF = Path("/root/reference")
 
-pytestmark = pytest.mark.skipif(not (REF / "scripts" / "main_predict.py").exists(), reason="reference checkout not present")
+_MST_IMPORTS = """
+        from mst.data.datasets.dataset_3d_lidc import LIDC_Dataset3D
+        from mst.data.datamodules import DataModule
+        from mst.models.resnet import ResNet, ResNetSliceTrans
+        from mst.models.dino import DinoV2ClassifierSlice, DinoV3ClassifierSlice
+"""
+_DECOY = "raise ImportError('the reference checkout was imported instead of the build: ' + __name__)\n"
+_STAND_IN = {
+    "scripts/main_predict.py": """
+        from pathlib import Path
+        import sys
+        import torch
+
+        project_root = Path(__file__).parent.parent
+        sys.path.insert(0, str(project_root))
+        import torchio as tio
+        import numpy as np
+        from monai.metrics import compute_iou
+    """ + _MST_IMPORTS + """
+        from mst.utils.roc_curve import plot_roc_curve, cm2acc, cm2x
+        from mst.models.utils.functions import tensor2image, tensor_cam2image, minmax_norm, one_hot
+
+        def main():
+            pass
+    """,
+    "scripts/main_train.py": """
+        import torch
+        import transformers
+        print(transformers.__version__)
+        from pytorch_lightning.trainer import Trainer
+        from pytorch_lightning.callbacks import EarlyStopping, ModelCheckpoint
+    """ + _MST_IMPORTS + """
+        def main():
+            pass
+    """,
+    "mst/__init__.py": "",
+    "mst/data/__init__.py": "",
+    "mst/data/datamodules/__init__.py": """
+        import pytorch_lightning as pl
+
+        class DataModule(pl.LightningDataModule):
+            pass
+    """,
+    "mst/data/datasets/__init__.py": "",
+    "mst/data/datasets/dataset_3d_lidc.py": """
+        import torchio as tio
+        import torch.utils.data as data
+
+        class LIDC_Dataset3D(data.Dataset):
+            pass
+    """,
+    "mst/utils/__init__.py": "",
+    "mst/utils/roc_curve.py": "".join(f"def {f}(*args, **kwargs):\n    pass\n" for f in ("plot_roc_curve", "cm2acc", "cm2x")),
+    "mst/models/__init__.py": _DECOY,
+    "mst/models/dino.py": _DECOY,
+    "mst/models/resnet.py": _DECOY,
+    "mst/models/base_model.py": _DECOY,
+    "mst/models/utils/__init__.py": "",
+    "mst/models/utils/functions.py": "".join(f"def {f}(*args, **kwargs):\n    pass\n"
+                                            for f in ("tensor2image", "tensor_cam2image", "minmax_norm", "one_hot")),
+}
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    """A stand-in reference checkout: the modules the two scripts import, with empty bodies."""
+    root = tmp_path_factory.mktemp("reference")
+    for rel, text in _STAND_IN.items():
+        f = root / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(textwrap.dedent(text).lstrip("\n"))
+    return root
+
 
 _DRIVER = textwrap.dedent(r'''
     import importlib.abc, importlib.machinery, importlib.util, json, re, sys, types
@@ -101,10 +173,10 @@ _DRIVER = textwrap.dedent(r'''
 
 
 @pytest.mark.parametrize("mode", ["pythonpath", "dropin"])
-def test_reference_script_imports_resolve(mode, tmp_path):
+def test_reference_script_imports_resolve(mode, ref, tmp_path):
     drv = tmp_path / "drv.py"
     drv.write_text(_DRIVER)
-    r = subprocess.run([sys.executable, str(drv), str(BUILD), str(REF), mode], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, str(drv), str(BUILD), str(ref), mode], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     info = json.loads(r.stdout.strip().splitlines()[-1])
     ex = "\n".join(info["executed"])
@@ -120,16 +192,16 @@ def test_reference_script_imports_resolve(mode, tmp_path):
         assert f[name].startswith(str(BUILD)), (name, f[name])
     for name in ("mst.data", "mst.data.datamodules", "mst.data.datasets.dataset_3d_lidc", "mst.utils.roc_curve",
                  "mst.models.utils.functions"):
-        assert f[name].startswith(str(REF)), (name, f[name])
+        assert f[name].startswith(str(ref)), (name, f[name])
     assert info["cls_module_file"].startswith(str(BUILD)) and info["same_class"]
 
 
-def test_dropin_runner_runs_a_script(tmp_path):
+def test_dropin_runner_runs_a_script(ref, tmp_path):
     """python -m mst_dropin <script>: the script sees the build's classes even after pushing the reference to sys.path[0]."""
     script = tmp_path / "probe.py"
     script.write_text(textwrap.dedent(f'''
         import sys
-        sys.path.insert(0, {str(REF)!r})            # what scripts/main_predict.py:11-12 does
+        sys.path.insert(0, {str(ref)!r})            # what scripts/main_predict.py:11-12 does
         from mst.models.dino import DinoV2ClassifierSlice
         import mst.models.dino as d
         assert __name__ == "__main__" and sys.argv[1:] == ["--flag", "7"], sys.argv
