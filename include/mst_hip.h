@@ -111,6 +111,25 @@ int mst_attention_cls_probs(const void* qkv, int dtype, int n_seq, int N, int he
 int mst_attention_probs_full(const void* qkv, int dtype, int n_seq, int N, int heads, int head_dim,
                              float* probs, mst_stream_t stream);
 
+/* Memory-efficient attention for the mixed-precision TRAINING step (FlashAttention-2 form): no [N, N] tensor in the forward or the
+ * backward.  Per-slice encoder blocks only: head_dim == 64, no key mask, any N >= 1.
+ *   qkv16  [n_seq*N, 3*heads*64], dtype MST_BF16 or MST_F16: q | k | v head-major, as mst_attention; q carries head_dim^-0.5
+ *          already (the QKV projection's epilogue), so the scores are q.k with no further scale.
+ * mst_attention_train_fwd: out fp32 [n_seq*N, heads*64] = softmax(q k^T) v (fp32 softmax and accumulation, exact running row
+ *   maximum); lse fp32 [n_seq, heads, N] = ln sum_j exp(q_i . k_j) in NATURAL-log units, the sum `out` is normalised by.
+ * mst_attention_train_bwd: from the forward's qkv16, out, lse and dout fp32 [n_seq*N, heads*64] (the gradient of out), writes every
+ *   element of dqkv fp32 [n_seq*N, 3*heads*64] (laid out like qkv16): dK and dV are the gradients of the stored k and v, dQ that of
+ *   the stored q times dq_scale (pass the epilogue's factor, 0.125, for the gradient of the un-scaled projection output).
+ *   workspace: device memory of at least mst_attention_train_bwd_workspace_bytes(n_seq, N, heads, 64) bytes (a 16-bit image of dout
+ *   and the row sums D = rowsum(dout o out)).  Deterministic (no atomics): identical calls return identical bits.
+ * Unsupported arguments (head_dim != 64, a dtype other than bf16 / fp16, N < 1, a short workspace) return MST_EINVAL. */
+size_t mst_attention_train_bwd_workspace_bytes(int n_seq, int N, int heads, int head_dim);
+int mst_attention_train_fwd(const void* qkv16, int dtype, int n_seq, int N, int heads, int head_dim, float* out, float* lse,
+                            mst_stream_t stream);
+int mst_attention_train_bwd(const void* qkv16, int dtype, const float* out, const float* dout, const float* lse, int n_seq, int N,
+                            int heads, int head_dim, float dq_scale, float* dqkv, void* workspace, size_t workspace_bytes,
+                            mst_stream_t stream);
+
 /* Bicubic resampling of the patch position grid: vision_transformer.py:179-211 (F.interpolate bicubic).
  * offset = interpolate_offset (l.194-202): != 0 -> scale_factor = (g + offset) / M, the vendored default 0.1; 0 -> the
  * output size is given.  antialias = interpolate_antialias (l.206): torch's anti-aliased bicubic (Keys A = -0.5, support

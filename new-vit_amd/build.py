@@ -24,7 +24,8 @@ LIB = Path(os.environ.get("MST_BUILD_LIB", HERE / "mst" / "hip" / "libmst_hip.so
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 PER_FILE_FLAGS = {"k_block16s.hip": ["-fno-slp-vectorize"],   # the SLP pass re-places the hand-placed GELU / LayerNorm arithmetic (and packs it)
-                  "k_attn16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "k_attn32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+                  "k_attn16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "k_attn32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                  "k_attn16_train.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def hipcc() -> str:

@@ -151,6 +151,26 @@ int mst_attention_probs_full(const void* qkv, int dtype, int n_seq, int N, int h
     return launch_probs_full(qkv, dtype, n_seq, N, heads, head_dim, probs, 0, (hipStream_t)stream);
 }
 
+size_t mst_attention_train_bwd_workspace_bytes(int n_seq, int N, int heads, int head_dim) {
+    return head_dim == 64 ? attn_train_workspace_bytes(n_seq, N, heads) : 0;
+}
+
+int mst_attention_train_fwd(const void* qkv16, int dtype, int n_seq, int N, int heads, int head_dim, float* out, float* lse,
+                            mst_stream_t stream) {
+    MST_CHECK_ARG(qkv16 && out && lse, "attention_train_fwd: null pointer");
+    MST_CHECK_ARG(head_dim == 64, "attention_train_fwd: head_dim=%d unsupported (64)", head_dim);
+    return launch_attn_train_fwd(qkv16, dtype, n_seq, N, heads, out, lse, (hipStream_t)stream);
+}
+
+int mst_attention_train_bwd(const void* qkv16, int dtype, const float* out, const float* dout, const float* lse, int n_seq, int N,
+                            int heads, int head_dim, float dq_scale, float* dqkv, void* workspace, size_t workspace_bytes,
+                            mst_stream_t stream) {
+    MST_CHECK_ARG(qkv16 && out && dout && lse && dqkv, "attention_train_bwd: null pointer");
+    MST_CHECK_ARG(head_dim == 64, "attention_train_bwd: head_dim=%d unsupported (64)", head_dim);
+    return launch_attn_train_bwd(qkv16, dtype, out, dout, lse, n_seq, N, heads, dq_scale, dqkv, workspace, workspace_bytes,
+                                 (hipStream_t)stream);
+}
+
 int mst_pos_embed_interp(const float* pos_patch, int M, int E, int gh, int gw, double offset, int antialias, float* out,
                          mst_stream_t stream) {
     MST_CHECK_ARG(pos_patch && out, "pos_embed_interp: null pointer");

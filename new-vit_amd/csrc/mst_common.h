@@ -178,6 +178,11 @@ int launch_conv_wgrad32(const float* dz, const float* x, int n, int H, int W, in
                         int nsplit, int64_t rows_per_split, hipStream_t s);
 int launch_conv_wgrad16(const void* dz, const void* x, int dt, int n, int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, float* part,
                         int nsplit, int64_t rows_per_split, hipStream_t s);
+// memory-efficient training attention (k_attn16_train.hip)
+size_t attn_train_workspace_bytes(int n_seq, int N, int heads);
+int launch_attn_train_fwd(const void* qkv, int dt, int n_seq, int N, int heads, float* out, float* lse, hipStream_t s);
+int launch_attn_train_bwd(const void* qkv, int dt, const float* out, const float* dout, const float* lse, int n_seq, int N, int heads,
+                          float dq_scale, float* dqkv, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const float* freqs, float sign, hipStream_t s);
 int launch_im2col_nhwc16(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, void* col, int dt, hipStream_t s);
 int launch_maxpool_nhwc16(const void* x, int dt, int n, int H, int W, int C, void* y, hipStream_t s);

@@ -66,6 +66,9 @@ SIGNATURES = {
     "mst_attention": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_attention_cls_probs": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_attention_probs_full": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mst_attention_train_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mst_attention_train_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mst_attention_train_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "mst_pos_embed_interp": (_i, [_vp, _i, _i, _i, _i, _d, _i, _vp, _vp]),
     "mst_mlp_fused": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "mst_block_fused_scratch_bytes": (_sz, []),
@@ -273,6 +276,53 @@ def attention_probs_full(qkv: torch.Tensor, n_seq: int, N: int, heads: int, head
     _check(load().mst_attention_probs_full(ptr(qkv), dt_of(qkv), n_seq, N, heads, head_dim, ptr(out), stream_of(qkv)),
            "mst_attention_probs_full")
     return out
+
+
+def _train_attn_args(qkv16: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int, what: str):
+    _dev(qkv16, what)
+    if qkv16.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what}: qkv16 must be bf16 or fp16 (got {qkv16.dtype})")
+    if n_seq < 1 or N < 1 or heads < 1 or tuple(qkv16.shape) != (n_seq * N, 3 * heads * head_dim):
+        raise ValueError(f"{what}: qkv16 {tuple(qkv16.shape)} is not [n_seq*N, 3*heads*head_dim] for n_seq={n_seq} N={N} heads={heads} "
+                         f"head_dim={head_dim}")
+
+
+def _f32_like(t: torch.Tensor, shape, dev, what: str, name: str):
+    _dev(t, what)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError(f"{what}: {name} must be fp32 {tuple(shape)} on {dev} (got {t.dtype} {tuple(t.shape)} on {t.device})")
+
+
+def attention_train_fwd(qkv16: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int = 64) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mst_attention_train_fwd: (out fp32 [n_seq*N, heads*head_dim], lse fp32 [n_seq, heads, N], natural log) of the training step's
+    memory-efficient attention on 16-bit packed q | k | v rows (q pre-scaled)."""
+    _train_attn_args(qkv16, n_seq, N, heads, head_dim, "attention_train_fwd")
+    out = torch.empty((n_seq * N, heads * head_dim), dtype=torch.float32, device=qkv16.device)
+    lse = torch.empty((n_seq, heads, N), dtype=torch.float32, device=qkv16.device)
+    _check(load().mst_attention_train_fwd(ptr(qkv16), dt_of(qkv16), n_seq, N, heads, head_dim, ptr(out), ptr(lse), stream_of(qkv16)),
+           "mst_attention_train_fwd")
+    return out, lse
+
+
+def attention_train_bwd(qkv16: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, n_seq: int, N: int, heads: int,
+                        dq_scale: float = 1.0, head_dim: int = 64, dqkv: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mst_attention_train_bwd: the gradient of the packed rows, dqkv fp32 [n_seq*N, 3*heads*head_dim] (dQ times dq_scale), from the
+    forward's qkv16 / out / lse and dout = d out.  Every element of dqkv is written; no [N, N] tensor is allocated."""
+    what = "attention_train_bwd"
+    _train_attn_args(qkv16, n_seq, N, heads, head_dim, what)
+    dev = qkv16.device
+    _f32_like(out, (n_seq * N, heads * head_dim), dev, what, "out")
+    _f32_like(dout, (n_seq * N, heads * head_dim), dev, what, "dout")
+    _f32_like(lse, (n_seq, heads, N), dev, what, "lse")
+    if dqkv is None:
+        dqkv = torch.empty((n_seq * N, 3 * heads * head_dim), dtype=torch.float32, device=dev)
+    _f32_like(dqkv, (n_seq * N, 3 * heads * head_dim), dev, what, "dqkv")
+    lib = load()
+    nb = int(lib.mst_attention_train_bwd_workspace_bytes(n_seq, N, heads, head_dim))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    _check(lib.mst_attention_train_bwd(ptr(qkv16), dt_of(qkv16), ptr(out), ptr(dout), ptr(lse), n_seq, N, heads, head_dim, dq_scale,
+                                       ptr(dqkv), ptr(ws), nb, stream_of(qkv16)), "mst_attention_train_bwd")
+    return dqkv
 
 
 def pos_embed_interp(pos_patch: torch.Tensor, M: int, gh: int, gw: int, offset: float = 0.1,

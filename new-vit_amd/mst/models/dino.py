@@ -15,6 +15,10 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
   train_precision 'fp32' (default) | 'bf16' | 'fp16': MFMA operand type of the blocks' nn.Linear products in the TRAINING step
                   (forward and backward; fp32 accumulation, fp32 storage and every other op fp32): the reference trains under
                   Trainer(precision='16-mixed') (scripts/main_train.py:110-123).  fp32 is the exact mode the gradient parity bar is on.
+  train_attention 'stored' (default) | 'flash' (env MST_TRAIN_ATTENTION): how the encoder blocks' attention trains.  'stored' keeps
+                  the fp32 [n, heads, N, N] probabilities until the backward; 'flash' (needs train_precision 'bf16' / 'fp16', same
+                  16-bit type) keeps the 16-bit q | k | v, the output and the per-row log-sum-exp and recomputes the probabilities
+                  per tile in the backward, like the reference's MemEffAttention.  ValueError with fp32 or an unknown value.
   chunk_slices    slices encoded per pass (activations of a pass sized for the Infinity Cache).
   full_attention_maps  keep the complete [n,h,N,N] softmax of every block on ``save_attn`` (needed
                   only by ``get_attention_cls``); default keeps the CLS rows ([n,h,1,N]) only.
@@ -195,6 +199,14 @@ class _SliceFusion(_Params):  # nn.TransformerEncoder(num_layers=1, norm=LayerNo
         self.norm = _ln(E)
 
 
+def _check_train_attention(train_attention: str, train_precision: str) -> None:
+    if train_attention not in ("stored", "flash"):
+        raise ValueError(f"train_attention must be 'stored' or 'flash' (got {train_attention!r})")
+    if train_attention == "flash" and train_precision not in ("bf16", "fp16"):
+        raise ValueError("train_attention='flash' runs on 16-bit MFMA operands: it needs train_precision 'bf16' or 'fp16' "
+                         f"(got {train_precision!r}; the fp32 step is the exact-parity mode and keeps the stored probabilities)")
+
+
 # ------------------------------------------------------------------------------------------------
 class DinoV2ClassifierSlice(BasicClassifier):
     def __init__(self, in_ch, out_ch, spatial_dims=2, pretrained=True, save_attn=False,
@@ -215,6 +227,10 @@ class DinoV2ClassifierSlice(BasicClassifier):
         train_precision = str(kwargs.pop("train_precision", os.environ.get("MST_TRAIN_PRECISION", "fp32"))).lower()
         if train_precision not in ("fp32", "bf16", "fp16"):
             raise ValueError("train_precision must be 'fp32', 'bf16' or 'fp16'")
+        # opt-in: the encoder blocks' attention in the TRAINING step without the stored [n, heads, N, N] probabilities (the reference's
+        # MemEffAttention): 16-bit flash forward + FlashAttention-2 backward (csrc/k_attn16_train.hip) on train_precision's type
+        train_attention = str(kwargs.pop("train_attention", os.environ.get("MST_TRAIN_ATTENTION", "stored"))).lower()
+        _check_train_attention(train_attention, train_precision)
         if compute_dtype not in hip.DT_NAMES:
             raise ValueError(f"compute_dtype must be one of {sorted(hip.DT_NAMES)}")
         super().__init__(in_ch, out_ch, spatial_dims=spatial_dims, optimizer_kwargs=optimizer_kwargs, **kwargs)
@@ -226,6 +242,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         self.prune_last_block = prune_last_block
         self.use_graph = use_graph
         self.train_precision = train_precision
+        self.train_attention = train_attention
         self._graphs = {}
         self.save_attn = save_attn
         self.attention_maps = []

@@ -10,9 +10,14 @@ backward produces the gradient of every parameter with the kernels of csrc/k_tra
 Default: everything in exact fp32 (fp32 MFMA), whatever ``compute_dtype`` the inference path uses -- the mode the gradient parity bar
 (1e-3 against autograd of the CPU oracle on every parameter, tests/test_train_gpu.py) is on.  ``train_precision='fp16' | 'bf16'`` (the
 reference's Trainer(precision='16-mixed'), scripts/main_train.py:110-123) runs the blocks' nn.Linear products -- forward, d input, d weight
--- on 16-bit MFMA operands with fp32 accumulation; every other op and everything stored stays fp32.  The attention probabilities of every
-block are kept ([n, heads, N, N] fp32: 2.9 GB per block at 64 x 518^2 -- sized for 288 GB of HBM).  RoPE slice transformers and
-register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn`` inside a training forward.
+-- on 16-bit MFMA operands with fp32 accumulation; every other op and everything stored stays fp32.  By default
+(``train_attention='stored'``) the attention probabilities of every block are kept ([n, heads, N, N] fp32: 2.9 GB per block at
+64 x 518^2).  ``train_attention='flash'`` (16-bit train_precision only, ValueError otherwise) is the reference's MemEffAttention: the
+encoder blocks keep the 16-bit q | k | v (written so by the QKV GEMM), the fp32 output and the per-row log-sum-exp instead, and the
+backward recomputes the probabilities per tile (csrc/k_attn16_train.hip: 16-bit flash forward, FlashAttention-2 backward with a
+separate deterministic dQ pass); no [N, N] tensor exists.  The across-slice transformer's attention always stays on the stored path.
+RoPE slice transformers and register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn``
+inside a training forward.
 """
 from __future__ import annotations
 
@@ -36,13 +41,26 @@ def _mp(model) -> Optional[torch.dtype]:
     return _MP[getattr(model, "train_precision", "fp32")]
 
 
-def _lin_fwd(x: torch.Tensor, lin, mp: Optional[torch.dtype] = None, keep: Optional[dict] = None, **kw) -> torch.Tensor:
+def _flash(model, mp: Optional[torch.dtype]) -> bool:
+    """train_attention of the encoder blocks: 'stored' (default) keeps the fp32 probabilities, 'flash' recomputes them per tile in the
+    backward (mst_attention_train_fwd / _bwd) and needs a 16-bit train_precision.  Re-checked here: the attributes may have been changed
+    after construction."""
+    ta = getattr(model, "train_attention", "stored")
+    if ta not in ("stored", "flash"):
+        raise ValueError(f"train_attention must be 'stored' or 'flash' (got {ta!r})")
+    if ta == "flash" and mp is None:
+        raise ValueError("train_attention='flash' needs train_precision 'bf16' or 'fp16' (the fp32 step keeps the stored probabilities)")
+    return ta == "flash"
+
+
+def _lin_fwd(x: torch.Tensor, lin, mp: Optional[torch.dtype] = None, keep: Optional[dict] = None,
+             out_dtype: torch.dtype = torch.float32, **kw) -> torch.Tensor:
     if mp is None:
         return hip.gemm(x, lin.weight.detach(), lin.bias.detach(), **kw)
     x16 = hip.cvt16(x, mp)
     if keep is not None and x.shape[0] <= 12288:         # the weight gradient of this product reads the same image (mst_conv_wgrad16 path)
         keep[id(lin)] = x16
-    return hip.gemm(x16, hip.cvt16(lin.weight.detach(), mp), lin.bias.detach(), out_dtype=torch.float32, **kw)
+    return hip.gemm(x16, hip.cvt16(lin.weight.detach(), mp), lin.bias.detach(), out_dtype=out_dtype, **kw)
 
 
 class _Grads:
@@ -274,12 +292,19 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     # ---- blocks (block.py:89-114)
     blocks = []
     mp = _mp(model)
+    flash = _flash(model, mp)
     for blk in enc.block_list():
         s = {"x0": xt, "x16": {}}
         k16 = s["x16"] if mp is not None else None
         s["xn1"] = hip.layernorm(xt, blk.norm1.weight.detach(), blk.norm1.bias.detach(), 1e-6)
-        s["qkv"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, col_scale=0.125, scale_cols=E)            # q * head_dim^-0.5 (attention.py:60)
-        s["a"], s["P"] = _attention_fwd(s["qkv"], n, N, heads, 64, 1.0, None)
+        if flash:
+            # q | k | v straight in the 16-bit type the attention kernels read; kept with the output and the per-row log-sum-exp instead of
+            # the [n, heads, N, N] probabilities (the backward recomputes them per tile)
+            s["qkv16"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, out_dtype=mp, col_scale=0.125, scale_cols=E)
+            s["a"], s["lse"] = hip.attention_train_fwd(s["qkv16"], n, N, heads)
+        else:
+            s["qkv"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, col_scale=0.125, scale_cols=E)        # q * head_dim^-0.5 (attention.py:60)
+            s["a"], s["P"] = _attention_fwd(s["qkv"], n, N, heads, 64, 1.0, None)
         s["br1"] = _lin_fwd(s["a"], blk.attn.proj, mp, k16)
         x1 = xt.clone()
         hip.axpby_cols(s["br1"], x1, g=blk.ls1.gamma.detach() if hasattr(blk, "ls1") else None)
@@ -379,7 +404,10 @@ def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
             dbr = torch.empty_like(dx1)
             hip.axpby_cols(dx1, dbr, g=blk.ls1.gamma.detach(), beta=0.0)
         da = G.lin_bwd(dbr, s["a"], blk.attn.proj, X16=x16.get(id(blk.attn.proj)))
-        dqkv = _attention_bwd(da, s["qkv"], s["P"], n, N, heads, 64, 1.0, 0.125)
+        if "lse" in s:                                   # train_attention='flash': dQ carries the epilogue's factor like _attention_bwd's q_scale
+            dqkv = hip.attention_train_bwd(s["qkv16"], s["a"], da, s["lse"], n, N, heads, dq_scale=0.125)
+        else:
+            dqkv = _attention_bwd(da, s["qkv"], s["P"], n, N, heads, 64, 1.0, 0.125)
         dxn1 = G.lin_bwd(dqkv, s["xn1"], blk.attn.qkv, X16=x16.get(id(blk.attn.qkv)))
         dx0 = torch.empty_like(dx)
         G.ln_bwd(s["x0"], E, blk.norm1, dxn1, E, dx1, E, dx0, E, M, E, 1e-6)

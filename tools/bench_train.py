@@ -75,6 +75,42 @@ def backward_rooflines():
     line("ResNet-34 mixed step: d input of that convolution (implicit GEMM, gathered LDS-DMA)", "conv16_kernel", fl, ev(lambda: hip.conv_dgrad(dz16.view(n, H, H, C), wt, k, 1, 1, H, H), 5), 2500.0, "bf16")
 
 
+def attention_rooflines():
+    """`roofline` lines for the memory-efficient training attention (csrc/k_attn16_train.hip) at the encoder shapes of 2 x 32 x 224^2 and
+    64 x 518^2 (64 sequences x 6 heads): algorithmic FLOPs only (forward 4 n h N^2 64, backward 8 n h N^2 64 -- the recomputed S and dP are
+    not credited) against the dense 16-bit MFMA peak."""
+    from mst import hip
+
+    def ev(fn, n=10):
+        for _ in range(2):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for N in (257, 1370):
+        n, h = 64, 6
+        for dt, nm in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
+            x = torch.randn(n * N, 3, h, 64, device="cuda", generator=g)
+            x[:, 0] *= 0.125
+            qkv = x.view(n * N, 3 * h * 64).to(dt)
+            out, lse = hip.attention_train_fwd(qkv, n, N, h)
+            dout = torch.randn_like(out)
+            dqkv = torch.empty(n * N, 3 * h * 64, device="cuda")
+            for kernel, fl, fn in (("attn_train_fwd_kernel", 4.0 * n * h * N * N * 64, lambda: hip.attention_train_fwd(qkv, n, N, h)),
+                                   ("attn_train_pre + dkv + dq kernels", 8.0 * n * h * N * N * 64,
+                                    lambda: hip.attention_train_bwd(qkv, out, dout, lse, n, N, h, 0.125, dqkv=dqkv))):
+                ms = ev(fn)
+                tf = fl / ms / 1e9
+                print(json.dumps({"case": f"DINOv2 flash training attention {n} x {h} heads x N={N}", "roofline": {
+                    "kernel": kernel, "bound": "mfma", "achieved": round(tf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 3),
+                    "flops_per_launch": fl, "avg_launch_ms": round(ms, 4), "dtype": nm}}), flush=True)
+
+
 def train_case(name, model, shape, n=5):
     model = model.cuda().train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-5)
@@ -102,14 +138,22 @@ def train_case(name, model, shape, n=5):
 def main():
     if "--rooflines" in sys.argv:
         backward_rooflines()
+        attention_rooflines()
         return
-    dino_shapes = ((1, 1, 16, 224, 224),) if "--only-dino-c1" in sys.argv else ((2, 1, 32, 224, 224),) if "--only-dino-2x32" in sys.argv else ((1, 1, 16, 224, 224), (2, 1, 32, 224, 224))
+    # --train-attention flash: the encoder blocks' attention without stored probabilities (16-bit precisions only; fp32 cases keep 'stored')
+    attn = sys.argv[sys.argv.index("--train-attention") + 1] if "--train-attention" in sys.argv else "stored"
+    dino_shapes = ((1, 1, 16, 224, 224),) if "--only-dino-c1" in sys.argv else ((2, 1, 32, 224, 224),) if "--only-dino-2x32" in sys.argv else \
+        ((1, 1, 64, 518, 518),) if "--only-dino-518" in sys.argv else ((1, 1, 16, 224, 224), (2, 1, 32, 224, 224), (1, 1, 64, 518, 518))
     for shape in (() if "--only-resnet" in sys.argv else dino_shapes):
         for prec in (("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("fp32",)):
-            m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, train_precision=prec)
+            a = attn if prec != "fp32" else "stored"
+            m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, train_precision=prec, train_attention=a)
             m.load_state_dict(synth.synth_state_dict("s", 0))
-            train_case(f"DinoV2ClassifierSlice training step ({prec} linear products, HIP backward)", m, shape)
-    if "--only-dino-c1" in sys.argv or "--only-dino-2x32" in sys.argv:
+            train_case(f"DinoV2ClassifierSlice training step ({prec} linear products, {a} attention, HIP backward)", m, shape,
+                       n=3 if shape[2] >= 64 else 5)
+            del m
+            torch.cuda.empty_cache()
+    if "--only-dino-c1" in sys.argv or "--only-dino-2x32" in sys.argv or "--only-dino-518" in sys.argv:
         return
     for shape in (() if "--c3-only" in sys.argv else ((2, 1, 32, 224, 224),)):
         m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34)
