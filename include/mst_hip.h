@@ -333,6 +333,50 @@ int mst_axpby_cols(const float* x, int64_t x_stride, const float* g, float alpha
 int mst_im2col14(const void* vol, int dtype, int n, int H, int W, float* col, mst_stream_t stream);
 int mst_pos_embed_interp_bwd(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, mst_stream_t stream);
 
+/* Fixed-order (deterministic) forms of every floating-point reduction of the training steps and of mst_znorm: what the Python layer calls
+ * while torch.are_deterministic_algorithms_enabled().  ORDER CONTRACT: for fixed shape arguments (rows, cols, n, H, W, C, M, E, gh, gw,
+ * kernel geometry) the summation order is fixed -- it does not depend on timing, occupancy, which XCD runs a workgroup, strides or pointer
+ * alignment -- so two calls on the same inputs give bit-identical results.  None of them uses a floating-point atomic.  Each reduction
+ * writes per-workgroup partials with plain stores into a caller-given workspace (the library never allocates) of at least
+ * ..._workspace_bytes(shape) bytes (0 is a valid answer: then the workspace may be NULL) and sums them in ascending workgroup order.
+ * The results agree with the atomic forms within fp32 reassociation error; they are not bit-identical to them.
+ * mst_colsum_ordered: out[c] += sum_r a[r][c] * (b ? b[r][c] : 1), as mst_colsum, without its column-count limit (cols < 2^31 / rows
+ *   blocks).  Row blocks of the plan of mst_colsum (about 2,048 workgroups); workspace [row blocks, cols] fp32, none for one row block.
+ * mst_layernorm_bwd_ordered: mst_layernorm_bwd; dx computed exactly as there, d gamma / d beta (+=) through a [workgroups, 2, cols] slab.
+ * mst_batchnorm_train_ordered: mst_batchnorm_train with the ordered column sums of the mean and the variance (its scratch lives in the
+ *   workspace).  mst_batchnorm_bwd_ordered: mst_batchnorm_bwd (dgamma, dbeta +=, zero them first) through a [row blocks, 2, C] slab.
+ * mst_col2im_nhwc_gather: mst_col2im_nhwc (dx +=) as a gather: every input element adds its entries in ascending (ky, kx).  No workspace.
+ * mst_maxpool_bwd_nhwc_gather: mst_maxpool_bwd_nhwc (dx +=; the same first-maximum rule, ties included) as a gather: every input adds the dy
+ *   of the windows whose argument it is in ascending (oy, ox).  Workspace: one byte per window.
+ * mst_pos_embed_interp_bwd_ordered: mst_pos_embed_interp_bwd (dpos +=) as dpos += Wy^T . dout . Wx with the dense clamped tap matrices;
+ *   workspace [gh, M, E] fp32.
+ * mst_znorm_ordered: mst_znorm with fp64 per-workgroup moment partials summed by one workgroup.  Workspace: one double per workgroup. */
+size_t mst_colsum_ordered_workspace_bytes(int64_t rows, int cols);
+int mst_colsum_ordered(const float* a, int64_t a_stride, const float* b, int64_t b_stride, int64_t rows, int cols, float* out,
+                       void* workspace, size_t workspace_bytes, mst_stream_t stream);
+size_t mst_layernorm_bwd_ordered_workspace_bytes(int64_t rows, int cols);
+int mst_layernorm_bwd_ordered(const float* x, int64_t x_stride, const float* gamma, const float* dy, int64_t dy_stride, const float* dres,
+                              int64_t dres_stride, float* dx, int64_t dx_stride, float* dgamma, float* dbeta, int64_t rows, int cols,
+                              float eps, void* workspace, size_t workspace_bytes, mst_stream_t stream);
+size_t mst_batchnorm_train_ordered_workspace_bytes(int64_t rows, int C);
+int mst_batchnorm_train_ordered(const float* z, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
+                                const float* residual, int relu, float* y, float* mean, float* rstd, float* running_mean,
+                                float* running_var, void* workspace, size_t workspace_bytes, mst_stream_t stream);
+size_t mst_batchnorm_bwd_ordered_workspace_bytes(int64_t rows, int C);
+int mst_batchnorm_bwd_ordered(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, int64_t rows, int C,
+                              float* dgamma, float* dbeta, float* dz, void* workspace, size_t workspace_bytes, mst_stream_t stream);
+int mst_col2im_nhwc_gather(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
+                           mst_stream_t stream);
+size_t mst_maxpool_bwd_nhwc_gather_workspace_bytes(int n, int H, int W, int C);
+int mst_maxpool_bwd_nhwc_gather(const float* x, const float* dy, int n, int H, int W, int C, float* dx, void* workspace, size_t workspace_bytes,
+                                mst_stream_t stream);
+size_t mst_pos_embed_interp_bwd_ordered_workspace_bytes(int M, int E, int gh, int gw);
+int mst_pos_embed_interp_bwd_ordered(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, void* workspace,
+                                     size_t workspace_bytes, mst_stream_t stream);
+size_t mst_znorm_ordered_workspace_bytes(int64_t n);
+int mst_znorm_ordered(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, void* workspace, size_t workspace_bytes,
+                      mst_stream_t stream);
+
 /* Optional per-kernel timing of the launches inside mst_vit_encode (bench / profiling only).  A caller-owned object:
  * while mst_vit_weights.profiler points at one, every launch of that call is bracketed by hipEventRecord on the call's own
  * stream; mst_profiler_collect waits for the recorded events, returns the accumulated milliseconds and launch counts per

@@ -285,6 +285,12 @@ int launch_bn_bwd(const float* z, const float* mean, const float* rstd, const fl
     bn_bwd_apply_kernel<<<dim3(cgrid(rows * C)), dim3(256), 0, s>>>(z, mean, rstd, gamma, dy, dgamma, dbeta, rows, C, dz);
     return mst_check_launch("bn_bwd_apply");
 }
+// the second half of launch_bn_bwd on finished d gamma / d beta (the ordered form: mst_batchnorm_bwd_ordered)
+int launch_bn_bwd_apply(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, const float* dgamma,
+                        const float* dbeta, int64_t rows, int C, float* dz, hipStream_t s) {
+    bn_bwd_apply_kernel<<<dim3(cgrid(rows * C)), dim3(256), 0, s>>>(z, mean, rstd, gamma, dy, dgamma, dbeta, rows, C, dz);
+    return mst_check_launch("bn_bwd_apply");
+}
 int launch_col2im_nhwc(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
                        hipStream_t s) {
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1, K = kh * kw * C;

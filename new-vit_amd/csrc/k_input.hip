@@ -249,6 +249,44 @@ __global__ void z_moments_kernel(const float* __restrict__ x, int64_t n, ZState*
     if ((threadIdx.x & 63) == 0) atomicAdd(PASS == 0 ? &st->sum : &st->sq, acc);
 }
 
+// the ordered form (mst_znorm_ordered): workgroup g stores its fp64 partial into slab[g] (waves in ascending order), then one workgroup
+// sums the slab in a fixed order -- the moments of the same shape are bit-identical from run to run
+template <int PASS>
+__global__ __launch_bounds__(256) void z_moments_slab_kernel(const float* __restrict__ x, int64_t n, const ZState* st, double* __restrict__ slab) {
+    __shared__ double red[4];
+    const float mn = st->mn, mx = st->mx, lo = st->cut_lo, hi = st->cut_hi;
+    const float mean = st->mean;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = x[i];
+        if (!(v > mn && v < mx)) continue;
+        const float c = fminf(fmaxf(v, lo), hi);
+        if (PASS == 0) acc += (double)c;
+        else { const double d = (double)c - (double)mean; acc += d * d; }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) slab[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// st->sum (PASS 0) / st->sq (PASS 1) = sum of slab[0..nb): thread t adds t, t + 256, ... in sequence, then a fixed LDS tree
+template <int PASS>
+__global__ __launch_bounds__(256) void z_moments_reduce_kernel(const double* __restrict__ slab, int nb, ZState* st) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int g = threadIdx.x; g < nb; g += 256) acc += slab[g];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (PASS == 0) st->sum = red[0];
+        else st->sq = red[0];
+    }
+}
+
 __global__ void z_finish_kernel(ZState* st, int pass) {
     if (threadIdx.x || st->count == 0) return;
     if (pass == 0) st->mean = (float)(st->sum / (double)st->count);
@@ -290,6 +328,34 @@ int launch_copy_block(const float* src, int sn1, int sn2, int s0, int s1, int s2
     if (n <= 0) return MST_OK;
     copy_block_kernel<<<dim3(sgrid(n)), dim3(256), 0, s>>>(src, sn1, sn2, s0, s1, s2, dst, dn1, dn2, d0, d1, d2, c0, c1, c2);
     return mst_check_launch("copy_block");
+}
+
+size_t znorm_ordered_workspace_bytes(int64_t n) { return n > 0 ? ((size_t)sgrid(n) * sizeof(double) + 255) / 256 * 256 : 0; }
+
+// launch_znorm with the two moment passes in the ordered form (the order statistics and counts are integer work: exact already)
+int launch_znorm_ordered(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, void* ws, size_t ws_bytes, hipStream_t s) {
+    MST_CHECK_ARG(ws && ws_bytes >= znorm_ordered_workspace_bytes(n), "znorm_ordered: workspace of %zu bytes, %zu needed", ws_bytes,
+                  znorm_ordered_workspace_bytes(n));
+    ZState* st = (ZState*)state;
+    double* slab = (double*)ws;
+    const dim3 g(sgrid(n)), b(256);
+    z_init_kernel<<<1, 256, 0, s>>>(st);
+    z_minmax_kernel<<<g, b, 0, s>>>(x, n, st);
+    z_count_kernel<<<g, b, 0, s>>>(x, n, st);
+    z_ranks_kernel<<<1, 64, 0, s>>>(st, q_lo, q_hi);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        z_hist_kernel<<<g, b, 0, s>>>(x, n, st, shift);
+        z_scan_kernel<<<1, 256, 0, s>>>(st, shift);
+    }
+    z_cutoffs_kernel<<<1, 64, 0, s>>>(st, q_lo, q_hi);
+    z_moments_slab_kernel<0><<<g, b, 0, s>>>(x, n, st, slab);
+    z_moments_reduce_kernel<0><<<1, 256, 0, s>>>(slab, (int)g.x, st);
+    z_finish_kernel<<<1, 64, 0, s>>>(st, 0);
+    z_moments_slab_kernel<1><<<g, b, 0, s>>>(x, n, st, slab);
+    z_moments_reduce_kernel<1><<<1, 256, 0, s>>>(slab, (int)g.x, st);
+    z_finish_kernel<<<1, 64, 0, s>>>(st, 1);
+    z_apply_kernel<<<g, b, 0, s>>>(x, y, n, st);
+    return mst_check_launch("znorm_ordered");
 }
 
 int launch_znorm(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, hipStream_t s) {

@@ -54,11 +54,14 @@ __global__ void softmax_rows_bwd_kernel(const float* __restrict__ P, float* __re
 // LayerNorm backward.  One wave per row at a time, waves stride over the rows; d gamma / d beta partial sums live in registers
 // (column c = lane + 64 i, i < CI), meet in LDS at the end and are added to the fp32 outputs with one atomic per column per workgroup.
 //   dx[row] = (dres ? dres[row] : 0) + rstd * (dyg - mean(dyg) - xhat * mean(dyg * xhat)),   dyg = dy * gamma
-template <int CI>
+// SLAB (the ordered form, mst_layernorm_bwd_ordered): no atomic -- workgroup g stores its column sums into slab[g][0 | 1][cols]
+// (d gamma | d beta) with plain stores, and launch_slab_reduce adds the slabs in ascending g.
+template <int CI, bool SLAB = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, int64_t xs, const float* __restrict__ gamma,
                                                             const float* __restrict__ dy, int64_t dys, const float* dres, int64_t drs,
                                                             float* dx, int64_t dxs, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, int64_t rows, int cols, float eps) {
+                                                            float* __restrict__ dbeta, int64_t rows, int cols, float eps,
+                                                            float* __restrict__ slab = nullptr) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (blockDim.x >> 6);
     float gsum[CI], bsum[CI], gm[CI];
@@ -122,6 +125,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         red[wave][1][lane + 64 * i] = bsum[i];
     }
     __syncthreads();
+    if constexpr (SLAB) {
+        float* o = slab + (int64_t)blockIdx.x * 2 * cols;
+        for (int c = threadIdx.x; c < cols; c += 256) {
+            o[c] = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]);
+            o[cols + c] = (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]);
+        }
+        return;
+    }
     for (int c = threadIdx.x; c < cols; c += 256) {
         if (dgamma) atomicAdd(dgamma + c, (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]));
         if (dbeta) atomicAdd(dbeta + c, (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]));
@@ -302,6 +313,32 @@ int launch_layernorm_bwd(const float* x, int64_t xs, const float* gamma, const f
     else LNB(32);
 #undef LNB
     return mst_check_launch("layernorm_bwd");
+}
+
+static unsigned layernorm_bwd_grid(int64_t rows) { return (unsigned)(rows < 16 ? 1 : (rows / 16 < 1024 ? rows / 16 : 1024)); }
+
+size_t layernorm_bwd_ordered_workspace_bytes(int64_t rows, int cols) {
+    return rows > 0 && cols > 0 ? ((size_t)layernorm_bwd_grid(rows) * 2 * cols * sizeof(float) + 255) / 256 * 256 : 0;
+}
+
+int launch_layernorm_bwd_ordered(const float* x, int64_t xs, const float* gamma, const float* dy, int64_t dys, const float* dres, int64_t drs,
+                                 float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, void* ws,
+                                 size_t ws_bytes, hipStream_t s) {
+    MST_CHECK_ARG(cols > 0 && cols <= 2048, "layernorm_bwd_ordered: cols=%d unsupported (<= 2048)", cols);
+    const size_t need = layernorm_bwd_ordered_workspace_bytes(rows, cols);
+    MST_CHECK_ARG(ws && ws_bytes >= need, "layernorm_bwd_ordered: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    const unsigned grid = layernorm_bwd_grid(rows);                     // a function of rows only: so is the summation order
+    float* slab = (float*)ws;
+#define LNB(CI) layernorm_bwd_kernel<CI, true><<<dim3(grid), dim3(256), 0, s>>>(x, xs, gamma, dy, dys, dres, drs, dx, dxs, dgamma, dbeta, rows, cols, eps, slab)
+    if (cols <= 128) LNB(2);
+    else if (cols <= 384) LNB(6);
+    else if (cols <= 768) LNB(12);
+    else if (cols <= 1024) LNB(16);
+    else LNB(32);
+#undef LNB
+    int rc = mst_check_launch("layernorm_bwd_ordered");
+    if (rc || (!dgamma && !dbeta)) return rc;
+    return launch_slab_reduce(slab, grid, 2 * (int64_t)cols, cols, dgamma, dbeta, s);
 }
 
 int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const float* freqs, float sign, hipStream_t s) {

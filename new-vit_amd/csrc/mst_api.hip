@@ -325,6 +325,80 @@ int mst_maxpool_bwd_nhwc(const float* x, const float* dy, int n, int H, int W, i
     MST_CHECK_ARG(x && dy && dx && n > 0, "maxpool_bwd_nhwc: bad arguments");
     return launch_maxpool_bwd_nhwc(x, dy, n, H, W, C, dx, (hipStream_t)stream);
 }
+// ---- fixed-order forms (torch.use_deterministic_algorithms): no floating-point atomics, bit-reproducible for fixed shapes -----------
+static int ws_short(const char* what, size_t have, size_t need) {
+    mst_set_error("%s: workspace of %zu bytes, %zu needed", what, have, need);
+    return MST_EINVAL;
+}
+size_t mst_colsum_ordered_workspace_bytes(int64_t rows, int cols) { return colsum_ordered_workspace_bytes(rows, cols, 1); }
+int mst_colsum_ordered(const float* a, int64_t a_stride, const float* b, int64_t b_stride, int64_t rows, int cols, float* out,
+                       void* workspace, size_t workspace_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(a && out && rows > 0 && cols > 0, "colsum_ordered: bad arguments");
+    return launch_colsum_ordered(a, a_stride, b, b_stride, rows, cols, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t mst_layernorm_bwd_ordered_workspace_bytes(int64_t rows, int cols) { return layernorm_bwd_ordered_workspace_bytes(rows, cols); }
+int mst_layernorm_bwd_ordered(const float* x, int64_t x_stride, const float* gamma, const float* dy, int64_t dy_stride, const float* dres,
+                              int64_t dres_stride, float* dx, int64_t dx_stride, float* dgamma, float* dbeta, int64_t rows, int cols,
+                              float eps, void* workspace, size_t workspace_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(x && dy && rows > 0, "layernorm_bwd_ordered: bad arguments");
+    return launch_layernorm_bwd_ordered(x, x_stride, gamma, dy, dy_stride, dres, dres_stride, dx, dx_stride, dgamma, dbeta, rows, cols, eps,
+                                        workspace, workspace_bytes, (hipStream_t)stream);
+}
+static size_t bn_acc_bytes(int C) { return ((size_t)C * sizeof(float) + 255) / 256 * 256; }
+size_t mst_batchnorm_train_ordered_workspace_bytes(int64_t rows, int C) {
+    return rows > 0 && C > 0 ? bn_acc_bytes(C) + colsum_ordered_workspace_bytes(rows, C, 1) : 0;
+}
+int mst_batchnorm_train_ordered(const float* z, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
+                                const float* residual, int relu, float* y, float* mean, float* rstd, float* running_mean,
+                                float* running_var, void* workspace, size_t workspace_bytes, mst_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    MST_CHECK_ARG(z && gamma && beta && y && mean && rstd && workspace && rows > 0 && C > 0, "batchnorm_train_ordered: bad arguments");
+    const size_t need = mst_batchnorm_train_ordered_workspace_bytes(rows, C);
+    if (workspace_bytes < need) return ws_short("batchnorm_train_ordered", workspace_bytes, need);
+    float* acc = (float*)workspace;                                     // C floats, then the slab of the column sums
+    void* slab = (char*)workspace + bn_acc_bytes(C);
+    const size_t slab_bytes = workspace_bytes - bn_acc_bytes(C);
+    if (hipMemsetAsync(acc, 0, sizeof(float) * C, s) != hipSuccess) { mst_set_error("batchnorm_train_ordered: memset failed"); return MST_ELAUNCH; }
+    int rc = launch_colsum_ordered(z, C, nullptr, 0, rows, C, acc, slab, slab_bytes, s);
+    if (rc) return rc;
+    if ((rc = launch_bn_finalize(0, acc, rows, C, eps, momentum, mean, rstd, nullptr, nullptr, s))) return rc;
+    if (hipMemsetAsync(acc, 0, sizeof(float) * C, s) != hipSuccess) { mst_set_error("batchnorm_train_ordered: memset failed"); return MST_ELAUNCH; }
+    if ((rc = launch_colsqdev_ordered(z, mean, rows, C, acc, slab, slab_bytes, s))) return rc;
+    if ((rc = launch_bn_finalize(1, acc, rows, C, eps, momentum, mean, rstd, running_mean, running_var, s))) return rc;
+    return launch_bn_apply(z, mean, rstd, gamma, beta, residual, relu, rows, C, y, s);
+}
+size_t mst_batchnorm_bwd_ordered_workspace_bytes(int64_t rows, int C) { return colsum_ordered_workspace_bytes(rows, C, 2); }
+int mst_batchnorm_bwd_ordered(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, int64_t rows, int C,
+                              float* dgamma, float* dbeta, float* dz, void* workspace, size_t workspace_bytes, mst_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    MST_CHECK_ARG(z && mean && rstd && gamma && dy && dgamma && dbeta && dz && rows > 0 && C > 0, "batchnorm_bwd_ordered: bad arguments");
+    int rc = launch_bn_bwd_reduce_ordered(z, mean, rstd, dy, rows, C, dgamma, dbeta, workspace, workspace_bytes, s);
+    if (rc) return rc;
+    return launch_bn_bwd_apply(z, mean, rstd, gamma, dy, dgamma, dbeta, rows, C, dz, s);
+}
+int mst_col2im_nhwc_gather(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
+                           mst_stream_t stream) {
+    MST_CHECK_ARG(dcol && dx && n > 0 && H > 0 && W > 0 && C > 0, "col2im_nhwc_gather: bad arguments");
+    return launch_col2im_gather(dcol, n, H, W, C, kh, kw, stride, pad, Kpad, dx, (hipStream_t)stream);
+}
+size_t mst_maxpool_bwd_nhwc_gather_workspace_bytes(int n, int H, int W, int C) { return maxpool_bwd_gather_workspace_bytes(n, H, W, C); }
+int mst_maxpool_bwd_nhwc_gather(const float* x, const float* dy, int n, int H, int W, int C, float* dx, void* workspace, size_t workspace_bytes,
+                                mst_stream_t stream) {
+    MST_CHECK_ARG(x && dy && dx && n > 0 && H > 0 && W > 0 && C > 0, "maxpool_bwd_nhwc_gather: bad arguments");
+    return launch_maxpool_bwd_gather(x, dy, n, H, W, C, dx, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t mst_pos_embed_interp_bwd_ordered_workspace_bytes(int M, int E, int gh, int gw) { return pos_interp_bwd_ordered_workspace_bytes(M, E, gh, gw); }
+int mst_pos_embed_interp_bwd_ordered(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, void* workspace,
+                                     size_t workspace_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(dout && dpos && M > 0 && E > 0 && gh > 0 && gw > 0, "pos_embed_interp_bwd_ordered: bad arguments");
+    return launch_pos_interp_bwd_ordered(dout, M, E, gh, gw, offset, dpos, workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t mst_znorm_ordered_workspace_bytes(int64_t n) { return znorm_ordered_workspace_bytes(n); }
+int mst_znorm_ordered(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, void* workspace, size_t workspace_bytes,
+                      mst_stream_t stream) {
+    MST_CHECK_ARG(x && y && state && n > 0 && q_lo >= 0.f && q_lo <= q_hi && q_hi <= 1.f, "znorm_ordered: bad arguments");
+    return launch_znorm_ordered(x, n, q_lo, q_hi, y, state, workspace, workspace_bytes, (hipStream_t)stream);
+}
 int mst_avgpool_bwd_nhwc(const float* dy, int n, int HW, int C, float* dx, mst_stream_t stream) {
     MST_CHECK_ARG(dy && dx && n > 0 && HW > 0 && C > 0, "avgpool_bwd_nhwc: bad arguments");
     return launch_avgpool_bwd_nhwc(dy, n, HW, C, dx, (hipStream_t)stream);

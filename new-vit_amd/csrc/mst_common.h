@@ -281,6 +281,30 @@ int launch_pad_axis(float* v, int n0, int n1, int n2, int axis, int lo, int hi, 
 int launch_copy_block(const float* src, int sn1, int sn2, int s0, int s1, int s2, float* dst, int dn1, int dn2, int d0, int d1,
                       int d2, int c0, int c1, int c2, hipStream_t s);
 int launch_znorm(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, hipStream_t s);
+// fixed-order reductions (k_ordered.hip, and the ordered forms in k_train.hip / k_conv.hip / k_input.hip): bit-reproducible for fixed
+// shape arguments, no floating-point atomics
+size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs);
+int launch_slab_reduce(const float* slab, int64_t nrb, int64_t width, int64_t split, float* o0, float* o1, hipStream_t s);
+int launch_colsum_ordered(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, void* ws,
+                          size_t ws_bytes, hipStream_t s);
+int launch_colsqdev_ordered(const float* z, const float* mean, int64_t rows, int C, float* out, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_bn_bwd_reduce_ordered(const float* z, const float* mean, const float* rstd, const float* dy, int64_t rows, int C, float* dgamma,
+                                 float* dbeta, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_bn_bwd_apply(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, const float* dgamma,
+                        const float* dbeta, int64_t rows, int C, float* dz, hipStream_t s);
+int launch_col2im_gather(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
+                         hipStream_t s);
+size_t maxpool_bwd_gather_workspace_bytes(int n, int H, int W, int C);
+int launch_maxpool_bwd_gather(const float* x, const float* dy, int n, int H, int W, int C, float* dx, void* ws, size_t ws_bytes, hipStream_t s);
+size_t pos_interp_bwd_ordered_workspace_bytes(int M, int E, int gh, int gw);
+int launch_pos_interp_bwd_ordered(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, void* ws, size_t ws_bytes,
+                                  hipStream_t s);
+size_t layernorm_bwd_ordered_workspace_bytes(int64_t rows, int cols);
+int launch_layernorm_bwd_ordered(const float* x, int64_t xs, const float* gamma, const float* dy, int64_t dys, const float* dres, int64_t drs,
+                                 float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, void* ws,
+                                 size_t ws_bytes, hipStream_t s);
+size_t znorm_ordered_workspace_bytes(int64_t n);
+int launch_znorm_ordered(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_slices2rgb(const void* vol, int dt, int B, int D, int H, int W, void* out, hipStream_t s);
 int launch_mean_slices(const float* x, int B, int D, int E, float* out, hipStream_t s);
 int launch_readout(const float* cls_probs, const float* slice_probs, int B, int D, int heads, int N,

@@ -118,6 +118,22 @@ SIGNATURES = {
     "mst_saliency_upsample": (_i, [_vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
     "mst_liere_rotation": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mst_attention_rollout": (_i, [C.POINTER(_vp), _i, _i64, _i, _vp, _vp, _vp]),
+    # fixed-order forms (torch.use_deterministic_algorithms): no floating-point atomics, caller-given workspace
+    "mst_colsum_ordered_workspace_bytes": (_sz, [_i64, _i]),
+    "mst_colsum_ordered": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
+    "mst_layernorm_bwd_ordered_workspace_bytes": (_sz, [_i64, _i]),
+    "mst_layernorm_bwd_ordered": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _f, _vp, _sz, _vp]),
+    "mst_batchnorm_train_ordered_workspace_bytes": (_sz, [_i64, _i]),
+    "mst_batchnorm_train_ordered": (_i, [_vp, _i64, _i, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mst_batchnorm_bwd_ordered_workspace_bytes": (_sz, [_i64, _i]),
+    "mst_batchnorm_bwd_ordered": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mst_col2im_nhwc_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mst_maxpool_bwd_nhwc_gather_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mst_maxpool_bwd_nhwc_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mst_pos_embed_interp_bwd_ordered_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mst_pos_embed_interp_bwd_ordered": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp]),
+    "mst_znorm_ordered_workspace_bytes": (_sz, [_i64]),
+    "mst_znorm_ordered": (_i, [_vp, _i64, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "mst_profiler_create": (_vp, []),
     "mst_profiler_destroy": (None, [_vp]),
     "mst_profiler_collect": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -170,6 +186,18 @@ def ptr(t: Optional[torch.Tensor]):
 
 def stream_of(t: torch.Tensor):
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def deterministic() -> bool:
+    """torch.use_deterministic_algorithms(True) (warn_only or not) is in force: every floating-point reduction of the training steps and
+    of preprocess.znormalize then takes its fixed-order entry point (mst_*_ordered / *_gather), bit-reproducible for fixed shapes.  Read
+    at every call, so that toggling the flag between steps takes effect."""
+    return torch.are_deterministic_algorithms_enabled()
+
+
+def workspace(nbytes: int, device) -> Optional[torch.Tensor]:
+    """Device scratch of `nbytes` bytes for an entry point's `workspace` argument (None for 0: the library accepts NULL then)."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device) if nbytes else None
 
 
 def _dev(t: torch.Tensor, what: str):
@@ -668,6 +696,13 @@ def layernorm_rows(x: torch.Tensor, x_stride: int, rows: int, cols: int, weight,
 
 
 def layernorm_bwd(x, x_stride, gamma, dy, dy_stride, dres, dres_stride, dx, dx_stride, dgamma, dbeta, rows, cols, eps):
+    if deterministic():
+        lib = load()
+        ws = workspace(lib.mst_layernorm_bwd_ordered_workspace_bytes(rows, cols), x.device)
+        _check(lib.mst_layernorm_bwd_ordered(ptr(x), x_stride, ptr(gamma), ptr(dy), dy_stride, ptr(dres), dres_stride, ptr(dx), dx_stride,
+                                             ptr(dgamma), ptr(dbeta), rows, cols, eps, ptr(ws), 0 if ws is None else ws.numel(), stream_of(x)),
+               "mst_layernorm_bwd_ordered")
+        return
     _check(load().mst_layernorm_bwd(ptr(x), x_stride, ptr(gamma), ptr(dy), dy_stride, ptr(dres), dres_stride, ptr(dx), dx_stride,
                                     ptr(dgamma), ptr(dbeta), rows, cols, eps, stream_of(x)), "mst_layernorm_bwd")
 
@@ -684,8 +719,20 @@ def act_bwd(h: torch.Tensor, dy: torch.Tensor, kind: int) -> torch.Tensor:
 
 
 def colsum(a: torch.Tensor, out: torch.Tensor, b: Optional[torch.Tensor] = None):
+    """out[c] += sum_r a[r][c] * (b ? b[r][c] : 1); a (and b) 2-D with unit column stride (any row stride: a column block of a wider
+    matrix), out contiguous."""
     rows, cols = a.shape
-    _check(load().mst_colsum(ptr(a), cols, ptr(b), cols, rows, cols, ptr(out), stream_of(a)), "mst_colsum")
+    if a.stride(1) != 1 or (b is not None and (b.shape != a.shape or b.stride(1) != 1)) or not out.is_contiguous():
+        raise ValueError("colsum: a / b need unit column strides and equal shapes, out must be contiguous")
+    as_ = a.stride(0) if rows > 1 else cols
+    bs = (b.stride(0) if rows > 1 else cols) if b is not None else cols
+    if deterministic():
+        lib = load()
+        ws = workspace(lib.mst_colsum_ordered_workspace_bytes(rows, cols), a.device)
+        _check(lib.mst_colsum_ordered(ptr(a), as_, ptr(b), bs, rows, cols, ptr(out), ptr(ws), 0 if ws is None else ws.numel(), stream_of(a)),
+               "mst_colsum_ordered")
+        return out
+    _check(load().mst_colsum(ptr(a), as_, ptr(b), bs, rows, cols, ptr(out), stream_of(a)), "mst_colsum")
     return out
 
 
@@ -708,6 +755,12 @@ def im2col14(vol: torch.Tensor) -> torch.Tensor:
 
 def pos_embed_interp_bwd(dout: torch.Tensor, M: int, gh: int, gw: int, offset: float, dpos: torch.Tensor):
     E = dout.shape[-1]
+    if deterministic():
+        lib = load()
+        ws = workspace(lib.mst_pos_embed_interp_bwd_ordered_workspace_bytes(M, E, gh, gw), dout.device)
+        _check(lib.mst_pos_embed_interp_bwd_ordered(ptr(dout), M, E, gh, gw, offset, ptr(dpos), ptr(ws), ws.numel(), stream_of(dout)),
+               "mst_pos_embed_interp_bwd_ordered")
+        return dpos
     _check(load().mst_pos_embed_interp_bwd(ptr(dout), M, E, gh, gw, offset, ptr(dpos), stream_of(dout)), "mst_pos_embed_interp_bwd")
     return dpos
 
@@ -846,6 +899,13 @@ def batchnorm_train(z: torch.Tensor, bn, residual: Optional[torch.Tensor], relu:
     y = torch.empty_like(z)
     mean = torch.empty(Cc, dtype=torch.float32, device=dev)
     rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
+    if deterministic():
+        lib = load()
+        ws = workspace(lib.mst_batchnorm_train_ordered_workspace_bytes(rows, Cc), dev)
+        _check(lib.mst_batchnorm_train_ordered(ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum,
+                                               ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean),
+                                               ptr(bn.running_var), ptr(ws), ws.numel(), stream_of(z)), "mst_batchnorm_train_ordered")
+        return y, mean, rstd
     scratch = torch.empty(Cc, dtype=torch.float32, device=dev)
     _check(load().mst_batchnorm_train(ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum, ptr(residual),
                                       1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var),
@@ -859,6 +919,12 @@ def batchnorm_bwd(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma
     dg = torch.zeros(Cc, dtype=torch.float32, device=z.device)
     db = torch.zeros(Cc, dtype=torch.float32, device=z.device)
     dz = torch.empty_like(z)
+    if deterministic():
+        lib = load()
+        ws = workspace(lib.mst_batchnorm_bwd_ordered_workspace_bytes(rows, Cc), z.device)
+        _check(lib.mst_batchnorm_bwd_ordered(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), rows, Cc, ptr(dg), ptr(db), ptr(dz),
+                                             ptr(ws), 0 if ws is None else ws.numel(), stream_of(z)), "mst_batchnorm_bwd_ordered")
+        return dz, dg, db
     _check(load().mst_batchnorm_bwd(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), rows, Cc, ptr(dg), ptr(db), ptr(dz),
                                     stream_of(z)), "mst_batchnorm_bwd")
     return dz, dg, db
@@ -867,6 +933,10 @@ def batchnorm_bwd(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma
 def col2im_nhwc(dcol: torch.Tensor, dx: torch.Tensor, kh: int, kw: int, stride: int, pad: int):
     """dx [n,H,W,C] += adjoint of im2col_nhwc applied to dcol [n*Ho*Wo, Kpad]."""
     n, H, W, Cc = dx.shape
+    if deterministic():
+        _check(load().mst_col2im_nhwc_gather(ptr(dcol), n, H, W, Cc, kh, kw, stride, pad, dcol.shape[1], ptr(dx), stream_of(dx)),
+               "mst_col2im_nhwc_gather")
+        return dx
     _check(load().mst_col2im_nhwc(ptr(dcol), n, H, W, Cc, kh, kw, stride, pad, dcol.shape[1], ptr(dx), stream_of(dx)), "mst_col2im_nhwc")
     return dx
 
@@ -874,6 +944,12 @@ def col2im_nhwc(dcol: torch.Tensor, dx: torch.Tensor, kh: int, kw: int, stride: 
 def maxpool_bwd_nhwc(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     n, H, W, Cc = x.shape
     dx = torch.zeros_like(x)
+    if deterministic():
+        lib = load()
+        ws = workspace(lib.mst_maxpool_bwd_nhwc_gather_workspace_bytes(n, H, W, Cc), x.device)
+        _check(lib.mst_maxpool_bwd_nhwc_gather(ptr(x), ptr(dy), n, H, W, Cc, ptr(dx), ptr(ws), ws.numel(), stream_of(x)),
+               "mst_maxpool_bwd_nhwc_gather")
+        return dx
     _check(load().mst_maxpool_bwd_nhwc(ptr(x), ptr(dy), n, H, W, Cc, ptr(dx), stream_of(x)), "mst_maxpool_bwd_nhwc")
     return dx
 

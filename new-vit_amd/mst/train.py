@@ -18,6 +18,12 @@ backward recomputes the probabilities per tile (csrc/k_attn16_train.hip: 16-bit 
 separate deterministic dQ pass); no [N, N] tensor exists.  The across-slice transformer's attention always stays on the stored path.
 RoPE slice transformers and register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn``
 inside a training forward.
+
+Determinism: while ``torch.use_deterministic_algorithms(True)`` is set (``warn_only`` too; read at every call, so it may be toggled
+between steps) every floating-point reduction of the step -- bias / LayerScale / token / pos-embed column sums, the split-K weight-gradient
+partials, LayerNorm d gamma / d beta, the bicubic pos-embed adjoint -- takes its fixed-order entry point (csrc/k_ordered.hip: per-workgroup
+slabs summed in ascending order, no floating-point atomics), and two steps on the same state and inputs give bit-identical logits, loss and
+gradients.  Flag off: the atomic kernels, as before.
 """
 from __future__ import annotations
 
@@ -239,7 +245,7 @@ def fusion_bwd(G: "_Grads", model, t, dfeat: torch.Tensor, B: int, D: int, e: in
     dxs = torch.empty_like(dxs2)
     G.ln_bwd(t["xs"], e, lay.norm1, dy1, e, dxs1, e, dxs, e, B * L, e, 1e-5)
     dcls = torch.zeros(e, dtype=torch.float32, device=dev)
-    hip._check(hip.load().mst_colsum(hip.ptr(dxs), L * e, None, 0, B, e, hip.ptr(dcls), hip.stream_of(dxs)), "mst_colsum")
+    hip.colsum(dxs.view(B, L * e)[:, :e], dcls)
     G.put(model.cls_token, dcls)
     return dxs.view(B, L, e)[:, 1:].contiguous().view(B * D, e)
 
@@ -414,12 +420,12 @@ def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
         dx = dx0
     # ---- tokens
     dcls = torch.zeros(E, dtype=torch.float32, device=dev)
-    hip._check(hip.load().mst_colsum(hip.ptr(dx), N * E, None, 0, n, E, hip.ptr(dcls), hip.stream_of(dx)), "mst_colsum")
+    hip.colsum(dx.view(n, N * E)[:, :E], dcls)
     G.put(enc.cls_token, dcls.clone())
     if R:                                                # d register_tokens[r] = sum over slices of row 1 + r
         dreg = torch.zeros((R, E), dtype=torch.float32, device=dev)
         for r in range(R):
-            hip._check(hip.load().mst_colsum(hip.ptr(dx) + (1 + r) * E * 4, N * E, None, 0, n, E, hip.ptr(dreg) + r * E * 4, hip.stream_of(dx)), "mst_colsum")
+            hip.colsum(dx.view(n, N * E)[:, (1 + r) * E:(2 + r) * E], dreg[r])
         G.put(enc.register_tokens, dreg.view(1, R, E))
     dpatch = dx.view(n, N, E)[:, 1 + R:].contiguous().view(n * Np, E)
     dposp = torch.zeros(Np * E, dtype=torch.float32, device=dev)

@@ -20,6 +20,11 @@ forward runs the model op by op through the C ABI and whose backward produces ev
 BatchNorm in train mode normalises over ALL (B D) images of the step, so the step is not chunked: activations of the whole batch stay
 resident (fp32 NHWC; about 60 MB per 224^2 image for resnet34 -- sized for 288 GB of HBM; the mixed mode keeps a 16-bit image of every
 convolution input beside it).  Checked against torch.autograd of oracle/resnet_oracle.py on every parameter (tests/test_resnet_gpu.py).
+
+Determinism: under ``torch.use_deterministic_algorithms(True)`` (read at every call) the BatchNorm statistics and their gradients
+(mst_batchnorm_train_ordered / mst_batchnorm_bwd_ordered), the weight-gradient partial sums (mst_colsum_ordered), col2im and the max-pool
+backward (gather forms: every input sums its own contributions in a fixed order) run without floating-point atomics, so a step -- logits,
+loss, gradients, running statistics -- is bit-reproducible.  Flag off: the atomic kernels, as before.
 """
 from __future__ import annotations
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Timings that are NOT the headline, for the record: the training steps (forward + backward through the
-HIP kernels + AdamW) of both model families, and the ViT-B forward on the unfused path.  One JSON line per case."""
+HIP kernels + AdamW) of both model families, and the ViT-B forward on the unfused path.  One JSON line per case.
+--deterministic: torch.use_deterministic_algorithms(True) for every case (the fixed-order reductions; DESIGN.md "Determinism");
+--no-fill on top: torch.utils.deterministic.fill_uninitialized_memory = False, to tell torch's NaN fill from the kernels' cost."""
 import json
 import sys
 import time
@@ -132,10 +134,16 @@ def train_case(name, model, shape, n=5):
     model.eval()
     ms_f = timed(fwd, n)
     print(json.dumps({"case": name, "shape": list(shape), "train_step_ms": round(ms, 2), "eval_forward_ms": round(ms_f, 2),
-                      "volumes_per_s_training": round(shape[0] / ms * 1e3, 2), "peak_GiB": round(peak, 2)}), flush=True)
+                      "volumes_per_s_training": round(shape[0] / ms * 1e3, 2), "peak_GiB": round(peak, 2),
+                      "deterministic": torch.are_deterministic_algorithms_enabled(),
+                      "fill_uninitialized_memory": torch.utils.deterministic.fill_uninitialized_memory}), flush=True)
 
 
 def main():
+    if "--deterministic" in sys.argv:                    # the fixed-order reductions of the training steps (mst.hip.deterministic)
+        torch.use_deterministic_algorithms(True)
+        if "--no-fill" in sys.argv:                      # attribution only: without torch's NaN fill of every torch.empty under the flag
+            torch.utils.deterministic.fill_uninitialized_memory = False
     if "--rooflines" in sys.argv:
         backward_rooflines()
         attention_rooflines()
