@@ -332,6 +332,15 @@ int mst_axpby_cols(const float* x, int64_t x_stride, const float* g, float alpha
                    int64_t rows, int cols, mst_stream_t stream);
 int mst_im2col14(const void* vol, int dtype, int n, int H, int W, float* col, mst_stream_t stream);
 int mst_pos_embed_interp_bwd(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, mst_stream_t stream);
+/* mst_patch_embed_dgrad: gradient of the training step with respect to the input volume -- the adjoint of the grey -> RGB repeat
+ * (mst/models/dino.py:121-127) and of the stride-14 patch convolution (extern/dinov2/layers/patch_embed.py:68-81):
+ *   dvol[s][14 py + i][14 px + j] = sum_e dx[s * tokens_per_image + first_patch_token + py * gw + px][e] * wsum[e][16 i + j]   (i, j < 14)
+ * dx fp32 [n * tokens_per_image, E] (the encoder's token gradient: first_patch_token = 1 + registers; or the patch rows alone,
+ * tokens_per_image = Np, first_patch_token = 0), wsum fp32 [E, 14 * 16] the three channel kernels summed (the one mst_patch_embed reads,
+ * columns 14, 15 of every kernel row unused), dvol fp32 [n, H, W], every pixel written once.  H, W multiples of 14, E a multiple of 16,
+ * dx and wsum 16-byte aligned.  Exact fp32 MFMA, no atomics: bit-reproducible, one entry point for both determinism modes. */
+int mst_patch_embed_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wsum, int n, int H, int W, int E,
+                          float* dvol, mst_stream_t stream);
 
 /* Fixed-order (deterministic) forms of every floating-point reduction of the training steps and of mst_znorm: what the Python layer calls
  * while torch.are_deterministic_algorithms_enabled().  ORDER CONTRACT: for fixed shape arguments (rows, cols, n, H, W, C, M, E, gh, gw,

@@ -246,6 +246,11 @@ int mst_pos_embed_interp_bwd(const float* dout, int M, int E, int gh, int gw, do
     MST_CHECK_ARG(dout && dpos && M > 0 && E > 0 && gh > 0 && gw > 0, "pos_embed_interp_bwd: bad arguments");
     return launch_pos_interp_bwd(dout, M, E, gh, gw, offset, dpos, (hipStream_t)stream);
 }
+int mst_patch_embed_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wsum, int n, int H, int W, int E,
+                          float* dvol, mst_stream_t stream) {
+    MST_CHECK_ARG(dx && wsum && dvol, "patch_embed_dgrad: null pointer");
+    return launch_patch_embed_dgrad(dx, tokens_per_image, first_patch_token, wsum, n, H, W, E, dvol, (hipStream_t)stream);
+}
 
 // ---- convolutional backbone of the ResNet models ------------------------------------------------------------
 int mst_im2col_nhwc(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* col,

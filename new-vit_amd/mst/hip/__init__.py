@@ -84,6 +84,7 @@ SIGNATURES = {
     "mst_axpby_cols": (_i, [_vp, _i64, _vp, _f, _f, _vp, _i64, _i64, _i, _vp]),
     "mst_im2col14": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_pos_embed_interp_bwd": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp]),
+    "mst_patch_embed_dgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_im2col_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_cvt16": (_i, [_vp, _i64, _i64, _i, _f, _vp, _i, _i64, _i, _i64, _vp]),
     "mst_gemm16_splitk": (_i, [_vp, _i, _i64, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i64, _vp]),
@@ -751,6 +752,26 @@ def im2col14(vol: torch.Tensor) -> torch.Tensor:
     col = torch.empty((n * (H // 14) * (W // 14), 196), dtype=torch.float32, device=vol.device)
     _check(load().mst_im2col14(ptr(vol), dt_of(vol), n, H, W, ptr(col), stream_of(vol)), "mst_im2col14")
     return col
+
+
+def patch_embed_dgrad(dx: torch.Tensor, wsum: torch.Tensor, n: int, H: int, W: int, tokens: Optional[int] = None, first: int = 0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient with respect to the grey volume [n, H, W] (fp32) of the patch embedding: dx holds the patch-row gradients, row
+    s * tokens + first + p for patch p of image s (tokens defaults to the patch count: dx is the patch rows alone), wsum is the
+    [E, 14 * 16] channel-summed kernel the forward's mst_patch_embed read.  Every pixel of `out` is written."""
+    _dev(dx, "patch_embed_dgrad")
+    E = wsum.shape[0]
+    Np = (H // 14) * (W // 14)
+    tokens = Np if tokens is None else tokens
+    if (dx.dtype != torch.float32 or not dx.is_contiguous() or dx.numel() != n * tokens * E or wsum.dtype != torch.float32
+            or not wsum.is_contiguous() or tuple(wsum.shape) != (E, 224) or wsum.device != dx.device):
+        raise ValueError(f"patch_embed_dgrad: dx must be contiguous fp32 [{n} * {tokens}, E], wsum contiguous fp32 [E, 224] on its device")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.float32, device=dx.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, H, W) or out.device != dx.device:
+        raise ValueError(f"patch_embed_dgrad: out must be contiguous fp32 [{n}, {H}, {W}] on dx's device")
+    _check(load().mst_patch_embed_dgrad(ptr(dx), tokens, first, ptr(wsum), n, H, W, E, ptr(out), stream_of(dx)), "mst_patch_embed_dgrad")
+    return out
 
 
 def pos_embed_interp_bwd(dout: torch.Tensor, M: int, gh: int, gw: int, offset: float, dpos: torch.Tensor):

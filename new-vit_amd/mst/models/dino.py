@@ -19,6 +19,11 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
                   the fp32 [n, heads, N, N] probabilities until the backward; 'flash' (needs train_precision 'bf16' / 'fp16', same
                   16-bit type) keeps the 16-bit q | k | v, the output and the per-row log-sum-exp and recomputes the probabilities
                   per tile in the backward, like the reference's MemEffAttention.  ValueError with fp32 or an unknown value.
+  Gradients: under torch.enable_grad() the forward returns logits with one autograd node (mst/train.py) when a parameter requires grad,
+                  or when ``source`` is a floating tensor that requires grad (a frozen model: saliency, attribution), ``save_attn`` is off and
+                  the model is not slice-sharded.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
+                  dtype and device).  Such a call computes its logits on the TRAINING forward (fp32, or ``train_precision``'s linear
+                  products), not on ``compute_dtype``.
   chunk_slices    slices encoded per pass (activations of a pass sized for the Infinity Cache).
   full_attention_maps  keep the complete [n,h,N,N] softmax of every block on ``save_attn`` (needed
                   only by ``get_attention_cls``); default keeps the CLS rows ([n,h,1,N]) only.
@@ -614,6 +619,12 @@ class DinoV2ClassifierSlice(BasicClassifier):
                 raise NotImplementedError("save_attn inside a training forward: run the attention read-outs under torch.no_grad()")
             if self._sharding is not None and self._sharding.world_size > 1:
                 raise NotImplementedError("training under slice sharding: use data-parallel ranks (DDP) for the training step")
+            from .. import train
+            return train.forward_with_grad(self, source, src_key_padding_mask, bool(kwargs.get("without_linear", False)))
+        if (torch.is_grad_enabled() and isinstance(source, torch.Tensor) and source.is_floating_point() and source.requires_grad
+                and not save_attn and not (self._sharding is not None and self._sharding.world_size > 1)):
+            # gradient with respect to the input of a frozen model (saliency, attribution, adversarial checks): the same autograd node,
+            # its backward runs the d x chain only and ends in the patch embedding's data gradient (mst_patch_embed_dgrad)
             from .. import train
             return train.forward_with_grad(self, source, src_key_padding_mask, bool(kwargs.get("without_linear", False)))
         x = source.to(self.device)                      # [B, C, D, H, W]  (reference dino.py:121)

@@ -19,16 +19,25 @@ separate deterministic dQ pass); no [N, N] tensor exists.  The across-slice tran
 RoPE slice transformers and register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn``
 inside a training forward.
 
+Source gradient: ``source`` is an input of the node too.  When it requires grad the backward also returns d ``source`` (source's shape,
+dtype and device): the encoder's d x chain, then the patch embedding's data gradient (csrc/k_patch_dgrad.hip: the adjoint of the stride-14
+convolution and of the grey -> RGB repeat, read straight from the patch rows of d x) and the inverse of the forward's channel / slice
+reshape.  A frozen model (no parameter requires grad) reaches this node through models/dino.py when ``source`` requires grad.  The backward
+computes only what is asked for: weight, bias, LayerScale, token and position gradients of parameters whose ``needs_input_grad`` is off are
+skipped (a source-only backward is the d x chain alone), the encoder's d x chain runs if an encoder parameter or ``source`` needs it, and the
+patch-embedding data gradient only for ``source``.
+
 Determinism: while ``torch.use_deterministic_algorithms(True)`` is set (``warn_only`` too; read at every call, so it may be toggled
 between steps) every floating-point reduction of the step -- bias / LayerScale / token / pos-embed column sums, the split-K weight-gradient
 partials, LayerNorm d gamma / d beta, the bicubic pos-embed adjoint -- takes its fixed-order entry point (csrc/k_ordered.hip: per-workgroup
 slabs summed in ascending order, no floating-point atomics), and two steps on the same state and inputs give bit-identical logits, loss and
-gradients.  Flag off: the atomic kernels, as before.
+gradients.  Flag off: the atomic kernels, as before.  The patch embedding's data gradient has no reduction across workgroups (every pixel is
+written once by one workgroup), so one entry point serves both modes.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Set, Tuple
 
 import torch
 
@@ -70,11 +79,17 @@ def _lin_fwd(x: torch.Tensor, lin, mp: Optional[torch.dtype] = None, keep: Optio
 
 
 class _Grads:
-    def __init__(self, mp: Optional[torch.dtype] = None):
+    def __init__(self, mp: Optional[torch.dtype] = None, needed: Optional[Set[int]] = None):
         self.by_param: Dict[int, torch.Tensor] = {}
         self.mp = mp
+        self.needed = needed                             # ids of the parameters whose gradient is asked for (None: all)
+
+    def need(self, param) -> bool:
+        return param is not None and (self.needed is None or id(param) in self.needed)
 
     def put(self, param, g: torch.Tensor):
+        if not self.need(param):
+            return
         g = g.reshape(param.shape)
         if id(param) in self.by_param:
             hip.axpby_cols(g.reshape(1, -1), self.by_param[id(param)].reshape(1, -1))
@@ -82,12 +97,26 @@ class _Grads:
             self.by_param[id(param)] = g
 
     def lin_bwd(self, dY: torch.Tensor, X: torch.Tensor, lin, need_dx: bool = True, X16: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
-        """nn.Linear backward: d weight = dY^T . X, d bias = column sums of dY, returns dX = dY . W."""
+        """nn.Linear backward: d weight = dY^T . X, d bias = column sums of dY (each only if asked for), returns dX = dY . W."""
         M, N = dY.shape
         K = X.shape[1]
         dev = dY.device
         if self.mp is not None and N % 128 == 0 and K % 128 == 0 and M >= 64:
             return self._lin_bwd_16(dY, X, lin, need_dx, X16)
+        if self.need(lin.weight):
+            self._dw(dY, X, lin)
+        if self.need(getattr(lin, "bias", None)):
+            self.put(lin.bias, hip.colsum(dY, torch.zeros(N, dtype=torch.float32, device=dev)))
+        if not need_dx:
+            return None
+        dX = torch.empty((M, K), dtype=torch.float32, device=dev)
+        hip.gemm_ex(dY, lin.weight.detach(), dX, M, K, N, sa=(N, 1), sb=(K, 1), sc=(K, 1))
+        return dX
+
+    def _dw(self, dY: torch.Tensor, X: torch.Tensor, lin):
+        M, N = dY.shape
+        K = X.shape[1]
+        dev = dY.device
         # d weight: an [N, K] output reduced over M rows is 36-144 tiles walking thousands of rows each; split the rows into up to
         # 16 slabs (more workgroups than CUs), partial products reduced by mst_colsum
         sp = next((d for d in (16, 8, 4, 2) if M % d == 0 and M // d >= 64), 1)
@@ -100,13 +129,6 @@ class _Grads:
             dW = torch.empty((N, K), dtype=torch.float32, device=dev)
             hip.gemm_ex(dY, X, dW, N, K, M, sa=(1, N), sb=(K, 1), sc=(K, 1))
         self.put(lin.weight, dW)
-        if getattr(lin, "bias", None) is not None:
-            self.put(lin.bias, hip.colsum(dY, torch.zeros(N, dtype=torch.float32, device=dev)))
-        if not need_dx:
-            return None
-        dX = torch.empty((M, K), dtype=torch.float32, device=dev)
-        hip.gemm_ex(dY, lin.weight.detach(), dX, M, K, N, sa=(N, 1), sb=(K, 1), sc=(K, 1))
-        return dX
 
     def _lin_bwd_16(self, dY: torch.Tensor, X: torch.Tensor, lin, need_dx: bool, X16: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """The same three results on 16-bit MFMA operands (fp32 accumulation, fp32 results): operands are rounded into scratch images right
@@ -116,13 +138,14 @@ class _Grads:
         dev = dY.device
         mp = self.mp
         dY16 = hip.cvt16(dY, mp)
-        if M <= 12288:
+        want_dw = self.need(lin.weight)
+        if want_dw and M <= 12288:
             # d weight = dY^T . X is the weight gradient of a 1 x 1 "convolution" over M one-pixel images: mst_conv_wgrad16 reads both operands
             # row-major (token-major) and transposes the fragments in the LDS read -- no transposed operand images, token-split partial
             # products (1 x 16 x 224^2: 14.4 -> 10.9 ms per step against the form below)
             x16 = X16 if (X16 is not None and X16.dtype == mp and X16.shape == X.shape) else hip.cvt16(X, mp)   # the forward's image, if it was kept
             self.put(lin.weight, hip.conv_wgrad(dY16, x16.view(M, 1, 1, K), 1, 1, 0))
-        else:
+        elif want_dw:
             # many tokens: TRANSPOSED operand images (both operands contiguous along the token index) through the 128 x 128 x 64 GEMM with
             # 16-byte fragment reads, split over the tokens (mst_gemm16_splitk): 3 % faster at 16,448 tokens than the transposing reads
             tiles = (N // 128) * (K // 128)
@@ -130,7 +153,7 @@ class _Grads:
             kc = -(-M // (sp * 64)) * 64                                 # token rows per split, a multiple of the K-step
             part = hip.gemm16_splitk(hip.cvt16(dY, mp, transpose=True, rows_pad=kc * sp), hip.cvt16(X, mp, transpose=True, rows_pad=kc * sp), sp)
             self.put(lin.weight, hip.colsum(part.view(sp, N * K), torch.zeros(N * K, dtype=torch.float32, device=dev)).view(N, K))
-        if getattr(lin, "bias", None) is not None:
+        if self.need(getattr(lin, "bias", None)):
             self.put(lin.bias, hip.colsum(dY, torch.zeros(N, dtype=torch.float32, device=dev)))
         if not need_dx:
             return None
@@ -139,11 +162,13 @@ class _Grads:
 
     def ln_bwd(self, x, x_stride, ln, dy, dy_stride, dres, dres_stride, dx, dx_stride, rows, cols, eps):
         dev = dy.device
-        dg = torch.zeros(cols, dtype=torch.float32, device=dev)
-        db = torch.zeros(cols, dtype=torch.float32, device=dev)
+        dg = torch.zeros(cols, dtype=torch.float32, device=dev) if self.need(ln.weight) else None
+        db = torch.zeros(cols, dtype=torch.float32, device=dev) if self.need(ln.bias) else None
         hip.layernorm_bwd(x, x_stride, ln.weight.detach(), dy, dy_stride, dres, dres_stride, dx, dx_stride, dg, db, rows, cols, eps)
-        self.put(ln.weight, dg)
-        self.put(ln.bias, db)
+        if dg is not None:
+            self.put(ln.weight, dg)
+        if db is not None:
+            self.put(ln.bias, db)
 
 
 def _attention_fwd(qkv: torch.Tensor, nb: int, L: int, heads: int, hd: int, alpha: float, mask: Optional[torch.Tensor]):
@@ -236,17 +261,20 @@ def fusion_bwd(G: "_Grads", model, t, dfeat: torch.Tensor, B: int, D: int, e: in
     if t["rope"] is not None:
         hip.rope_rows(dqkv, L, hs, hd, t["rope"], -1.0)    # adjoint of the rotation: gradients of the un-rotated projections
     sa = lay.self_attn
-    dW = torch.empty_like(sa.in_proj_weight)
-    hip.gemm_ex(dqkv, t["y1"], dW, 3 * e, e, B * L, sa=(1, 3 * e), sb=(e, 1), sc=(e, 1))
-    G.put(sa.in_proj_weight, dW)
-    G.put(sa.in_proj_bias, hip.colsum(dqkv, torch.zeros(3 * e, dtype=torch.float32, device=dev)))
+    if G.need(sa.in_proj_weight):
+        dW = torch.empty_like(sa.in_proj_weight)
+        hip.gemm_ex(dqkv, t["y1"], dW, 3 * e, e, B * L, sa=(1, 3 * e), sb=(e, 1), sc=(e, 1))
+        G.put(sa.in_proj_weight, dW)
+    if G.need(sa.in_proj_bias):
+        G.put(sa.in_proj_bias, hip.colsum(dqkv, torch.zeros(3 * e, dtype=torch.float32, device=dev)))
     dy1 = torch.empty((B * L, e), dtype=torch.float32, device=dev)
     hip.gemm_ex(dqkv, sa.in_proj_weight.detach(), dy1, B * L, e, 3 * e, sa=(3 * e, 1), sb=(e, 1), sc=(e, 1))
     dxs = torch.empty_like(dxs2)
     G.ln_bwd(t["xs"], e, lay.norm1, dy1, e, dxs1, e, dxs, e, B * L, e, 1e-5)
-    dcls = torch.zeros(e, dtype=torch.float32, device=dev)
-    hip.colsum(dxs.view(B, L * e)[:, :e], dcls)
-    G.put(model.cls_token, dcls)
+    if G.need(model.cls_token):
+        dcls = torch.zeros(e, dtype=torch.float32, device=dev)
+        hip.colsum(dxs.view(B, L * e)[:, :e], dcls)
+        G.put(model.cls_token, dcls)
     return dxs.view(B, L, e)[:, 1:].contiguous().view(B * D, e)
 
 
@@ -266,7 +294,7 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     vol = x.reshape(B * D, H, W).float().contiguous()
     assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
     assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
-    sv = {"B": B, "D": D, "H": H, "W": W, "vol": vol, "without_linear": without_linear}
+    sv = {"B": B, "D": D, "H": H, "W": W, "vol": vol, "without_linear": without_linear, "src_shape": (B, C, D0, H, W)}
     E, heads = enc.embed_dim, enc.num_heads
     n = B * D
     gh, gw = H // PATCH, W // PATCH
@@ -294,6 +322,7 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     w = enc.patch_embed.proj.weight.detach()
     for c in range(3):
         hip.axpby_cols(w[:, c].contiguous().view(E * PATCH, PATCH), wsum, x_stride=PATCH, y_stride=16, rows=E * PATCH, cols=PATCH)
+    sv["wsum"] = wsum                                    # the source gradient's kernel (mst_patch_embed_dgrad) reads the same sum
     xt = hip.patch_embed(vol, wsum, enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
     # ---- blocks (block.py:89-114)
     blocks = []
@@ -355,8 +384,11 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     return _lin_fwd(feat, model.linear), sv
 
 
-def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
-    G = _Grads()
+def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = None,
+                   need_src: bool = False) -> Tuple[Dict[int, torch.Tensor], Optional[torch.Tensor]]:
+    """Gradients of the parameters whose id is in `needed` (None: all) and, with `need_src`, of the volume the forward read (fp32
+    [B*D, H, W], the forward's slice order); products whose result nobody asked for are skipped."""
+    G = _Grads(needed=needed)
     enc = model.encoder
     dev = dout.device
     B, D, H, W = sv["B"], sv["D"], sv["H"], sv["W"]
@@ -370,15 +402,15 @@ def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
     else:
         dtok = dfeat[:, None, :].expand(B, D, e).contiguous().view(B * D, e)
         hip.axpby_cols(dtok, dtok, alpha=1.0 / D, beta=0.0)
-    if hasattr(model, "slice_pos_emb"):
+    if hasattr(model, "slice_pos_emb") and G.need(model.slice_pos_emb.weight):
         dp = torch.zeros_like(model.slice_pos_emb.weight)
         acc = torch.zeros(D * e, dtype=torch.float32, device=dev)
         hip.colsum(dtok.view(B, D * e), acc)
         dp[:D].copy_(acc.view(D, e))
         G.put(model.slice_pos_emb.weight, dp)
     demb = G.lin_bwd(dtok, sv["emb"], model.bottleneck) if hasattr(model, "bottleneck") else dtok
-    if not any(p.requires_grad for p in enc.parameters()):
-        return G.by_param                                                        # frozen encoder (dino.py:65-67)
+    if not need_src and not any(p.requires_grad for p in enc.parameters()):
+        return G.by_param, None                                                  # frozen encoder (dino.py:65-67)
     # ---- encoder
     G.mp = _mp(model)                                    # the blocks' nn.Linear products on 16-bit operands, if asked for
     E, heads = enc.embed_dim, enc.num_heads
@@ -394,7 +426,8 @@ def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
         # x2 = x1 + ls2 * fc2(gelu(fc1(norm2 x1)))
         dbr = dx
         if hasattr(blk, "ls2"):
-            G.put(blk.ls2.gamma, hip.colsum(dx, torch.zeros(E, dtype=torch.float32, device=dev), b=s["br2"]))
+            if G.need(blk.ls2.gamma):
+                G.put(blk.ls2.gamma, hip.colsum(dx, torch.zeros(E, dtype=torch.float32, device=dev), b=s["br2"]))
             dbr = torch.empty_like(dx)
             hip.axpby_cols(dx, dbr, g=blk.ls2.gamma.detach(), beta=0.0)
         x16 = s.get("x16", {})
@@ -406,7 +439,8 @@ def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
         # x1 = x0 + ls1 * proj(attn(qkv(norm1 x0)))
         dbr = dx1
         if hasattr(blk, "ls1"):
-            G.put(blk.ls1.gamma, hip.colsum(dx1, torch.zeros(E, dtype=torch.float32, device=dev), b=s["br1"]))
+            if G.need(blk.ls1.gamma):
+                G.put(blk.ls1.gamma, hip.colsum(dx1, torch.zeros(E, dtype=torch.float32, device=dev), b=s["br1"]))
             dbr = torch.empty_like(dx1)
             hip.axpby_cols(dx1, dbr, g=blk.ls1.gamma.detach(), beta=0.0)
         da = G.lin_bwd(dbr, s["a"], blk.attn.proj, X16=x16.get(id(blk.attn.proj)))
@@ -419,53 +453,75 @@ def backward_train(model, sv, dout: torch.Tensor) -> Dict[int, torch.Tensor]:
         G.ln_bwd(s["x0"], E, blk.norm1, dxn1, E, dx1, E, dx0, E, M, E, 1e-6)
         dx = dx0
     # ---- tokens
-    dcls = torch.zeros(E, dtype=torch.float32, device=dev)
-    hip.colsum(dx.view(n, N * E)[:, :E], dcls)
-    G.put(enc.cls_token, dcls.clone())
-    if R:                                                # d register_tokens[r] = sum over slices of row 1 + r
+    dsrc = None
+    if need_src:                                         # d volume straight from the patch rows of dx (adjoint of the grey -> RGB patch embedding)
+        dsrc = hip.patch_embed_dgrad(dx, sv["wsum"], n, H, W, tokens=N, first=1 + R)
+    pe = enc.patch_embed.proj
+    if G.need(enc.cls_token) or G.need(enc.pos_embed):
+        dcls = torch.zeros(E, dtype=torch.float32, device=dev)
+        hip.colsum(dx.view(n, N * E)[:, :E], dcls)
+        G.put(enc.cls_token, dcls.clone())
+    if R and G.need(enc.register_tokens):                # d register_tokens[r] = sum over slices of row 1 + r
         dreg = torch.zeros((R, E), dtype=torch.float32, device=dev)
         for r in range(R):
             hip.colsum(dx.view(n, N * E)[:, (1 + r) * E:(2 + r) * E], dreg[r])
         G.put(enc.register_tokens, dreg.view(1, R, E))
+    if not (G.need(enc.pos_embed) or G.need(pe.bias) or G.need(pe.weight)):
+        return G.by_param, dsrc
     dpatch = dx.view(n, N, E)[:, 1 + R:].contiguous().view(n * Np, E)
-    dposp = torch.zeros(Np * E, dtype=torch.float32, device=dev)
-    hip.colsum(dpatch.view(n, Np * E), dposp)
-    dpos = torch.zeros_like(enc.pos_embed)
-    dpos[0, 0].copy_(dcls)
-    if sv["interp"]:
-        Mg = int(math.isqrt(enc.pos_embed.shape[1] - 1))
-        hip.pos_embed_interp_bwd(dposp.view(Np, E), Mg, gh, gw, 0.1, dpos[0, 1:])
-    else:
-        dpos[0, 1:].copy_(dposp.view(Np, E))
-    G.put(enc.pos_embed, dpos)
-    G.put(enc.patch_embed.proj.bias, hip.colsum(dpatch, torch.zeros(E, dtype=torch.float32, device=dev)))
-    col = hip.im2col14(sv["vol"])
-    dW = torch.empty((E, 196), dtype=torch.float32, device=dev)
-    hip.gemm_ex(dpatch, col, dW, E, 196, n * Np, sa=(1, E), sb=(196, 1), sc=(196, 1))
-    G.put(enc.patch_embed.proj.weight, dW.view(E, 1, PATCH, PATCH).expand(E, 3, PATCH, PATCH).contiguous())
-    return G.by_param
+    if G.need(enc.pos_embed):
+        dposp = torch.zeros(Np * E, dtype=torch.float32, device=dev)
+        hip.colsum(dpatch.view(n, Np * E), dposp)
+        dpos = torch.zeros_like(enc.pos_embed)
+        dpos[0, 0].copy_(dcls)
+        if sv["interp"]:
+            Mg = int(math.isqrt(enc.pos_embed.shape[1] - 1))
+            hip.pos_embed_interp_bwd(dposp.view(Np, E), Mg, gh, gw, 0.1, dpos[0, 1:])
+        else:
+            dpos[0, 1:].copy_(dposp.view(Np, E))
+        G.put(enc.pos_embed, dpos)
+    if G.need(pe.bias):
+        G.put(pe.bias, hip.colsum(dpatch, torch.zeros(E, dtype=torch.float32, device=dev)))
+    if G.need(pe.weight):
+        col = hip.im2col14(sv["vol"])
+        dW = torch.empty((E, 196), dtype=torch.float32, device=dev)
+        hip.gemm_ex(dpatch, col, dW, E, 196, n * Np, sa=(1, E), sb=(196, 1), sc=(196, 1))
+        G.put(pe.weight, dW.view(E, 1, PATCH, PATCH).expand(E, 3, PATCH, PATCH).contiguous())
+    return G.by_param, dsrc
+
+
+def _source_grad(dvol: torch.Tensor, sv, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
+    """Adjoint of the forward's input handling: [B*D, H, W] fp32 -> source's [B, C, D0, H, W] layout (inverse of the
+    permute(0, 2, 1, 3, 4) / reshape), dtype and device."""
+    B, C, D0, H, W = sv["src_shape"]
+    g = dvol.view(B, D0, C, H, W).permute(0, 2, 1, 3, 4) if C != 1 else dvol.view(B, C, D0, H, W)
+    return g.to(device=device, dtype=dtype).contiguous()
 
 
 class _MSTFunction(torch.autograd.Function):
     """One autograd node for the whole model: inputs are the parameters (so that autograd, DDP hooks and optimisers see
-    ordinary ``.grad`` accumulation), output the logits (or features)."""
+    ordinary ``.grad`` accumulation) and the source volume, output the logits (or features)."""
 
     @staticmethod
     def forward(ctx, model, source, mask, without_linear, *params):
         with torch.no_grad():
             out, saved = forward_train(model, source, mask, without_linear)
         ctx.model, ctx.saved, ctx.params = model, saved, params
+        ctx.src_dtype, ctx.src_device = source.dtype, source.device
         return out
 
     @staticmethod
     def backward(ctx, dout):
+        needed = {id(p) for p, need in zip(ctx.params, ctx.needs_input_grad[4:]) if need}
+        need_src = bool(ctx.needs_input_grad[1])
         with torch.no_grad():
-            grads = backward_train(ctx.model, ctx.saved, dout.contiguous().float())
+            grads, dvol = backward_train(ctx.model, ctx.saved, dout.contiguous().float(), needed, need_src)
+            dsrc = _source_grad(dvol, ctx.saved, ctx.src_dtype, ctx.src_device) if need_src else None
         ctx.saved = None
         out: List[Optional[torch.Tensor]] = []
         for p, need in zip(ctx.params, ctx.needs_input_grad[4:]):
             out.append(grads.get(id(p)) if need else None)
-        return (None, None, None, None, *out)
+        return (None, dsrc, None, None, *out)
 
 
 def forward_with_grad(model, source, mask, without_linear: bool):

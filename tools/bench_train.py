@@ -2,7 +2,8 @@
 """Timings that are NOT the headline, for the record: the training steps (forward + backward through the
 HIP kernels + AdamW) of both model families, and the ViT-B forward on the unfused path.  One JSON line per case.
 --deterministic: torch.use_deterministic_algorithms(True) for every case (the fixed-order reductions; DESIGN.md "Determinism");
---no-fill on top: torch.utils.deterministic.fill_uninitialized_memory = False, to tell torch's NaN fill from the kernels' cost."""
+--no-fill on top: torch.utils.deterministic.fill_uninitialized_memory = False, to tell torch's NaN fill from the kernels' cost.
+--input-grad: the source-gradient timings (input_grad_cases)."""
 import json
 import sys
 import time
@@ -113,6 +114,67 @@ def attention_rooflines():
                     "flops_per_launch": fl, "avg_launch_ms": round(ms, 4), "dtype": nm}}), flush=True)
 
 
+def input_grad_cases():
+    """--input-grad: gradients with respect to the source volume (mst_patch_embed_dgrad + the encoder's d x chain).  Per case one JSON line
+    with the full step (parameters and source), the same step without the source gradient, and a frozen-parameter source-only backward
+    (saliency); then a `roofline` line for mst_patch_embed_dgrad alone (HIP events) against the fp32 MFMA peak (157 TF) and HBM (8 TB/s)."""
+    from mst import hip
+
+    def ev(fn, n=20):
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n
+    for shape, prec, attn in (((2, 1, 32, 224, 224), "fp16", "flash"), ((1, 1, 64, 518, 518), "fp16", "flash")):
+        m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, train_precision=prec, train_attention=attn)
+        m.load_state_dict(synth.synth_state_dict("s", 0))
+        m = m.cuda().train()
+        src = synth.synth_volume(shape, 3).cuda()
+        tgt = torch.arange(shape[0]).cuda() % 2
+        reps = 3 if shape[2] >= 64 else 5
+
+        def step(with_src):
+            m.zero_grad(set_to_none=True)
+            x = src.clone().requires_grad_(with_src)
+            torch.nn.functional.cross_entropy(m(x), tgt).backward()
+        ms_params = timed(lambda: step(False), reps)
+        ms_full = timed(lambda: step(True), reps)
+        m.requires_grad_(False)
+        m.eval()
+
+        def saliency():
+            x = src.clone().requires_grad_(True)
+            torch.autograd.grad(m(x)[:, 1].sum(), x)
+        ms_src = timed(saliency, reps)
+        print(json.dumps({"case": f"DinoV2ClassifierSlice input gradient ({prec} linear products, {attn} attention)", "shape": list(shape),
+                          "step_params_ms": round(ms_params, 2), "step_params_and_source_ms": round(ms_full, 2),
+                          "frozen_source_only_fwd_bwd_ms": round(ms_src, 2)}), flush=True)
+        del m
+        torch.cuda.empty_cache()
+        # the kernel alone at this shape: ViT-S/14 (E 384) and, for scale, ViT-L/14 (E 1024)
+        B, C, D, H, W = shape
+        n, Np = B * C * D, (H // 14) * (W // 14)
+        for E in (384, 1024):
+            g = torch.Generator(device="cuda").manual_seed(0)
+            dx = torch.randn(n * (1 + Np), E, device="cuda", generator=g)
+            wsum = torch.randn(E, 224, device="cuda", generator=g)
+            out = torch.empty(n, H, W, device="cuda")
+            ms = ev(lambda: hip.patch_embed_dgrad(dx, wsum, n, H, W, tokens=1 + Np, first=1, out=out))
+            fl = 2.0 * n * Np * E * 196
+            nbytes = 4.0 * (n * Np * E + n * H * W + E * 224)
+            tf, tbs = fl / ms / 1e9, nbytes / ms / 1e9
+            print(json.dumps({"case": f"mst_patch_embed_dgrad {n} x {H}x{W}, E={E}", "roofline": {
+                "kernel": "patch_dgrad_kernel", "bound": "mfma" if fl / 157e12 > nbytes / 8e12 else "hbm", "achieved": round(tf, 1), "peak": 157.0,
+                "unit": "TFLOP/s", "frac": round(tf / 157.0, 3), "achieved_TBps": round(tbs, 2), "hbm_peak_TBps": 8.0,
+                "frac_hbm": round(tbs / 8.0, 3), "flops_per_launch": fl, "bytes_per_launch": nbytes, "avg_launch_ms": round(ms, 4),
+                "dtype": "fp32"}}), flush=True)
+
+
 def train_case(name, model, shape, n=5):
     model = model.cuda().train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-5)
@@ -144,6 +206,9 @@ def main():
         torch.use_deterministic_algorithms(True)
         if "--no-fill" in sys.argv:                      # attribution only: without torch's NaN fill of every torch.empty under the flag
             torch.utils.deterministic.fill_uninitialized_memory = False
+    if "--input-grad" in sys.argv:
+        input_grad_cases()
+        return
     if "--rooflines" in sys.argv:
         backward_rooflines()
         attention_rooflines()
