@@ -185,8 +185,7 @@ int launch_t(const void* A, int64_t lda, const void* W, int64_t ldw, const float
              int64_t ldc, int64_t M, int N, int K, const float* gamma, float col_scale, int scale_cols,
              hipStream_t s) {
     const int tiles_m = (int)((M + BM - 1) / BM);
-    static const bool narrow_ok = !(getenv("MST_GEMM16_NARROW") && atoi(getenv("MST_GEMM16_NARROW")) == 0);
-    if (narrow_ok && tiles_m * (N / BN) < 224) {          // the 128-wide grid would leave CUs idle: 128 x 64 tiles, twice the workgroups
+    if (tiles_m * (N / BN) < 224) {          // the 128-wide grid would leave CUs idle: 128 x 64 tiles, twice the workgroups
         const int tiles_n = N / 64, nwg = tiles_m * tiles_n;
         static mst_lds_once lds_once_n;
         auto kern = gemm16_kernel<T, EPI, OutT, 64, 2>;
@@ -271,19 +270,16 @@ int launch_gemm16(const void* A, int dt, int64_t lda, const void* W, int64_t ldw
     MST_CHECK_ARG(epi != MST_EPI_RESIDUAL || cdt == MST_F32, "gemm16: residual epilogue needs f32 C");
     MST_CHECK_ARG(epi != MST_EPI_RESIDUAL_RELU, "gemm16: the residual + ReLU epilogue exists for f32 operands only");
     if (M <= 0) return MST_OK;
-    static const bool big_ok = !(getenv("MST_GEMM_BIG") && atoi(getenv("MST_GEMM_BIG")) == 0);
     // measured on MI355X (tools/bench_gemm.py): the read-modify-write epilogue of the residual GEMMs is
     // HBM-bound and overlaps better with two small workgroups per CU; the others favour the big tile
-    static const bool mid_ok = !(getenv("MST_GEMM_MID") && atoi(getenv("MST_GEMM_MID")) == 0);
-    static const bool wreg_ok = !(getenv("MST_GEMM_WREG") && atoi(getenv("MST_GEMM_WREG")) == 0);
     // the weights-in-registers kernel moves 16-byte pieces on every operand (LDS-DMA of A, vector loads of W, vector stores of C): a
     // caller of the C ABI with an odd row pitch or a sliced pointer falls back to the tiled kernels
     const bool al16 = lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0;
-    if (wreg_ok && al16 && gemm16_wreg_applicable(M, N, K, dt, cdt, epi, scale_cols, lda, ldc))
+    if (al16 && gemm16_wreg_applicable(M, N, K, dt, cdt, epi, scale_cols, lda, ldc))
         return launch_gemm16_wreg(A, dt, lda, W, ldw, bias, C, ldc, M, N, col_scale, scale_cols, s);
-    if (mid_ok && gemm16_mid_applicable(M, N, K, dt, cdt, epi))
+    if (gemm16_mid_applicable(M, N, K, dt, cdt, epi))
         return launch_gemm16_mid(A, dt, lda, W, ldw, bias, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    if (big_ok && epi != MST_EPI_RESIDUAL && gemm16_big_applicable(M, N, K))
+    if (epi != MST_EPI_RESIDUAL && gemm16_big_applicable(M, N, K))
         return launch_gemm16_big(A, dt, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
     if (dt == MST_BF16) return dispatch<bf16_t>(A, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
     if (dt == MST_F16) return dispatch<f16_t>(A, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);

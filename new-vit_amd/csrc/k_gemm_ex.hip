@@ -139,8 +139,7 @@ int launch_gemm_ex(const float* A, const float* B, float* C, int M, int N, int K
     GemmExArgs g{A, B, C, M, N, K, nb2, sam, sak, sbk, sbn, scm, scn, sa1, sa2, sb1, sb2, sc1, sc2, alpha, beta};
     // a float4 lies wholly inside or outside the operand when the vectorised extent is a multiple of 4, and is aligned when base and
     // every stride that moves it are multiples of 4 elements
-    static const bool vec_ok = !(getenv("MST_GEMM_EX_SCALAR") && atoi(getenv("MST_GEMM_EX_SCALAR")) == 1);
-    const bool a_al = vec_ok && al16(A) && sa1 % 4 == 0 && sa2 % 4 == 0, b_al = vec_ok && al16(B) && sb1 % 4 == 0 && sb2 % 4 == 0;
+    const bool a_al = al16(A) && sa1 % 4 == 0 && sa2 % 4 == 0, b_al = al16(B) && sb1 % 4 == 0 && sb2 % 4 == 0;
     int amode = 0, bmode = 0;
     if (a_al && sak == 1 && sam % 4 == 0 && K % 4 == 0) amode = 1;
     else if (a_al && sam == 1 && sak % 4 == 0 && M % 4 == 0) amode = 2;

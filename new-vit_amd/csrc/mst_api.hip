@@ -513,6 +513,147 @@ size_t mst_vit_workspace_bytes(const mst_vit_weights* w, int H, int W, int chunk
     return t;
 }
 
+#define RUN(call)              \
+    do {                       \
+        int rc_ = (call);      \
+        if (rc_) return rc_;   \
+    } while (0)
+#define RUNK(kind, call) RUN([&] { ProfScope ps_(prof, kind, s); return (call); }())   // the launch, timed under `kind` when a profiler is attached
+
+// What a call runs, resolved once from what the encoder can observe: fp8_linear, the compute dtype, embed_dim, the token count of
+// the WHOLE call (never of a chunk) and which packed weights the caller filled (include/mst_hip.h, mst_vit_layer).
+enum vit_tail {           // a block's work behind attention
+    TAIL_UNFUSED,         // out-projection, LayerNorm2, fc1, fc2: one launch each
+    TAIL_MLP_FUSED,       // out-projection, then norm2 + MLP in one kernel (k_mlp16.hip)
+    TAIL_BLOCK_ROLES,     // out-projection folded into that launch, producer/consumer form (k_block16.hip)
+    TAIL_BLOCK_SINGLE,    // the same in the single-role form (k_block16s.hip)
+    TAIL_FP8_DYNAMIC,     // e4m3 GEMMs, every input quantised with this chunk's max|x|
+    TAIL_FP8_STATIC       // e4m3 GEMMs with calibrated scales: producers write e4m3, nothing is scanned
+};
+struct vit_plan {
+    vit_tail tail;
+    bool fused_ln;        // norm1 folded into the QKV weights: the token kernel and every tail write the next block's plain-normalised rows
+    bool may_prune;       // prune_last_block, for chunks of at most 65535 slices
+};
+
+static vit_plan vit_resolve(const mst_vit_weights* w, int64_t tokens) {
+    if (w->fp8_linear) return {w->fp8_amax ? TAIL_FP8_STATIC : TAIL_FP8_DYNAMIC, false, false};
+    const bool may_prune = w->prune_last_block && w->num_heads * 64 == w->embed_dim;
+    // fused-LayerNorm pipeline (16-bit, E = 384): norm1 folded into QKV, norm2 + MLP in one kernel.  The fused MLP is a
+    // persistent kernel of 128-token tiles: below ~one tile per CU it leaves CUs idle (c1 shape, 4k tokens: 90 us per
+    // launch on 33 CUs against ~45 us for LN + fc1 + fc2 as three well-filled launches), so small calls take the unfused path.
+    static const int64_t fused_min_tokens = getenv("MST_FUSED_MIN_TOKENS") ? atoll(getenv("MST_FUSED_MIN_TOKENS")) : 12288;   // measured crossover (tools/bench_crossover.py): 8k tokens unfused 1.57 vs 1.92 ms, 16k fused 2.34 vs 2.62
+    bool fused = w->compute_dtype != MST_F32 && w->embed_dim == 384 && tokens >= fused_min_tokens, folded = true, single_role = true;
+    for (int l = 0; l < w->depth && fused; ++l) {
+        const mst_vit_layer* L = &w->layers[l];
+        fused = L->mlp_pack && L->fc1_bf && L->fc2_bf && L->qkv_wf && L->qkv_bf;
+        folded = folded && L->proj_pack && L->proj_bf;
+        single_role = single_role && L->block_seq;
+    }
+    if (!fused) return {TAIL_UNFUSED, false, may_prune};
+    return {!folded ? TAIL_MLP_FUSED : single_role ? TAIL_BLOCK_SINGLE : TAIL_BLOCK_ROLES, true, may_prune};
+}
+
+// One encoder call: what every launch needs, and the pieces of a block.  c, Mc and blocked belong to the current chunk.
+struct vit_call {
+    const mst_vit_weights* w;
+    float *x, *amax;
+    void *xn, *big, *a8, *blk;   // blk: lane-private hand-off of the producer/consumer block kernel
+    int dt, E, heads, N, log2q;
+    float qscale;
+    mst_profiler* prof;
+    hipStream_t s;
+    int c;
+    int64_t Mc;
+    bool blocked;
+
+    // big = qkv(norm1 x)                                       block.py:90-91,112
+    int qkv(const vit_plan& p, int l) const {
+        const mst_vit_layer* L = &w->layers[l];
+        if (p.tail == TAIL_FP8_STATIC) {
+            const float* am = w->fp8_amax + l * 4;
+            RUNK(MST_K_LAYERNORM, launch_layernorm_f8(x, E, L->ln1_w, L->ln1_b, a8, E, Mc, E, 1e-6f, am + 0, s));
+            RUNK(MST_K_GEMM_QKV, launch_gemm8(a8, E, L->qkv_w8, E, L->qkv_b, am + 0, L->w8_scale[0], big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, nullptr, nullptr, s));
+        } else if (p.tail == TAIL_FP8_DYNAMIC) {
+            // every linear layer: quantise its input with a fresh per-tensor scale (this chunk's max|x|), e4m3 GEMM.  The
+            // [M,E] inputs are scanned (53 us; a running maximum kept by the one-wave-per-row LayerNorm kernel cost 125 us:
+            // 350 k waves polling one address serialise in one L2 channel); the 4x larger hidden activation gets its maximum
+            // from the fc1 epilogue (one conditional atomic per workgroup)
+            float* am = amax + l * 4;
+            RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln1_w, L->ln1_b, xn, dt, E, Mc, E, 1e-6f, s));
+            RUN(launch_quant8(xn, dt, Mc * E, am + 0, a8, 1, s));
+            RUNK(MST_K_GEMM_QKV, launch_gemm8(a8, E, L->qkv_w8, E, L->qkv_b, am + 0, L->w8_scale[0], big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, nullptr, nullptr, s));
+        } else if (p.fused_ln && blocked && l > 0) {
+            RUNK(MST_K_GEMM_QKV, launch_gemm16_wreg(xn, dt, E, L->qkv_wf, E, L->qkv_bf, big, 3 * E, Mc, 3 * E, qscale, E, s, 1));
+        } else if (p.fused_ln) {
+            RUNK(MST_K_GEMM_QKV, mst_gemm(xn, dt, E, L->qkv_wf, E, L->qkv_bf, big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, s));
+        } else {
+            RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln1_w, L->ln1_b, xn, dt, E, Mc, E, 1e-6f, s));
+            RUNK(MST_K_GEMM_QKV, mst_gemm(xn, dt, E, L->qkv_w, E, L->qkv_b, big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, s));
+        }
+        return MST_OK;
+    }
+    // nothing behind the last block reads a patch token (final norm + head take the CLS rows): attention, out-projection
+    // and MLP for the c CLS rows only, on the unfused kernels.  Scratch: xn[0, cE) attention rows, xn[cE, 2cE)
+    // LayerNorm2 rows, big (free once K and V are consumed) the hidden rows.
+    int pruned_last_block(int l, float* pr) const {
+        const mst_vit_layer* L = &w->layers[l];
+        char* const a_cls = (char*)xn;
+        char* const n_cls = (char*)xn + (size_t)c * E * (dt == MST_F32 ? 4 : 2);
+        RUNK(MST_K_ATTENTION, launch_cls_attn(big, dt, c, N, heads, pr, a_cls, log2q, s));
+        RUNK(MST_K_GEMM_PROJ, mst_gemm(a_cls, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, (int64_t)N * E, c, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
+        RUNK(MST_K_LAYERNORM, launch_layernorm(x, (int64_t)N * E, L->ln2_w, L->ln2_b, n_cls, dt, E, c, E, 1e-6f, s));
+        RUNK(MST_K_GEMM_FC1, mst_gemm(n_cls, dt, E, L->fc1_w, E, L->fc1_b, big, dt, 4 * E, c, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, s));
+        RUNK(MST_K_GEMM_FC2, mst_gemm(big, dt, 4 * E, L->fc2_w, 4 * E, L->fc2_b, x, MST_F32, (int64_t)N * E, c, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, s));
+        return MST_OK;
+    }
+    // x += ls1(proj(attn)); x += ls2(fc2(gelu(fc1(norm2 x))))   block.py:91,93-94,113; the fused forms also write xn = normalise(x) for the next block
+    int tail(vit_tail t, int l) const {
+        const mst_vit_layer* L = &w->layers[l];
+        void* const xn_out = (l + 1 < w->depth) ? xn : nullptr;
+        switch (t) {
+            case TAIL_FP8_STATIC: {   // the e4m3 hidden activation lives in `big` (bytes); fc1 reads a8 and writes big, fc2 reads big
+                const float* am = w->fp8_amax + l * 4;
+                RUN(launch_quant8_static(xn, dt, Mc * E, am + 1, a8, s));
+                RUNK(MST_K_GEMM_PROJ, launch_gemm8(a8, E, L->proj_w8, E, L->proj_b, am + 1, L->w8_scale[1], x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, nullptr, nullptr, s));
+                RUNK(MST_K_LAYERNORM, launch_layernorm_f8(x, E, L->ln2_w, L->ln2_b, a8, E, Mc, E, 1e-6f, am + 2, s));
+                RUNK(MST_K_GEMM_FC1, launch_gemm8(a8, E, L->fc1_w8, E, L->fc1_b, am + 2, L->w8_scale[2], big, MST_F8E4M3, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, nullptr, am + 3, s));
+                RUNK(MST_K_GEMM_FC2, launch_gemm8(big, 4 * E, L->fc2_w8, 4 * E, L->fc2_b, am + 3, L->w8_scale[3], x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, nullptr, nullptr, s));
+                return MST_OK;
+            }
+            case TAIL_FP8_DYNAMIC: {
+                float* am = amax + l * 4;
+                RUN(launch_quant8(xn, dt, Mc * E, am + 1, a8, 1, s));
+                RUNK(MST_K_GEMM_PROJ, launch_gemm8(a8, E, L->proj_w8, E, L->proj_b, am + 1, L->w8_scale[1], x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, nullptr, nullptr, s));
+                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
+                RUN(launch_quant8(xn, dt, Mc * E, am + 2, a8, 1, s));
+                RUNK(MST_K_GEMM_FC1, launch_gemm8(a8, E, L->fc1_w8, E, L->fc1_b, am + 2, L->w8_scale[2], big, dt, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, am + 3, nullptr, s));
+                RUN(launch_quant8(big, dt, Mc * 4 * E, am + 3, a8, 0, s));
+                RUNK(MST_K_GEMM_FC2, launch_gemm8(a8, 4 * E, L->fc2_w8, 4 * E, L->fc2_b, am + 3, L->w8_scale[3], x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, nullptr, nullptr, s));
+                return MST_OK;
+            }
+            case TAIL_BLOCK_SINGLE:   // one launch, x read and written once; rows stay in the registers of the wave that owns them
+                RUNK(MST_K_BLOCK_FUSED, launch_block16s(x, xn, xn_out, dt, L->block_seq, L->fc1_bf, L->proj_bf, L->fc2_bf, Mc, E, 1e-6f,
+                                                       blocked ? (MST_LAYOUT_ACT_BLOCKED | (l > 0 ? MST_LAYOUT_X_IN_IMAGE : 0) | (l + 1 < w->depth ? MST_LAYOUT_X_OUT_IMAGE : 0)) : 0, s));
+                return MST_OK;
+            case TAIL_BLOCK_ROLES:
+                RUNK(MST_K_BLOCK_FUSED, launch_block16(x, xn, xn_out, dt, L->proj_pack, L->proj_bf, L->mlp_pack, L->fc1_bf, L->fc2_bf, blk, Mc, E, 1e-6f, s));
+                return MST_OK;
+            case TAIL_MLP_FUSED:
+                RUNK(MST_K_GEMM_PROJ, mst_gemm(xn, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
+                RUNK(MST_K_MLP_FUSED, launch_mlp16(x, xn_out, dt, L->mlp_pack, L->fc1_bf, L->fc2_bf, Mc, E, 1e-6f, s));
+                return MST_OK;
+            case TAIL_UNFUSED:
+                RUNK(MST_K_GEMM_PROJ, mst_gemm(xn, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
+                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
+                RUNK(MST_K_GEMM_FC1, mst_gemm(xn, dt, E, L->fc1_w, E, L->fc1_b, big, dt, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, s));
+                RUNK(MST_K_GEMM_FC2, mst_gemm(big, dt, 4 * E, L->fc2_w, 4 * E, L->fc2_b, x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, s));
+                return MST_OK;
+        }
+        return MST_EINVAL;   // not reached: every vit_tail returns above
+    }
+};
+
 int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int n_slices, int H, int W,
                    float* cls_out, float* cls_probs, float* full_probs, int n_layers_probs, int chunk_slices,
                    void* ws, size_t ws_bytes, mst_stream_t stream) {
@@ -536,13 +677,7 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
         mst_set_error("vit_encode: workspace %zu < %zu bytes", ws_bytes, total);
         return MST_EWORKSPACE;
     }
-    float* x = (float*)ws;
-    void* xn = (char*)ws + off_xn;
-    void* big = (char*)ws + off_big;
     const bool fp8 = w->fp8_linear != 0;
-    const bool fp8_static = fp8 && w->fp8_amax != nullptr;   // calibrated scales: producers write e4m3, nothing is scanned
-    void* a8 = fp8 ? (char*)ws + off_a8 : nullptr;
-    float* amax = fp8 ? (float*)((char*)ws + off_amax) : nullptr;
     if (fp8) {
         MST_CHECK_ARG(dt == MST_F16 || dt == MST_BF16, "vit_encode: fp8_linear needs a 16-bit compute dtype");
         MST_CHECK_ARG(E % 128 == 0, "vit_encode: fp8_linear needs embed_dim %% 128 == 0 (got %d)", E);
@@ -555,155 +690,48 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
     // on the same fp32 multiply of the QKV epilogue (one rounding of q, not two)
     const int log2q = dt != MST_F32;
     const float qscale = log2q ? 0.125f * 1.4426950408889634f : 0.125f;
-
-#define RUN(call)              \
-    do {                       \
-        int rc_ = (call);      \
-        if (rc_) return rc_;   \
-    } while (0)
-#define RUNK(kind, call)             \
-    do {                             \
-        int rc_;                     \
-        {                            \
-            ProfScope ps_(prof, kind, s); \
-            rc_ = (call);            \
-        }                            \
-        if (rc_) return rc_;         \
-    } while (0)
+    char* const p = (char*)ws;
+    vit_call k{w, (float*)ws, fp8 ? (float*)(p + off_amax) : nullptr, p + off_xn, p + off_big, fp8 ? p + off_a8 : nullptr, p + off_blk,
+               dt, E, heads, N, log2q, qscale, prof, s, 0, 0, false};
+    const vit_plan plan = vit_resolve(w, (int64_t)n_slices * N);
 
     for (int s0 = 0; s0 < n_slices; s0 += chunk_slices) {
-        const int c = (n_slices - s0 < chunk_slices) ? n_slices - s0 : chunk_slices;
-        const int64_t Mc = (int64_t)c * N;
+        const int c = k.c = (n_slices - s0 < chunk_slices) ? n_slices - s0 : chunk_slices;
+        const int64_t Mc = k.Mc = (int64_t)c * N;
         const char* v = (const char*)vol + (size_t)s0 * H * W * in_sz;
-        // fused-LayerNorm pipeline (16-bit, E = 384): norm1 folded into QKV, norm2 + MLP in one kernel.  The fused MLP is a
-        // persistent kernel of 128-token tiles: below ~one tile per CU it leaves CUs idle (c1 shape, 4k tokens: 90 us per
-        // launch on 33 CUs against ~45 us for LN + fc1 + fc2 as three well-filled launches), so small calls take the unfused
-        // path.  The choice depends on the WHOLE call (n_slices x N), never on the chunking.
-        static const int64_t fused_min_tokens = getenv("MST_FUSED_MIN_TOKENS") ? atoll(getenv("MST_FUSED_MIN_TOKENS")) : 12288;   // measured crossover (tools/bench_crossover.py): 8k tokens unfused 1.57 vs 1.92 ms, 16k fused 2.34 vs 2.62
-        const bool prune = w->prune_last_block && !fp8 && heads * 64 == E && c <= 65535;
-        bool fused = !fp8 && (dt != MST_F32) && E == 384 && (int64_t)n_slices * N >= fused_min_tokens;
-        for (int l = 0; l < w->depth && fused; ++l)
-            fused = w->layers[l].mlp_pack && w->layers[l].fc1_bf && w->layers[l].fc2_bf && w->layers[l].qkv_wf && w->layers[l].qkv_bf;
-        // out-projection folded into the same launch (k_block16.hip) when its packed image is there (MST_NO_PROJ_FOLD=1: A/B switch)
-        static const bool no_fold = getenv("MST_NO_PROJ_FOLD") && atoi(getenv("MST_NO_PROJ_FOLD"));
-        bool folded = fused && !no_fold;
-        for (int l = 0; l < w->depth && folded; ++l) folded = w->layers[l].proj_pack && w->layers[l].proj_bf;
-        // round 3: the single-role block kernel when its weight stream is there (MST_BLOCK_ROLES=1: the producer/consumer form, A/B switch)
-        static const bool roles = getenv("MST_BLOCK_ROLES") && atoi(getenv("MST_BLOCK_ROLES"));
-        bool single_role = folded && !roles;
-        for (int l = 0; l < w->depth && single_role; ++l) single_role = w->layers[l].block_seq != nullptr;
-        // between two single-role block launches the rows stay in the order the registers hold them (include/mst_hip.h, mst_layout_flags):
-        // x as the fp32 image from block 0's output to the last block's input, the 16-bit rows (attention output, normalised rows)
-        // blocked from block 0's attention on.  Needs the QKV kernel that reads blocked rows (weights-in-registers form) and every
-        // block on the fused path (MST_BLOCK_ROWMAJOR=1: row-major everywhere, A/B switch).
-        static const bool rowmajor = getenv("MST_BLOCK_ROWMAJOR") && atoi(getenv("MST_BLOCK_ROWMAJOR"));
-        const bool blocked = single_role && !rowmajor && !prune && (dt == MST_F16 || dt == MST_BF16) &&
-                             gemm16_wreg_applicable(Mc, 3 * E, E, dt, dt, MST_EPI_BIAS, E, E, 3 * E);
-        // tokens: in the fused pipeline one kernel writes the residual stream AND block 0's plain-normalised rows (k_patch_rows.hip;
-        // MST_PATCH_ROWS=0: the tiled patch kernel + a LayerNorm launch, the A/B baseline)
-        static const bool patch_rows = !(getenv("MST_PATCH_ROWS") && atoi(getenv("MST_PATCH_ROWS")) == 0);
-        if (fused && patch_rows) {
-            RUNK(MST_K_PATCH_EMBED, launch_patch_rows16(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, x, xn, s));
-        } else {
-            RUNK(MST_K_PATCH_EMBED, launch_patch_embed(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, E, x, s));
-            if (fused) RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, nullptr, nullptr, xn, dt, E, Mc, E, 1e-6f, s));
-        }
-        if (fp8 && !fp8_static && hipMemsetAsync(amax, 0, (size_t)w->depth * 4 * sizeof(float), s) != hipSuccess) {
+        // the two choices that depend on the chunk (the last one can be shorter).  Blocked: between two single-role block launches
+        // the rows stay in the order the registers hold them (include/mst_hip.h, mst_layout_flags): x as the fp32 image from block 0's
+        // output to the last block's input, the 16-bit rows (attention output, normalised rows) blocked from block 0's attention on.
+        // Needs the QKV kernel that reads blocked rows (weights-in-registers form) and every block on the fused path.
+        const bool prune = plan.may_prune && c <= 65535;
+        k.blocked = plan.tail == TAIL_BLOCK_SINGLE && !prune && gemm16_wreg_applicable(Mc, 3 * E, E, dt, dt, MST_EPI_BIAS, E, E, 3 * E);
+        // tokens: in the fused pipeline one kernel writes the residual stream AND block 0's plain-normalised rows (k_patch_rows.hip)
+        if (plan.fused_ln)
+            RUNK(MST_K_PATCH_EMBED, launch_patch_rows16(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, k.x, k.xn, s));
+        else
+            RUNK(MST_K_PATCH_EMBED, launch_patch_embed(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, E, k.x, s));
+        if (plan.tail == TAIL_FP8_DYNAMIC && hipMemsetAsync(k.amax, 0, (size_t)w->depth * 4 * sizeof(float), s) != hipSuccess) {
             mst_set_error("vit_encode: hipMemsetAsync(amax) failed");
             return MST_ELAUNCH;
         }
         for (int l = 0; l < w->depth; ++l) {
-            const mst_vit_layer* L = &w->layers[l];
-            // x += ls1(proj(attn(qkv(norm1 x))))                       block.py:90-91,112
-            if (fp8_static) {
-                const float* am = w->fp8_amax + l * 4;
-                RUNK(MST_K_LAYERNORM, launch_layernorm_f8(x, E, L->ln1_w, L->ln1_b, a8, E, Mc, E, 1e-6f, am + 0, s));
-                RUNK(MST_K_GEMM_QKV, launch_gemm8(a8, E, L->qkv_w8, E, L->qkv_b, am + 0, L->w8_scale[0], big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, nullptr, nullptr, s));
-            } else if (fp8) {
-                // every linear layer: quantise its input with a fresh per-tensor scale (this chunk's max|x|), e4m3 GEMM.  The
-                // [M,E] inputs are scanned (53 us; a running maximum kept by the one-wave-per-row LayerNorm kernel cost 125 us:
-                // 350 k waves polling one address serialise in one L2 channel); the 4x larger hidden activation gets its maximum
-                // from the fc1 epilogue (one conditional atomic per workgroup)
-                float* am = amax + l * 4;
-                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln1_w, L->ln1_b, xn, dt, E, Mc, E, 1e-6f, s));
-                RUN(launch_quant8(xn, dt, Mc * E, am + 0, a8, 1, s));
-                RUNK(MST_K_GEMM_QKV, launch_gemm8(a8, E, L->qkv_w8, E, L->qkv_b, am + 0, L->w8_scale[0], big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, nullptr, nullptr, s));
-            } else if (fused && blocked && l > 0) {
-                RUNK(MST_K_GEMM_QKV, launch_gemm16_wreg(xn, dt, E, L->qkv_wf, E, L->qkv_bf, big, 3 * E, Mc, 3 * E, qscale, E, s, 1));
-            } else if (fused) {
-                RUNK(MST_K_GEMM_QKV, mst_gemm(xn, dt, E, L->qkv_wf, E, L->qkv_bf, big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, s));
-            } else {
-                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln1_w, L->ln1_b, xn, dt, E, Mc, E, 1e-6f, s));
-                RUNK(MST_K_GEMM_QKV, mst_gemm(xn, dt, E, L->qkv_w, E, L->qkv_b, big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, s));
-            }
+            RUN(k.qkv(plan, l));
             const int li = l - (w->depth - n_layers_probs);
+            float* const pr = (cls_probs && li >= 0) ? cls_probs + ((int64_t)li * n_slices + s0) * heads * N : nullptr;
             if (full_probs && li >= 0)
-                RUN(launch_probs_full(big, dt, c, N, heads, 64, full_probs + ((int64_t)li * n_slices + s0) * heads * N * N, log2q, s));
+                RUN(launch_probs_full(k.big, dt, c, N, heads, 64, full_probs + ((int64_t)li * n_slices + s0) * heads * N * N, log2q, s));
             if (prune && l == w->depth - 1) {
-                // nothing behind this block reads a patch token (final norm + head take the CLS rows): attention, out-projection
-                // and MLP for the c CLS rows only, on the unfused kernels.  Scratch: xn[0, cE) attention rows, xn[cE, 2cE)
-                // LayerNorm2 rows, big (free once K and V are consumed) the hidden rows.
-                const size_t esz = dt == MST_F32 ? 4 : 2;
-                char* const a_cls = (char*)xn;
-                char* const n_cls = (char*)xn + (size_t)c * E * esz;
-                float* const pr = (cls_probs && li >= 0) ? cls_probs + ((int64_t)li * n_slices + s0) * heads * N : nullptr;
-                RUNK(MST_K_ATTENTION, launch_cls_attn(big, dt, c, N, heads, pr, a_cls, log2q, s));
-                RUNK(MST_K_GEMM_PROJ, mst_gemm(a_cls, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, (int64_t)N * E, c, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
-                RUNK(MST_K_LAYERNORM, launch_layernorm(x, (int64_t)N * E, L->ln2_w, L->ln2_b, n_cls, dt, E, c, E, 1e-6f, s));
-                RUNK(MST_K_GEMM_FC1, mst_gemm(n_cls, dt, E, L->fc1_w, E, L->fc1_b, big, dt, 4 * E, c, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, s));
-                RUNK(MST_K_GEMM_FC2, mst_gemm(big, dt, 4 * E, L->fc2_w, 4 * E, L->fc2_b, x, MST_F32, (int64_t)N * E, c, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, s));
+                RUN(k.pruned_last_block(l, pr));
                 continue;
             }
-            if (cls_probs && li >= 0)
-                RUNK(MST_K_CLS_PROBS, launch_cls_probs(big, dt, c, N, heads, 64, cls_probs + ((int64_t)li * n_slices + s0) * heads * N, log2q, s));
-            if (dt == MST_F32) RUNK(MST_K_ATTENTION, launch_attn32((const float*)big, c, N, heads, (float*)xn, s));
-            else RUNK(MST_K_ATTENTION, launch_attn16(big, dt, c, N, heads, xn, 1, s, blocked ? 1 : 0));
-            if (fp8_static) {
-                // the e4m3 hidden activation lives in `big` (bytes); fc1 reads a8 and writes big, fc2 reads big
-                const float* am = w->fp8_amax + l * 4;
-                RUN(launch_quant8_static(xn, dt, Mc * E, am + 1, a8, s));
-                RUNK(MST_K_GEMM_PROJ, launch_gemm8(a8, E, L->proj_w8, E, L->proj_b, am + 1, L->w8_scale[1], x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, nullptr, nullptr, s));
-                RUNK(MST_K_LAYERNORM, launch_layernorm_f8(x, E, L->ln2_w, L->ln2_b, a8, E, Mc, E, 1e-6f, am + 2, s));
-                RUNK(MST_K_GEMM_FC1, launch_gemm8(a8, E, L->fc1_w8, E, L->fc1_b, am + 2, L->w8_scale[2], big, MST_F8E4M3, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, nullptr, am + 3, s));
-                RUNK(MST_K_GEMM_FC2, launch_gemm8(big, 4 * E, L->fc2_w8, 4 * E, L->fc2_b, am + 3, L->w8_scale[3], x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, nullptr, nullptr, s));
-                continue;
-            }
-            if (fp8) {
-                float* am = amax + l * 4;
-                RUN(launch_quant8(xn, dt, Mc * E, am + 1, a8, 1, s));
-                RUNK(MST_K_GEMM_PROJ, launch_gemm8(a8, E, L->proj_w8, E, L->proj_b, am + 1, L->w8_scale[1], x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, nullptr, nullptr, s));
-                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
-                RUN(launch_quant8(xn, dt, Mc * E, am + 2, a8, 1, s));
-                RUNK(MST_K_GEMM_FC1, launch_gemm8(a8, E, L->fc1_w8, E, L->fc1_b, am + 2, L->w8_scale[2], big, dt, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, am + 3, nullptr, s));
-                RUN(launch_quant8(big, dt, Mc * 4 * E, am + 3, a8, 0, s));
-                RUNK(MST_K_GEMM_FC2, launch_gemm8(a8, 4 * E, L->fc2_w8, 4 * E, L->fc2_b, am + 3, L->w8_scale[3], x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, nullptr, nullptr, s));
-                continue;
-            }
-            if (folded && single_role) {
-                // the same in the single-role form (k_block16s.hip): rows stay in the registers of the wave that owns them
-                RUNK(MST_K_BLOCK_FUSED, launch_block16s(x, xn, (l + 1 < w->depth) ? xn : nullptr, dt, L->block_seq, L->fc1_bf, L->proj_bf, L->fc2_bf, Mc, E, 1e-6f,
-                                                       blocked ? (MST_LAYOUT_ACT_BLOCKED | (l > 0 ? MST_LAYOUT_X_IN_IMAGE : 0) | (l + 1 < w->depth ? MST_LAYOUT_X_OUT_IMAGE : 0)) : 0, s));
-                continue;
-            }
-            if (folded) {
-                // x += ls1(proj(attn)); x += ls2(fc2(gelu(fc1(norm2 x)))); xn = normalise(x): one launch, x read and written once
-                RUNK(MST_K_BLOCK_FUSED, launch_block16(x, xn, (l + 1 < w->depth) ? xn : nullptr, dt, L->proj_pack, L->proj_bf, L->mlp_pack,
-                                                     L->fc1_bf, L->fc2_bf, (char*)ws + off_blk, Mc, E, 1e-6f, s));
-                continue;
-            }
-            RUNK(MST_K_GEMM_PROJ, mst_gemm(xn, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
-            // x += ls2(fc2(gelu(fc1(norm2 x))))                        block.py:93-94,113
-            if (fused) {
-                RUNK(MST_K_MLP_FUSED, launch_mlp16(x, (l + 1 < w->depth) ? xn : nullptr, dt, L->mlp_pack, L->fc1_bf, L->fc2_bf, Mc, E, 1e-6f, s));
-            } else {
-                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
-                RUNK(MST_K_GEMM_FC1, mst_gemm(xn, dt, E, L->fc1_w, E, L->fc1_b, big, dt, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, s));
-                RUNK(MST_K_GEMM_FC2, mst_gemm(big, dt, 4 * E, L->fc2_w, 4 * E, L->fc2_b, x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, s));
-            }
+            if (pr) RUNK(MST_K_CLS_PROBS, launch_cls_probs(k.big, dt, c, N, heads, 64, pr, log2q, s));
+            if (dt == MST_F32) RUNK(MST_K_ATTENTION, launch_attn32((const float*)k.big, c, N, heads, (float*)k.xn, s));
+            else RUNK(MST_K_ATTENTION, launch_attn16(k.big, dt, c, N, heads, k.xn, 1, s, k.blocked ? 1 : 0));
+            RUN(k.tail(plan.tail, l));
         }
-        if (fp8 && !fp8_static && w->fp8_amax_out) RUN(launch_amax_merge(w->fp8_amax_out, amax, w->depth * 4, s));
+        if (plan.tail == TAIL_FP8_DYNAMIC && w->fp8_amax_out) RUN(launch_amax_merge(w->fp8_amax_out, k.amax, w->depth * 4, s));
         // final norm, CLS rows only (vision_transformer.py:263-265,329)
-        RUN(launch_layernorm(x, (int64_t)N * E, w->norm_w, w->norm_b, cls_out + (int64_t)s0 * E, MST_F32, E, c, E, 1e-6f, s));
+        RUN(launch_layernorm(k.x, (int64_t)N * E, w->norm_w, w->norm_b, cls_out + (int64_t)s0 * E, MST_F32, E, c, E, 1e-6f, s));
     }
     return MST_OK;
 }

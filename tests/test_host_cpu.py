@@ -231,6 +231,33 @@ def test_oracle_fp8_calibrated_table_reproduces_the_dynamic_run():
     assert not torch.equal(half, dyn)                       # a too-tight table saturates the largest values
 
 
+def test_csrc_environment_reads_are_thresholds_only():
+    """What the library does is decided by what it can observe (dtype, shape, alignment, which weights the caller filled), not by
+    A/B switches in the environment: csrc/ reads two numeric thresholds and MST_FP8_MX (bench.py quotes its peak by it), each in
+    one place and each documented; the ten switches that once forced or bypassed a kernel are gone from code, tools and user documents."""
+    kept = {"MST_GEMM_WREG_MIN_M", "MST_FUSED_MIN_TOKENS", "MST_FP8_MX"}
+    removed = ("MST_NO_PROJ_FOLD", "MST_BLOCK_ROLES", "MST_BLOCK_ROWMAJOR", "MST_PATCH_ROWS", "MST_GEMM_WREG", "MST_GEMM_MID",
+               "MST_GEMM_BIG", "MST_GEMM16_NARROW", "MST_GEMM32_SMALL", "MST_GEMM_EX_SCALAR")
+    readers = {}
+    for f in sorted((ROOT / "new-vit_amd" / "csrc").iterdir()):
+        for name in re.findall(r'getenv\(\s*"([^"]+)"', f.read_text()):
+            readers.setdefault(name, set()).add(f.name)
+    assert set(readers) == kept, set(readers) ^ kept
+    assert all(len(files) == 1 for files in readers.values()), readers
+    readme = (ROOT / "README.md").read_text()
+    for name in kept:
+        assert re.search(r"^\| `%s` \|" % name, readme, flags=re.M), f"{name} has no row in README.md's table of environment knobs"
+    built = {".so", ".o", ".a", ".pyc", ".hsaco", ".co"}
+    texts = [ROOT / "README.md", ROOT / "INTEGRATION.md"]
+    for top in ("new-vit_amd", "include", "tools"):
+        texts += [f for f in (ROOT / top).rglob("*") if f.is_file() and f.suffix not in built
+                  and not any(part == "build" or part.startswith("build_") for part in f.relative_to(ROOT).parts)]
+    for f in texts:
+        text = f.read_text(errors="ignore")
+        for name in removed:
+            assert not re.search(name + r"(?![A-Z0-9_])", text), f"{f.relative_to(ROOT)} still names {name}"
+
+
 def test_bench_flop_model_matches_the_oracle_and_survey():
     """bench.py owns its FLOP model (SURVEY.md 8d formula); the oracle's restatement of it must agree."""
     sys.path.insert(0, str(ROOT))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# FETCH_SIZE / WRITE_SIZE of the QKV GEMM for whatever library MST_HIP_LIB / MST_GEMM_BIG select.  Usage: bash tools/profile_qkv.sh <tag>
+# FETCH_SIZE / WRITE_SIZE of the QKV GEMM for whatever library MST_HIP_LIB selects.  Usage: bash tools/profile_qkv.sh <tag>
 set -e
 TAG=${1:-x}
 OUT=$PWD/gpurun_out/qkv_$TAG
