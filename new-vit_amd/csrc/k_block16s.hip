@@ -20,6 +20,9 @@
 // consumes one element in 24 slots of [fragment read 6 ahead | counted lgkmcnt | MFMA | a few vector instructions of the GELU
 // of a neighbouring chunk], with one s_barrier per phase.  Fragment reads run across the phase boundaries (the barrier of phase e
 // also publishes element e + 1), so the LDS latency never surfaces.
+// The twelve out-projection elements are fetched from that stream in another order, (accumulator tile pair, K half)-major, so that
+// pair P is first touched in phase 2P: the finished rows of the previous tile leave, and this tile's x arrives, pair by pair from
+// inside those phases, and only pair 0 and the attention rows stand between two tiles (see "row traffic" below).
 #include <type_traits>
 
 #include "mst_common.h"
@@ -56,6 +59,13 @@ constexpr int frag_of(int i) { return i; }
 #else
 constexpr int frag_of(int i) { return 2 * (i % 12) + i / 12; }
 #endif
+// Out-projection phases consume the stream pair-major: ring element (P, H) holds, for accumulator tiles 2P and 2P + 1, the K-chunks
+// j = 6H .. 6H + 5 as fragment n = 4 (j - 6H) + 2 (t - 2P) + p.  Slot i takes tile 2P + i % 2 and k-step i / 2 of the twelve
+// (j, p) in ascending order: the two tiles alternate (a tile's own MFMAs are 64 cycles apart) and every accumulator element sees the
+// summation order of the chunk-major walk.
+constexpr int pair_frag_of(int i) { return 4 * (i / 4) + 2 * (i % 2) + (i / 2) % 2; }
+constexpr int ORD_STREAM = 0, ORD_TILE = 1, ORD_PAIR = 2;
+constexpr int frag_in_order(int i, int ord) { return ord == ORD_PAIR ? pair_frag_of(i) : ord == ORD_TILE ? frag_of(i) : i; }
 constexpr int BIAS_SLOT = 8;                            // slot of a phase in which the next chunk's b1 is read
 
 template <int OFF, typename V> __device__ __forceinline__ void lds_read_b128(V& dst, unsigned addr) {
@@ -165,7 +175,6 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     // ---- weight stream.  Element ge (global index over this workgroup's tiles) = stream element ge % 108 -> ring slot ge % 6;
     // this wave's share: the six consecutive 1 KiB pieces 6 wave .. 6 wave + 5 (one lane address, one M0, six immediates).
     // The stream simply wraps: the four elements issued beyond the last tile land in slots nobody reads (drained before exit).
-#ifndef BLOCKS_DMA_GLOBAL
     // buffer form: the piece base rides in soffset (SGPR), the lane part is ONE 32-bit VGPR: half the address traffic per issue
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wseq, 0, ELEMS * ELEM_BYTES, 0x00020000);
     const int wlane_off = wave * 6144 + lane16;
@@ -178,17 +187,22 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, wlane_off, src_off + hi, u * 1024 - hi, 0);
 #endif
     };
-#else
-    const char* const wsrc_lane = wseq + (wave * 6144 + 2048) + lane16;
-    char* const wdst_wave = smem + wave * 6144 + 2048;
-    auto dma_piece = [&](int src_off, int slot, auto u_tag) {
-        constexpr int u = decltype(u_tag)::value;
+    // Out-projection element (P, H) is gathered from the unchanged stream: piece n = 6 wave + u of the ring element is fragment
+    // (4P + n % 4) of stream element 6H + n / 4.  Same lane address form, the per-piece source offset rides in an SGPR.
+    int pair_piece_off[6];
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+        const int n = 6 * wave + u;
+        pair_piece_off[u] = (n >> 2) * ELEM_BYTES + (n & 3) * 1024 - (u >= 4 ? u * 1024 - 4096 : u * 1024);
+    }
+    auto dma_pair_piece = [&](auto pe_tag, int slot, auto u_tag) {
+        constexpr int u = decltype(u_tag)::value, pe = decltype(pe_tag)::value, hi = u >= 4 ? 4096 : 0;
 #ifndef BLOCKS_NODMA
-        __builtin_amdgcn_global_load_lds(GLB_PTR(wsrc_lane + src_off), LDS_PTR(wdst_wave + slot * ELEM_BYTES), 16, (u - 2) * 1024, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, (int)lane16,
+                                                 pair_piece_off[u] + ((pe & 1) * 6 * ELEM_BYTES + (pe >> 1) * 4096), u * 1024 - hi, 0);
 #endif
     };
-#endif
-    for (int e0 = 0; e0 < AHEAD; ++e0) static_for<0, 6>([&](auto u) { dma_piece(e0 * ELEM_BYTES, e0, u); });
+    static_for<0, AHEAD>([&](auto e0) { static_for<0, 6>([&](auto u) { dma_pair_piece(e0, decltype(e0)::value, u); }); });
     int dsrc = AHEAD * ELEM_BYTES, dslot = AHEAD;         // stream byte offset / ring slot of the next element to request
 
     f32x16 acc[12];
@@ -202,7 +216,19 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
 #endif
 
     int slot = 0;                                        // ring slot of the element the next phase consumes
-    const unsigned b1_lane = lds_base + B1_OFF + half * 16;     // + 128 * chunk + 32 * q
+    // LDS addresses of the bias tables: lane part + a wave-uniform offset, added where they are used (volatile: kept as loop
+    // invariants, the handful of variants beyond the 16-bit instruction offset were spilled around the tile boundary)
+    auto bias_addr = [&](unsigned uniform_off) {          // uniform_off + 16 * (lane >> 5)
+        unsigned a;
+        asm volatile("v_lshrrev_b32 %0, 5, %2\n\tv_and_b32 %0, 16, %0\n\tv_add_u32 %0, %1, %0" : "=&v"(a) : "s"(lds_base + uniform_off), "v"(lane16));
+        return a;
+    };
+    // value + the value of the lane 32 further on / back (the two lanes that share a row): one v_permlane32_swap, no lane-address register
+    auto add_other_half = [](float v) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
+        const unsigned own = sw[0], other = sw[1];       // (as scalars first: a bit_cast of a vector element reads element 0)
+        return __builtin_bit_cast(float, own) + __builtin_bit_cast(float, other);
+    };
 
     // ---- one phase: 24 slots over ring element `slot` (prefetching the head of the next element), MFMA `mf(i, fragment)`,
     // vector filler `fill(i)`; BQ >= 0: b1 of chunk `bias_chunk` is read INTO hq[BQ] (dead at that point), where the GEMM1 of that
@@ -211,16 +237,21 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     unsigned long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long tstart = bstamp();
 #endif
-    // ord_tag / nord_tag: 1 = this / the next phase walks its fragments tile-major (frag_of), 0 = in stream order (GEMM1 k-steps)
-    auto phase = [&](auto head_tag, auto tail_tag, auto bq_tag, int bias_chunk, auto&& mf, auto&& fill, auto cat_tag, auto ord_tag, auto nord_tag) {
+    // ord_tag / nord_tag: how this / the next phase walks its fragments (ORD_STREAM: GEMM1 k-steps, ORD_TILE: frag_of, ORD_PAIR:
+    // pair_frag_of).  dma_tag: the element requested here (four ahead) is out-projection element 0..11 of the pair-major walk, or
+    // -1 = the next one of the stream as it lies.  rows_tag: row loads issued in the two phases before this one (below).
+    auto phase = [&](auto head_tag, auto tail_tag, auto bq_tag, int bias_chunk, auto&& mf, auto&& fill, auto cat_tag, auto ord_tag, auto nord_tag,
+                     auto dma_tag, auto rows_tag) {
         constexpr bool HEAD = decltype(head_tag)::value, TAIL = decltype(tail_tag)::value;
-        constexpr int ORD = decltype(ord_tag)::value, NORD = decltype(nord_tag)::value;
-        auto fr = [](int i, int ord) constexpr { return ord ? frag_of(i) : i; };
+        constexpr int ORD = decltype(ord_tag)::value, NORD = decltype(nord_tag)::value, DMA_PE = decltype(dma_tag)::value;
+        auto fr = [](int i, int ord) constexpr { return frag_in_order(i, ord); };
         constexpr int BQ = decltype(bq_tag)::value, CAT = decltype(cat_tag)::value;
         BST(p0);
         // element ge landed for everybody at the previous barrier; this one publishes ge + 1: own pieces first (all but the 12
-        // youngest vector-memory operations done: the pieces of ge + 2 and ge + 3 may stay in flight)
-        asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
+        // youngest vector-memory operations done: the pieces of ge + 2 and ge + 3 may stay in flight).  The counter is shared with the
+        // row traffic and retires in order, so the row LOADS issued since the last piece of ge + 1 are counted on top; the row stores
+        // between them are conditional and are left out, which only makes the wait reach a little further back.
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(12 + decltype(rows_tag)::value) : "memory");
         BST(p1);
         BACC(CAT, p0, p1);
         const unsigned cur = lds_base + slot * ELEM_BYTES + lane16;
@@ -229,7 +260,8 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         const int my_dsrc = dsrc, my_dslot = dslot;
         dsrc = dsrc + ELEM_BYTES == ELEMS * ELEM_BYTES ? 0 : dsrc + ELEM_BYTES;
         dslot = dslot + 1 == NSLOT ? 0 : dslot + 1;
-        const unsigned baddr = b1_lane + 128 * bias_chunk;
+        unsigned baddr = 0;                               // b1 of the chunk: + 32 * q
+        if constexpr (decltype(bq_tag)::value >= 0) baddr = bias_addr(B1_OFF + 128 * bias_chunk);
         f32x4 bt0, bt1, bt2, bt3;
         if constexpr (HEAD) static_for<0, D>([&](auto q) { lds_read_b128<fr(decltype(q)::value, ORD) * 1024>(w[decltype(q)::value % R], cur); });
         static_for<0, NF>([&](auto it) {
@@ -268,11 +300,10 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
                 hq[BQ < 0 ? 0 : BQ][3] = bt3;
             }
             mf(it, w[i % R]);
-#ifdef BLOCKS_DMA_FRONT
-            if constexpr (i == 0) static_for<0, 6>([&](auto u) { dma_piece(my_dsrc, my_dslot, u); });
-#else
-            if constexpr (i % 4 == 3) dma_piece(my_dsrc, my_dslot, std::integral_constant<int, i / 4>{});
-#endif
+            if constexpr (i % 4 == 3) {
+                if constexpr (DMA_PE >= 0) dma_pair_piece(dma_tag, my_dslot, std::integral_constant<int, i / 4>{});
+                else dma_piece(my_dsrc, my_dslot, std::integral_constant<int, i / 4>{});
+            }
             fill(it);
         });
         slot = nslot;
@@ -289,6 +320,10 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     constexpr std::integral_constant<int, -1> NOBIAS{};
     constexpr std::integral_constant<int, 0> I0{};
     constexpr std::integral_constant<int, 1> I1{};
+    constexpr std::integral_constant<int, 2> I2{};
+    constexpr std::integral_constant<int, 3> I3{};
+    constexpr std::integral_constant<int, -1> STREAM{};  // dma_tag: the next element of the stream
+    constexpr std::integral_constant<int, 0> ROWS0{};    // rows_tag: no row loads in flight behind the ring
 
     // GEMM1 of one chunk into hq[HS] (which holds the chunk's b1): 24 dependent MFMAs on one 32x32 accumulator
     auto gemm1_mf = [&](auto hs_tag) {
@@ -342,72 +377,150 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
 
     // ---- row traffic.  Blocked / image layouts (include/mst_hip.h): every instruction moves one contiguous KiB; row-major: lane =
     // row, 32 scattered 32-byte runs per instruction (what the first and the last block of an encoder still see).
-    // The rows of tile k + 1 are requested from inside the epilogue of tile k: the attention fragments as soon as xa is dead, the x
-    // pieces tile by tile right behind the stores that free their accumulator registers, so the loads queue behind nothing
-    // (stamps: 14-17 k cycles per tile spent ISSUING 72 loads behind the 72 stores of the epilogue when they came afterwards).
+    // The out-projection needs accumulator pair P (tiles 2P, 2P + 1) from its phase 2P on, so only pair 0 and the attention rows
+    // stand between two tiles: the finished pair P >= 1 of the previous tile is stored, and its registers are refilled with this
+    // tile's x, from inside out-projection phase 2P - 2, one instruction per MFMA slot (576 KB per workgroup in one burst with the
+    // matrix pipe idle otherwise: 28 k cycles of a 185 k-cycle tile, profiles/block_boundary_stamps_parent.txt).
+    // Aliasing (xn_out may be the attention buffer; x in place with differing in / out layouts): a 32-row group belongs to ONE wave
+    // of ONE tile.  That wave requests the group's attention rows before phase 0 and the last of its x in phase 8, and phase 10
+    // cannot start before those loads have returned (the counter retires in order and every phase waits on it), while the first
+    // store to the group is issued behind the tile's last phase: a group is still read whole before it is written.
     const int last_grp = (M - 1) >> 5;
-    auto row_of = [&](int tile) { const int g = tile * 128 + wave * 32 + row32; return (unsigned)(g < M ? g : M - 1); };
+    // The lane parts of the row addresses are derived again at every tile boundary from a copy of the lane address hipcc cannot
+    // see through: as loop invariants they would occupy registers across the MLP phases, where none is to spare.
+    auto lane16_here = [&]() {
+        unsigned l;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(l) : "v"(lane16));
+        return l;
+    };
+    auto row_of = [&](int tile) {
+        int wave_row;                                    // (an SGPR by force: hipcc kept a vector copy of it across the tile, and spilled it)
+        asm volatile("s_lshl_b32 %0, %1, 5" : "=s"(wave_row) : "s"(wave));
+        const int g = tile * 128 + wave_row + (int)((lane16_here() >> 4) & 31);
+        return (unsigned)(g < M ? g : M - 1);
+    };
     auto grp_of = [&](int tile) { return (size_t)((tile * 4 + wave) < last_grp ? (tile * 4 + wave) : last_grp); };
-    auto load_attn = [&](int tile) {
-        if (act_blk) {
-            const char* ap = (const char*)attn + (grp_of(tile) * (32 * E * 2) + lane16);
+    // Row x traffic is addressed from the wave-uniform base (SGPRs) of the 48 KiB block of the wave's 32 rows, the lane part in ONE
+    // VGPR and the (tile t, quarter q) part added where it is used: 32 (4t + q) bytes row-major, 32 times that in the image layout.
+    // (volatile: hoisted out of the tile loop, the 72 + 48 offsets of a tile were what hipcc spilled)
+    auto row_off = [](int lane_part, auto units_tag, int shift) {
+        int off;
+        asm volatile("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(off) : "n"(decltype(units_tag)::value), "s"(shift), "v"(lane_part));
+        return off;
+    };
+    const int xin_sh = x_in_img ? 10 : 5, att_sh = act_blk ? 10 : 5;
+    const char* in_x;
+    int xin_lane;
+    auto row_in_grp = [&](int tile) { return (int)(row_of(tile) - (unsigned)grp_of(tile) * 32u); };   // (clamped: every lane reads rows that exist)
+    auto x_in_of = [&](int tile) {
+        in_x = (const char*)x + grp_of(tile) * (32 * E * 4);
+        const unsigned l16 = lane16_here();
+        xin_lane = x_in_img ? (int)l16 : row_in_grp(tile) * (E * 4) + (int)((l16 >> 5) & 16);
+    };
+    auto load_attn = [&](int tile) {                     // fragment i: 1 KiB apart in the blocked layout, 32 bytes of the row otherwise
+        const char* const ap = (const char*)attn + grp_of(tile) * (32 * E * 2);
+        const unsigned l16 = lane16_here();
+        const int lane_part = act_blk ? (int)l16 : row_in_grp(tile) * (E * 2) + (int)((l16 >> 5) & 16);
+        static_for<0, 24>([&](auto i) {
+            xa[decltype(i)::value] = *reinterpret_cast<const u32x4*>(ap + (unsigned)row_off(lane_part, i, att_sh));
+        });
+    };
+    auto load_x = [&](auto t_tag, auto q_tag) {          // quarter q of accumulator tile t of the wave's 32 rows
+        constexpr int t = decltype(t_tag)::value, q = decltype(q_tag)::value;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(in_x + (unsigned)row_off(xin_lane, std::integral_constant<int, 4 * t + q>{}, xin_sh));
 #pragma unroll
-            for (int i = 0; i < 24; ++i) xa[i] = *reinterpret_cast<const u32x4*>(ap + 1024 * i);
-        } else {
-            const char* ap = (const char*)attn + ((size_t)row_of(tile) * (E * 2) + half * 16);
+        for (int r = 0; r < 4; ++r) acc[t][4 * q + r] = v[r];
+    };
+    // The output rows of the tile whose accumulators are being stored (the previous tile while the out-projection runs).  A wave's 32
+    // rows are one contiguous block in every layout, so the stores go through a buffer descriptor over exactly the bytes of that
+    // block that exist: rows past M (row-major) and groups past the last one are dropped by the range check, without a branch in the
+    // phases, and the descriptors (SGPRs) are all that is carried from one tile to the next.  Zero records = nothing to store yet /
+    // no xn_out.  (offsets go through the VGPR operand alone: that is the part the range check sees)
+    const int xout_sh = x_out_img ? 10 : 5, xn_sh = act_blk ? 10 : 5;
+    int xout_lane = 0, xn_lane = 0;
+    auto out_lanes = [&]() {
+        const unsigned l16 = lane16_here();
+        const int r32 = (l16 >> 4) & 31, h16 = (l16 >> 5) & 16;
+        xout_lane = x_out_img ? (int)l16 : r32 * (E * 4) + h16;
+        xn_lane = act_blk ? (int)l16 : r32 * (E * 2) + h16;
+    };
+    auto rows_rsrc = [&](void* base, int tile, int row_bytes, bool whole_groups) {
+        const int grp = tile * 4 + wave, rows = M - grp * 32;                 // wave-uniform
+        const int nrows = rows <= 0 || !base ? 0 : (rows > 32 || whole_groups) ? 32 : rows;
+        return __builtin_amdgcn_make_buffer_rsrc((char*)base + (size_t)grp * (32 * row_bytes), 0, nrows * row_bytes, 0x00020000);
+    };
+    __amdgpu_buffer_rsrc_t out_x = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, 0, 0x00020000), out_n = out_x;
+    float out_rstd = 0.f, out_nmr = 0.f;                 // LayerNorm statistics of those rows
+    auto store_x = [&](auto t_tag, auto q_tag) {
+        constexpr int t = decltype(t_tag)::value, q = decltype(q_tag)::value;
+        f32x4 v;
 #pragma unroll
-            for (int i = 0; i < 24; ++i) xa[i] = *reinterpret_cast<const u32x4*>(ap + 32 * i);
+        for (int r = 0; r < 4; ++r) v[r] = acc[t][4 * q + r];
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_x, row_off(xout_lane, std::integral_constant<int, 4 * t + q>{}, xout_sh), 0, 0);
+    };
+    auto store_n = [&](auto t_tag, auto p_tag) {
+        constexpr int t = decltype(t_tag)::value, p = decltype(p_tag)::value;
+        // registers 8p..8p+3 = features 32t + 16p + 4 half + 0..3, registers 8p+4..8p+7 = the same + 8: one
+        // v_permlane32_swap per register pair hands each lane eight CONSECUTIVE features (T21)
+        // (scalar fused multiply-adds: the statistics stay two registers per lane from one tile into the next)
+        vec4 lo, hi;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            // (rounded to fp32 first, then to 16 bits, as the vector form this replaces: no fused v_fma_mix with its single rounding)
+            float n0 = fmaf(acc[t][8 * p + e], out_rstd, out_nmr), n1 = fmaf(acc[t][8 * p + 4 + e], out_rstd, out_nmr);
+            asm volatile("" : "+v"(n0), "+v"(n1));
+            lo[e] = (T)n0;
+            hi[e] = (T)n1;
+        }
+        const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
+        u32x4 o;
+#pragma unroll
+        for (int d2 = 0; d2 < 2; ++d2) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(l2[d2], h2[d2], false, false);
+            o[d2] = sw[0];
+            o[2 + d2] = sw[1];
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(o, out_n, row_off(xn_lane, std::integral_constant<int, 2 * t + p>{}, xn_sh), 0, 0);
+    };
+    // the 20 row operations of accumulator pair P as one per slot: 12 stores (per tile 4 x quarters + 2 normalised fragments), then
+    // the 8 loads that refill the same registers
+    auto pair_op = [&](auto p_tag, auto n_tag) {
+        constexpr int P = decltype(p_tag)::value, n = decltype(n_tag)::value;
+        if constexpr (n < 12) {
+            constexpr int t = 2 * P + n / 6, m = n % 6;
+            if constexpr (m < 4) store_x(std::integral_constant<int, t>{}, std::integral_constant<int, m>{});
+            else store_n(std::integral_constant<int, t>{}, std::integral_constant<int, m - 4>{});
+        } else if constexpr (n < 20) {
+            load_x(std::integral_constant<int, 2 * P + (n - 12) / 4>{}, std::integral_constant<int, (n - 12) % 4>{});
         }
     };
-    auto load_x = [&](int tile, auto t_tag) {            // accumulator tile t of the wave's 32 rows
-        constexpr int t = decltype(t_tag)::value;
-        const char* xp = x_in_img ? (const char*)x + (grp_of(tile) * (32 * E * 4) + lane16) + 4096 * t
-                                  : (const char*)x + ((size_t)row_of(tile) * (E * 4) + half * 16) + 128 * t;
-        const int qstep = x_in_img ? 1024 : 32;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(xp + qstep * q);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][4 * q + r] = v[r];
-        }
-    };
-    // De-phase the persistent workgroups (k_mlp16.hip): every workgroup runs the same program on the same amount of work, so all 256
-    // tile boundaries (576 KB of row traffic per workgroup) would hit HBM in the same ~10 % of the tile period.  Workgroups with
-    // the smaller tile count start up to a whole tile late for free, the others up to half a tile.
-#ifndef BLOCKS_TILE_CYCLES
-#define BLOCKS_TILE_CYCLES 170000
-#endif
-#ifndef BLOCKS_NO_DEPHASE
-    if (my_tiles >= 4) {
-        const int min_tiles = ntiles / (int)gridDim.x;
-        const unsigned u = (((unsigned)blockIdx.x >> 3) + 5u * ((unsigned)blockIdx.x & 7u)) & 15u;   // 0..15
-        const unsigned long long delay = (unsigned long long)BLOCKS_TILE_CYCLES * ((my_tiles > min_tiles ? 0u : 16u) + u) / 32u;
-        const unsigned long long t0 = __builtin_readcyclecounter();
-        for (int it = 0; it < 640 && __builtin_readcyclecounter() - t0 < delay; ++it) __builtin_amdgcn_s_sleep(32);   // bounded: every wave leaves
-    }
-#endif
+    constexpr int PAIR_LOADS = 8, HEAD_LOADS = 24 + PAIR_LOADS;      // row loads per pair; in front of phase 0: attention rows + pair 0
+    // (The workgroups are not de-phased any more: with 70 % of the row traffic under the out-projection a start-up stagger that
+    // spreads the boundaries over the tile period measured 0.1 ms per step SLOWER than none, profiles/NOTES_block_boundary.md.)
     load_attn(blockIdx.x);
-    static_for<0, 12>([&](auto t) { load_x(blockIdx.x, t); });
+    x_in_of(blockIdx.x);
+    static_for<12, 20>([&](auto n) { pair_op(I0, n); });
 
     for (int k = 0; k < my_tiles; ++k) {
         const int tile = blockIdx.x + k * gridDim.x;
-        const int next_tile = k + 1 < my_tiles ? tile + (int)gridDim.x : tile;   // (last tile: its own rows once more, unused)
-        const int grow = tile * 128 + wave * 32 + row32;                 // this lane's token row
-        const bool valid = grow < M;
-        const unsigned crow = (unsigned)(valid ? grow : M - 1);
-        BST(q0);
-        BST(q1);
-        BACC(8, q0, q1);
-        // ---- out-projection: 12 phases, acc[t] += Wp chunk j (t, p) . attention columns
-        static_for<0, PJ>([&](auto jt) {
-            constexpr int j = decltype(jt)::value;
+        // ---- out-projection: 12 phases (pair P, K half H), acc[2P + i % 2] += Wp fragments . attention columns; the even phases
+        // 0..8 carry the row traffic of pair P + 1
+        static_for<0, PJ>([&](auto et) {
+            constexpr int e = decltype(et)::value, P = e / 2, H = e % 2;
             auto mf = [&](auto it, const vec8& wf) {
-                constexpr int i = frag_of(decltype(it)::value);
-                acc[i >> 1] = mfma32(wf, __builtin_bit_cast(vec8, xa[2 * j + (i & 1)]), acc[i >> 1]);
+                constexpr int i = decltype(it)::value;
+                acc[2 * P + i % 2] = mfma32(wf, __builtin_bit_cast(vec8, xa[12 * H + i / 2]), acc[2 * P + i % 2]);
             };
-            if constexpr (j == 0) phase(YES, YES, NOBIAS, 0, mf, no_fill, C_PROJ, I1, I1);
-            else if constexpr (j == PJ - 1) phase(NO, NO, I0, 0, mf, no_fill, C_PROJ, I1, I1);           // b1 of chunk 0 -> hq[0]; no prefetch across LayerNorm2
-            else phase(NO, YES, NOBIAS, 0, mf, no_fill, C_PROJ, I1, I1);
+            auto fill = [&](auto it) {
+                if constexpr (H == 0 && P + 1 < 6) pair_op(std::integral_constant<int, P + 1>{}, it);
+            };
+            // row loads issued behind the last piece of element e + 1 (that piece went out at the end of phase e - 3)
+            constexpr int rows = e == 0 ? HEAD_LOADS : e == 1 ? HEAD_LOADS + PAIR_LOADS : e <= 10 ? PAIR_LOADS : 0;
+            constexpr std::integral_constant<int, rows> ROWS{};
+            constexpr std::integral_constant<int, (e + AHEAD < PJ ? e + AHEAD : -1)> DMA{};
+            if constexpr (e == 0) phase(YES, YES, NOBIAS, 0, mf, fill, C_PROJ, I2, I2, DMA, ROWS);
+            else if constexpr (e == PJ - 1) phase(NO, NO, NOBIAS, 0, mf, fill, C_PROJ, I2, I2, DMA, ROWS);   // no prefetch across LayerNorm2
+            else phase(NO, YES, NOBIAS, 0, mf, fill, C_PROJ, I2, I2, DMA, ROWS);
         });
         BST(q2);
         // ---- LayerNorm2 on the accumulators (+ b_proj first), normalised rows -> xa, then + b2.  Vector-typed arithmetic on
@@ -415,7 +528,7 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         {
             // (no fragment read is in flight here: asm outputs that have not landed must not live across code hipcc schedules by
             // itself -- under LayerNorm2's register pressure it copied them into the accumulator file right behind the reads)
-            const unsigned bp = lds_base + BP_OFF + half * 16, bb = lds_base + B2_OFF + half * 16;
+            const unsigned bp = bias_addr(BP_OFF), bb = bias_addr(B2_OFF);
             f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
             static_for<0, 12>([&](auto tt) {
                 constexpr int t = decltype(tt)::value;
@@ -427,7 +540,7 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
                 asm volatile("" : "+v"(s4));
             });
             float sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-            sum += __shfl_xor(sum, 32, 64);
+            sum = add_other_half(sum);
             const float mean = sum * (1.0f / E);
             const f32x4 mean4 = {mean, mean, mean, mean};
             f32x4 q4 = {0.f, 0.f, 0.f, 0.f};
@@ -440,7 +553,7 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
                 asm volatile("" : "+v"(q4));
             });
             float sq = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-            sq += __shfl_xor(sq, 32, 64);
+            sq = add_other_half(sq);
             const float rstd = rsqrtf(sq * (1.0f / E) + eps);
             const float nmr = -mean * rstd;
             const f32x4 rstd4 = {rstd, rstd, rstd, rstd}, nmr4 = {nmr, nmr, nmr, nmr};
@@ -464,45 +577,58 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         }
         BST(q3);
         BACC(9, q2, q3);
+        // ---- b1 of chunk 0 -> hq[0] (behind LayerNorm2: sixteen more registers across it were sixteen spilled ones)
+        {
+            const unsigned baddr = bias_addr(B1_OFF);
+            f32x4 bt[4];
+            static_for<0, 4>([&](auto q) { lds_read_b128_acc<32 * decltype(q)::value>(bt[decltype(q)::value], baddr); });
+            wait_lgkm<0>();
+            asm volatile("" : "+a"(bt[0]), "+a"(bt[1]), "+a"(bt[2]), "+a"(bt[3]));     // (only now do the values exist for hipcc)
+            static_for<0, 4>([&](auto q) { hq[0][decltype(q)::value] = bt[decltype(q)::value]; });
+        }
         // ---- GEMM1 of chunk 0 (b1 of chunk 1 -> hq[1]), then the first half of its GELU
-        phase(YES, YES, I1, 1, gemm1_mf(I0), no_fill, C_G10, I0, I0);
+        phase(YES, YES, I1, 1, gemm1_mf(I0), no_fill, C_G10, I0, I0, STREAM, ROWS0);
         wait_lgkm<0>();
         gelu_now(I0, I0);
         // ---- chunks: A(c) = GEMM1(c + 1) beside the second half of GELU(c); B(c) = GEMM2(c) beside the first half of GELU(c + 1)
-        // (+ b1 of chunk c + 2 into the buffer GELU(c) has just left)
-        auto iter = [&](auto par_tag, auto bias_tag, int c) {
+        // (+ b1 of chunk c + 2 into the buffer GELU(c) has just left).  The last four phases of a tile request the first four
+        // out-projection elements of the next one (dma_a / dma_b).
+        auto iter = [&](auto par_tag, auto bias_tag, int c, auto dma_a, auto dma_b) {
             constexpr int cur = decltype(par_tag)::value, nx = cur ^ 1;
-            phase(NO, YES, NOBIAS, 0, gemm1_mf(std::integral_constant<int, nx>{}), gelu_fill(std::integral_constant<int, cur>{}, I1), C_A, I0, I1);
+            phase(NO, YES, NOBIAS, 0, gemm1_mf(std::integral_constant<int, nx>{}), gelu_fill(std::integral_constant<int, cur>{}, I1), C_A, I0, I1, dma_a, ROWS0);
             if constexpr (decltype(bias_tag)::value)
-                phase(NO, YES, std::integral_constant<int, cur>{}, c + 2, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I0);
+                phase(NO, YES, std::integral_constant<int, cur>{}, c + 2, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I0, dma_b, ROWS0);
             else                                         // chunk 46: the next phase is GEMM2(47)
-                phase(NO, YES, NOBIAS, 0, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I1);
+                phase(NO, YES, NOBIAS, 0, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I1, dma_b, ROWS0);
         };
 #pragma unroll 1
-        for (int c = 0; c < NCHUNK - 2; c += 2) {        // chunks 0 .. 45
-            iter(I0, YES, c);
-            iter(I1, YES, c + 1);
+        for (int c = 0; c < NCHUNK - 4; c += 2) {        // chunks 0 .. 43
+            iter(I0, YES, c, STREAM, STREAM);
+            iter(I1, YES, c + 1, STREAM, STREAM);
         }
-        iter(I0, NO, NCHUNK - 2);                        // chunk 46
+        iter(I0, YES, NCHUNK - 4, STREAM, STREAM);       // chunk 44
+        iter(I1, YES, NCHUNK - 3, STREAM, I0);           // chunk 45
+        iter(I0, NO, NCHUNK - 2, I1, I2);                // chunk 46
         wait_lgkm<0>();
         gelu_now(I1, I1);
-        phase(NO, NO, NOBIAS, 0, gemm2_mf(I1), no_fill, C_B, I1, I1); // GEMM2 of chunk 47
-        // ---- the block's output rows: x and the next block's normalised rows, interleaved with the requests for the next tile's rows
+        phase(NO, NO, NOBIAS, 0, gemm2_mf(I1), no_fill, C_B, I1, I1, I3, ROWS0); // GEMM2 of chunk 47
+        // ---- tile boundary: the next block's LayerNorm statistics (they need all twelve tiles), pair 0 out, the next tile's
+        // attention rows and pair 0 in.  Pairs 1..5 leave from inside the next out-projection, or behind the loop.
         BST(q4);
         {
-            const size_t grp = (size_t)tile * 4 + wave;
-            const bool grp_valid = (tile * 4 + wave) * 32 < M;           // wave-uniform: groups past M do not exist in the buffers
+            // (last tile: its own rows once more, unused -- a load under a condition makes hipcc wait for it at the join)
+            const int next_tile = k + 1 < my_tiles ? tile + (int)gridDim.x : tile;
             load_attn(next_tile);                                        // xa is dead since the last GEMM1
-            f32x4 rstd4 = {0.f, 0.f, 0.f, 0.f}, nmr4 = {0.f, 0.f, 0.f, 0.f};
             if (xn_out) {
                 f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
                 static_for<0, 12>([&](auto tt) {
                     constexpr int t = decltype(tt)::value;
                     s4 += (sub4<0>(acc[t]) + sub4<1>(acc[t])) + (sub4<2>(acc[t]) + sub4<3>(acc[t]));
                     asm volatile("" : "+v"(s4));
+                    __builtin_amdgcn_sched_barrier(0);
                 });
                 float sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-                sum += __shfl_xor(sum, 32, 64);
+                sum = add_other_half(sum);
                 const float mean = sum * (1.0f / E);
                 const f32x4 mean4 = {mean, mean, mean, mean};
                 f32x4 q4 = {0.f, 0.f, 0.f, 0.f};
@@ -513,65 +639,31 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
                         q4 = __builtin_elementwise_fma(d, d, q4);
                     });
                     asm volatile("" : "+v"(q4));
+                    __builtin_amdgcn_sched_barrier(0);
                 });
                 float sq = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-                sq += __shfl_xor(sq, 32, 64);
-                const float rstd = rsqrtf(sq * (1.0f / E) + eps);
-                const float nmr = -mean * rstd;
-                rstd4 = f32x4{rstd, rstd, rstd, rstd};
-                nmr4 = f32x4{nmr, nmr, nmr, nmr};
+                sq = add_other_half(sq);
+                out_rstd = rsqrtf(sq * (1.0f / E) + eps);
+                out_nmr = -mean * out_rstd;
             }
-            char* const xo = x_out_img ? (char*)x + (grp * (32 * E * 4) + lane16) : (char*)x + ((size_t)grow * (E * 4) + half * 16);
-            const int xt = x_out_img ? 4096 : 128, xq = x_out_img ? 1024 : 32;
-            const bool x_store = x_out_img ? grp_valid : valid;
-            char* const op = act_blk ? (char*)xn_out + (grp * (32 * E * 2) + lane16) : (char*)xn_out + ((size_t)crow * (E * 2) + half * 16);
-            const int ostep = act_blk ? 1024 : 32;
-            const bool n_store = act_blk ? grp_valid : valid;
-            static_for<0, 12>([&](auto tt) {
-                constexpr int t = decltype(tt)::value;
-                if (x_store) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        f32x4 v;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[t][4 * q + r];
-                        *reinterpret_cast<f32x4*>(xo + xt * t + xq * q) = v;
-                    }
-                }
-                if (xn_out) {
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        // registers 8p..8p+3 = features 32t + 16p + 4 half + 0..3, registers 8p+4..8p+7 = the same + 8: one
-                        // v_permlane32_swap per register pair hands each lane eight CONSECUTIVE features (T21)
-                        const f32x4 n0 = __builtin_elementwise_fma(p ? sub4<2>(acc[t]) : sub4<0>(acc[t]), rstd4, nmr4);
-                        const f32x4 n1 = __builtin_elementwise_fma(p ? sub4<3>(acc[t]) : sub4<1>(acc[t]), rstd4, nmr4);
-                        vec4 lo, hi;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { lo[e] = (T)n0[e]; hi[e] = (T)n1[e]; }
-                        const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-                        u32x4 o;
-#pragma unroll
-                        for (int d2 = 0; d2 < 2; ++d2) {
-                            const auto sw = __builtin_amdgcn_permlane32_swap(l2[d2], h2[d2], false, false);
-                            o[d2] = sw[0];
-                            o[2 + d2] = sw[1];
-                        }
-                        if (n_store) *reinterpret_cast<u32x4*>(op + ostep * (2 * t + p)) = o;
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#ifndef BLOCKS_EPI_LATE_LOADS
-                load_x(next_tile, tt);                                   // accumulator tile t is free: the next tile's x goes in
-                __builtin_amdgcn_sched_barrier(0);
-#endif
-            });
-#ifdef BLOCKS_EPI_LATE_LOADS
-            static_for<0, 12>([&](auto tt) { load_x(next_tile, tt); });
-#endif
+            out_lanes();
+            out_x = rows_rsrc(x, tile, E * 4, x_out_img);
+            out_n = rows_rsrc(xn_out, tile, E * 2, act_blk);
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<0, 12>([&](auto n) { pair_op(I0, n); });
+            __builtin_amdgcn_sched_barrier(0);
+            x_in_of(next_tile);
+            static_for<12, 20>([&](auto n) { pair_op(I0, n); });
+            __builtin_amdgcn_sched_barrier(0);
         }
         BST(q5);
         BACC(10, q4, q5);
     }
+    // ---- the last tile's pairs 1..5
+    BST(q6);
+    static_for<1, 6>([&](auto P) { static_for<0, 12>([&](auto n) { pair_op(P, n); }); });
+    BST(q7);
+    BACC(11, q6, q7);
 #ifdef BLOCKS_STAMPS
     st[15] = bstamp() - tstart;
     if (lane == 0) for (int i = 0; i < 16; ++i) g_bsstamps[(blockIdx.x * 4 + wave) * 16 + i] = st[i];

@@ -1,0 +1,121 @@
+"""Tile boundaries of the single-role block kernel (``mst_block_fused_s``) on a real MI355X (``-m gpu``).
+
+The kernel stores a finished tile's rows, and fetches the next tile's, from inside the next tile's out-projection phases; only
+one accumulator pair and the attention rows move between two tiles, and the last tile of a workgroup drains behind the loop.
+What that schedule can get wrong is a function of how many tiles a workgroup owns and of where the rows end, so the row counts
+below are written for the 256-workgroup persistent grid of MI355X: a single partial group; fewer tiles than workgroups; exactly
+one tile per workgroup; uneven tile counts (some workgroups drain one tile earlier); a ragged last 32-row group.
+
+Reference and bars are those of ``tests/test_hip_ops.py::test_block_fused_single_role``: the block arithmetic in fp64 on the same
+(already rounded) operands, 1.5e-2 (bf16) / 2.5e-3 (fp16) of max(|proj|, |mlp|) for ``x`` and four times that, absolute, for the
+normalised rows.  The kernel is given the true row count M; in the blocked layouts the buffers hold whole 32-row groups, which it
+may write whole.  Behind them lie guard rows: they must come back untouched, and so must every buffer the call has no business
+in (``xn`` when none is asked for, the attention rows when ``xn`` goes elsewhere).
+"""
+import math
+
+import pytest
+import torch
+
+from mst import synth
+
+pytestmark = pytest.mark.gpu
+
+DT = {"bf16": torch.bfloat16, "fp16": torch.float16}
+TOL = {"bf16": 1.5e-2, "fp16": 2.5e-3}
+E, HID = 384, 1536
+GUARD = 64                                  # sentinel rows behind the buffers
+SENTINEL = 12288.0                          # exact in bf16 and fp16
+ROWS = [1, 31, 33, 127, 129, 128 * 255 + 1, 128 * 256, 128 * 256 + 97, 128 * 513 + 5]
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from mst import hip as h
+    h.load()
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return h
+
+
+def rnd(shape, seed, scale=1.0):
+    return torch.from_numpy(synth.hash_normal(tuple(shape), seed, 77)) * scale
+
+
+@pytest.fixture(scope="module")
+def weights():
+    wp, bp = rnd((E, E), 62) / math.sqrt(E), rnd((E,), 63) * 0.1
+    w1, b1 = rnd((HID, E), 51) / math.sqrt(E), rnd((HID,), 52) * 0.1
+    w2, b2 = rnd((E, HID), 53) / math.sqrt(HID), rnd((E,), 54) * 0.1
+    g, be = rnd((E,), 55) * 0.2 + 1, rnd((E,), 56) * 0.2
+    return wp, bp, w1, b1, w2, b2, g, be
+
+
+_case = {}                                  # the operands and the reference of the last (dt, M): six cases share them
+
+
+def operands_and_reference(dt, M, weights):
+    """x, attention rows and the fp64 block arithmetic on them (attention.py:67-68; block.py:89-94,112-113; mlp.py:34-40)."""
+    if _case.get("key") != (dt, M):
+        x = rnd((M, E), 60, 1.5) + 0.3
+        att = rnd((M, E), 61, 1.0).to(DT[dt])
+        wp, bp, w1, b1, w2, b2, g, be = (w.double() for w in weights)
+        outs, norms, scale = [], [], 0.0
+        for lo in range(0, M, 16384):       # row chunks bound the memory of the hidden layer
+            xd, ad = x[lo:lo + 16384].double(), att[lo:lo + 16384].double()
+            proj = ad @ wp.t() + bp
+            xmid = xd + proj
+            h = torch.nn.functional.layer_norm(xmid, (E,), g, be, 1e-6)
+            h = h @ w1.t() + b1
+            h = 0.5 * h * (1 + torch.erf(h / math.sqrt(2)))
+            y = h @ w2.t() + b2
+            ref = xmid + y
+            scale = max(scale, float(y.abs().max()), float(proj.abs().max()))
+            outs.append(ref)
+            norms.append(torch.nn.functional.layer_norm(ref, (E,)))
+        _case.update(key=(dt, M), val=(x, att, torch.cat(outs), torch.cat(norms), scale))
+    return _case["val"]
+
+
+@pytest.mark.parametrize("xn_mode", ["none", "own", "alias"])
+@pytest.mark.parametrize("layout", [0, 7])
+@pytest.mark.parametrize("M", ROWS)
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+def test_block_boundary(hip, weights, dt, M, layout, xn_mode):
+    tdt = DT[dt]
+    wp, bp, w1, b1, w2, b2, g, be = weights
+    x, att, ref, refn, scale = operands_and_reference(dt, M, weights)
+    seq, b1f, pbf, b2f = hip.pack_block_seq(wp.cuda(), bp.cuda(), None, w1.cuda(), b1.cuda(), w2.cuda(), b2.cuda(), g.cuda(), be.cuda(),
+                                            None, tdt)
+    # buffers: the rows the layout defines (whole 32-row groups when blocked), then guard rows nobody may touch
+    Mp = (M + 31) // 32 * 32 if layout else M
+    guarded = lambda body: torch.cat([body, torch.full((GUARD, E), SENTINEL, dtype=body.dtype, device="cuda")])
+    xb = torch.cat([x.cuda(), torch.zeros(Mp - M, E, device="cuda")])
+    ab = torch.cat([att.cuda(), torch.zeros(Mp - M, E, dtype=tdt, device="cuda")])
+    if layout:
+        xb, ab = hip.to_image32(xb), hip.to_blocked16(ab)
+    x_full, a_full = guarded(xb), guarded(ab)
+    n_full = torch.full((Mp + GUARD, E), SENTINEL, dtype=tdt, device="cuda")
+    xn_full = {"none": None, "own": n_full, "alias": a_full}[xn_mode]
+
+    # the kernel sees M rows of each buffer (one launch per case)
+    hip.block_fused_s(x_full[:M], a_full[:M], seq, b1f, pbf, b2f, None if xn_full is None else xn_full[:M], layout=layout)
+    torch.cuda.synchronize()
+
+    got_x = (hip.from_image32(x_full[:Mp]) if layout else x_full)[:M]
+    err_x = float((got_x.double().cpu() - ref).abs().max() / scale)
+    print(f"{dt} M={M} layout={layout} xn={xn_mode}: x error {err_x:.3e} of scale (bar {TOL[dt]:g})")
+    assert err_x < TOL[dt]
+    if xn_full is not None:
+        got_n = (hip.from_blocked16(xn_full[:Mp]) if layout else xn_full)[:M]
+        err_n = float((got_n.double().cpu() - refn).abs().max())
+        print(f"{dt} M={M} layout={layout} xn={xn_mode}: xn error {err_n:.3e} (bar {4 * TOL[dt]:g})")
+        assert err_n < 4 * TOL[dt]
+    # nothing behind the rows the layout defines was written, and no buffer the call did not name for writing
+    sent = lambda t: bool((t.float() == SENTINEL).all())
+    assert sent(x_full[Mp:]), "x: guard rows written"
+    assert sent(a_full[Mp:]), "attention rows / aliased xn: guard rows written"
+    assert sent(n_full[Mp:]), "xn: guard rows written"
+    if xn_mode != "own":
+        assert sent(n_full), "a buffer that was not passed was written"
+    if xn_mode != "alias":
+        assert torch.equal(a_full[:Mp], ab), "attention rows changed although xn_out is another buffer"

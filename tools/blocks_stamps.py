@@ -28,5 +28,6 @@ tiles = 2740 / 256.0
 m = lambda i: float(np.median(a[:, i])) / tiles
 print("cycles per TILE (median over waves; 108 phases: 12 proj, G1(0), 47 x (A, B), B(47))")
 print("total %.0f | proj: wait %.0f body %.0f (per phase %.0f + %.0f) | A: wait %.0f body %.0f (per phase %.0f + %.0f) | B: wait %.0f body %.0f (per phase %.0f + %.0f) | "
-      "G1(0) %.0f + %.0f | row loads issue %.0f | LN2 %.0f | epilogue %.0f" % (
-          m(15), m(0), m(1), m(0) / 12, m(1) / 12, m(2), m(3), m(2) / 47, m(3) / 47, m(4), m(5), m(4) / 48, m(5) / 48, m(6), m(7), m(8), m(9), m(10)))
+      "G1(0) %.0f + %.0f | LN2 %.0f | tile boundary (statistics, pair 0 out, attention rows + pair 0 in) %.0f" % (
+          m(15), m(0), m(1), m(0) / 12, m(1) / 12, m(2), m(3), m(2) / 47, m(3) / 47, m(4), m(5), m(4) / 48, m(5) / 48, m(6), m(7), m(9), m(10)))
+print("once per workgroup: pairs 1..5 of the last tile out %.0f cycles" % float(np.median(a[:, 11])))
