@@ -3,9 +3,9 @@
 // The [N,N] score matrix of attention.py:61-63 is never materialised.
 //
 // Workgroup = 4 waves x 32 query rows; K/V tiles of 64 keys are shared through a 2-deep LDS ring,
-// register-staged (global loads for tile t+1 are issued before the MFMAs of tile t and written to
-// LDS after them: one barrier per tile).  Per wave and tile:
-//   S^T[key][q] = K . Q^T   (v_mfma_f32_32x32x16, K rows via ds_read_b128 from a 144-byte-row
+// filled by LDS-DMA (the pieces of tile t+1 are issued before the MFMAs of tile t and waited for
+// after them: one barrier per tile).  Per wave and tile:
+//   S^T[key][q] = K . Q^T   (v_mfma_f32_32x32x16, K rows via ds_read_b128 from a slot-permuted 128-byte-row
 //                            image, Q fragments resident in registers, pre-multiplied by log2 e; the chain starts with one
 //                            extra MFMA that puts -r[q], the per-query softmax reference point, into every key row)  -> the query sits on the
 //                            lane, so the row max / sum are in-lane plus ONE cross-half shuffle;
@@ -23,32 +23,18 @@
 namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
-constexpr int KV_TILE_BYTES = 64 * 128;  // V tile: 64 keys x 64 dims x 2 B
-// K rows are PADDED to 144 B instead of XOR-swizzled: 36-dword rows put the 16 lanes of a ds_read_b128 group on 16 distinct
-// 4-bank groups (conflict-free), and every fragment address of a tile becomes ONE lane offset plus an immediate (the
-// XOR made each of the 8 reads its own lane function: ~25 address VALU ops per tile in an issue-bound loop).
+constexpr int KV_TILE_BYTES = 64 * 128;  // a K or V tile of unpadded rows: 64 keys x 64 dims x 2 B
+// The register-staged kernels of this file (probs_full16_kernel and below) PAD their K rows to 144 B instead of XOR-swizzling them:
+// 36-dword rows put the 16 lanes of a ds_read_b128 group on 16 distinct 4-bank groups (conflict-free), and every fragment address
+// of a tile becomes ONE lane offset plus an immediate (the XOR made each of the 8 reads its own lane function: ~25 address VALU ops
+// per tile in an issue-bound loop).
 constexpr int K_ROW = 144, K_TILE_BYTES = 64 * K_ROW;
-// -DATTN_NO_DMA restores the register-staged K/V tiles (global_load -> ds_write_b128 behind the MFMAs).  Default: LDS-DMA, 4 pieces
-// of 1 KiB per wave and tile (waves 0-1 the K tile, 2-3 the V tile), both tiles as 128-byte rows whose 16-byte slots are permuted on
-// the SOURCE side (K: slot = chunk ^ ((row >> 1) & 7), V: chunk ^ (((row >> 1) & 1) << 2)), so a piece is still 8 whole rows.
-#ifndef ATTN_NO_DMA
-#define ATTN_DMA 1
-#endif
+// attn16_kernel fills its K/V tiles by LDS-DMA: 4 pieces of 1 KiB per wave and tile (waves 0-1 the K tile, 2-3 the V tile), both
+// tiles as 128-byte rows whose 16-byte slots are permuted on the SOURCE side (K: slot = chunk ^ ((row >> 1) & 7),
+// V: chunk ^ (((row >> 1) & 1) << 2)), so a piece is still 8 whole rows.  (It replaced register staging: global_load -> ds_write_b128
+// behind the MFMAs.)
 // (Tried in round 2 and removed in round 3: fragment reads in asm, four in flight behind counted lgkmcnt waits instead of the compiler's
 // one read per MFMA -- 0.978 vs 0.970 ms: with four waves per SIMD the exposed LDS latency is already covered by the other waves.)
-
-// c + a.x + a.y for a pair of 16-bit values (v_dot2_f32_bf16 / v_dot2_f32_f16 against (1, 1)): the row sums of the ROUNDED probabilities,
-// two per instruction
-__device__ __forceinline__ float sum2(bf16_t x, bf16_t y, float c) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 v2;
-    const v2 a = {x, y}, one = {(bf16_t)1.0f, (bf16_t)1.0f};
-    return __builtin_amdgcn_fdot2_f32_bf16(a, one, c, false);
-}
-__device__ __forceinline__ float sum2(f16_t x, f16_t y, float c) {
-    typedef __attribute__((ext_vector_type(2))) _Float16 v2;
-    const v2 a = {x, y}, one = {(f16_t)1.0f, (f16_t)1.0f};
-    return __builtin_amdgcn_fdot2(a, one, c, false);
-}
 
 template <typename T>
 __device__ __forceinline__ typename V8<T>::type tr_pair(const char* p_lo, const char* p_hi) {
@@ -61,25 +47,16 @@ __device__ __forceinline__ typename V8<T>::type tr_pair(const char* p_lo, const 
 
 // The softmax reference point is subtracted by the matrix pipe (one extra MFMA per 32 keys instead of 32 vector subtractions:
 // measured -5 % on the bench shape when it went in, -9 % against the fma form re-measured with the LDS-DMA tiles).
-#ifndef ATTN_WG_WAVES
-#define ATTN_WG_WAVES 4      // query rows per workgroup = 32 x waves (K/V tiles shared by the workgroup); 8 waves measured 1.5 % slower at N = 1370 (6 x 256 rows pad 12 %, 11 x 128 pad 3 %)
-#endif
+constexpr int ATTN_WG_WAVES = 4;      // query rows per workgroup = 32 x waves (K/V tiles shared by the workgroup); 8 waves measured 1.5 % slower at N = 1370 (6 x 256 rows pad 12 %, 11 x 128 pad 3 %)
 constexpr int WGW = ATTN_WG_WAVES, WGT = 64 * WGW, QB = 32 * WGW;
-#ifndef ATTN_WAVES_PER_EU
-#define ATTN_WAVES_PER_EU 4   // 128 VGPRs (5 spilled dwords): 4 waves per SIMD measured 3.4 % faster than 3 at 148
-#endif
+constexpr int ATTN_WAVES_PER_EU = 4;   // 128 VGPRs (5 spilled dwords): 4 waves per SIMD measured 3.4 % faster than 3 at 148
 template <typename T>
 __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_PER_EU, ATTN_WAVES_PER_EU))) void attn16_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                      int N, int heads, int log2q, int out_blocked) {
     typedef typename V8<T>::type vec8;
-#ifdef ATTN_DMA
-    constexpr int KT_BYTES = KV_TILE_BYTES;              // unpadded K rows
-#else
-    constexpr int KT_BYTES = K_TILE_BYTES;
-#endif
-    __shared__ __attribute__((aligned(16))) char smem[2 * KT_BYTES + 2 * KV_TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) char smem[4 * KV_TILE_BYTES];   // K ring | V ring: both tiles as unpadded 128-byte rows
     char* const Ks = smem;
-    char* const Vs = smem + 2 * KT_BYTES;
+    char* const Vs = smem + 2 * KV_TILE_BYTES;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -104,7 +81,6 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
         for (int ds = 0; ds < 4; ++ds) bq[ds] = *reinterpret_cast<const vec8*>(qp + ds * 16);
     }
 
-#ifdef ATTN_DMA
     static_assert(WGW == 4 || WGW == 8, "the LDS-DMA staging map deals 16 pieces per tile to 4 or 8 waves");
     // piece p = PPW wave + u: p < 8 -> K rows 8p .. 8p+7, else V rows 8(p-8) ..; lane l -> row + (l >> 3), LDS slot l & 7
     constexpr int PPW = 16 / WGW;
@@ -119,18 +95,11 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
 #pragma unroll
     for (int u = 0; u < PPW; ++u) d_off[u] = (unsigned)(((d_row0 + 8 * u) * ld + ((u & 1) && !d_isv ? (d_col0 ^ 32) : d_col0)) * 2);
     auto dma = [&](int t, int buf) {
-        char* dst = (d_isv ? Vs + buf * KV_TILE_BYTES : Ks + buf * KT_BYTES) + (d_p0 & 7) * 1024;
-#ifdef ATTN_DMA_VADDR
-        if (false) {
-#else
+        char* dst = (d_isv ? Vs + buf * KV_TILE_BYTES : Ks + buf * KV_TILE_BYTES) + (d_p0 & 7) * 1024;
         if (t * 64 + 64 <= N) {
-#endif
             const char* tb = reinterpret_cast<const char*>(base) + (int64_t)t * 64 * ld * 2;
 #pragma unroll
             for (int u = 0; u < PPW; ++u) {
-#ifdef ATTN_ABL_HALF_DMA
-                if (u & 1) continue;
-#endif
                 // saddr + 32-bit lane offset, spelled out: hipcc widens the offsets to 64-bit register pairs and adds the
                 // base per piece otherwise (8 more registers -> spills, one more vector instruction per piece)
                 const unsigned m0v = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(dst + u * 1024);
@@ -154,44 +123,12 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
             }
         }
     };
-#endif
-    // ---- K/V staging map: 64 key rows x 8 chunks of 16 B per operand; thread -> key row sr, CPT consecutive chunks
-    constexpr int CPT = 512 / WGT;                       // chunks per thread and operand: 2 (4 waves) or 1 (8 waves)
-    const int sr = tid / (8 / CPT), sc0 = (tid % (8 / CPT)) * CPT;
-    int k_off[CPT], v_off[CPT];
-#pragma unroll
-    for (int c = 0; c < CPT; ++c) {
-        k_off[c] = sr * K_ROW + (sc0 + c) * 16;
-        v_off[c] = sr * 128 + (((sc0 + c) ^ (((sr >> 1) & 1) << 2)) * 16);
-    }
-    u32x4 rk[CPT], rv[CPT];
-    auto gload = [&](int t) {
-        int key = t * 64 + sr;
-        key = key < N ? key : N - 1;
-        const T* kp = base + (int64_t)key * ld + E + h * 64 + sc0 * 8;
-#pragma unroll
-        for (int c = 0; c < CPT; ++c) {
-            rk[c] = *reinterpret_cast<const u32x4*>(kp + 8 * c);
-            rv[c] = *reinterpret_cast<const u32x4*>(kp + E + 8 * c);
-        }
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int c = 0; c < CPT; ++c) {
-            *reinterpret_cast<u32x4*>(Ks + buf * K_TILE_BYTES + k_off[c]) = rk[c];
-            *reinterpret_cast<u32x4*>(Vs + buf * KV_TILE_BYTES + v_off[c]) = rv[c];
-        }
-    };
-
     // ---- per-lane LDS read offsets
-    // K (ds_read_b128): row = kb*32 + (lane&31), 16-byte chunk 2*ds + h2 of a 144-byte row
+    // K (ds_read_b128): row = kb*32 + (lane&31), 16-byte chunk 2*ds + h2 of a 128-byte row, slot-permuted as the DMA wrote it
     const int krow = lane & 31;
-#ifdef ATTN_DMA
     int k_off4[4];                                       // chunk 2 ds + h2 of row krow: + kb*4096 immediate
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) k_off4[ds] = krow * 128 + (((2 * ds + h2) ^ ((krow >> 1) & 7)) << 4);
-#endif
-    const int k_lane_off = krow * K_ROW + h2 * 16;       // + kb*32*K_ROW + ds*32: immediates
     // V (ds_read_b64_tr_b16): 16-lane group g: rows key0 + (i>>2), key0 = ks*16 + 4*h2,
     // columns db*32 + 16*(g&1) + 4*(i&3) .. +3  ->  chunk = db*4 + (g&1)*2 + ((i&3)>>1), +8 B if i odd
     const int vi = lane & 15;
@@ -219,13 +156,8 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
     constexpr float RT = 8.0f;
 
     const int nt = (N + 63) >> 6;
-#ifdef ATTN_DMA
     dma(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    gload(0);
-    lstore(0);
-#endif
     __syncthreads();
 
     // FAST mode.  The reference point only exists to keep exp2 inside the range of its type: when the first tile's maxima are small
@@ -237,11 +169,6 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
     constexpr float TH0 = std::is_same<T, f16_t>::value ? 8.0f : 60.0f;
     constexpr float GUARD = std::is_same<T, f16_t>::value ? 32768.0f : 1.2676506e30f;
     bool fast = false;                                   // wave-uniform
-#ifdef ATTN_NO_FAST
-    constexpr bool fast_allowed = false;
-#else
-    constexpr bool fast_allowed = true;
-#endif
 
     // one KV tile; MASK = the ragged last tile (keys >= N get -inf; its upper 32 keys are skipped altogether when none is valid).
     // Peeled so the 32 selects per tile that the compiler otherwise if-converts into EVERY iteration stay out of the steady-state loop.
@@ -253,15 +180,9 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
         constexpr bool MASK = decltype(mask_tag)::value;
         constexpr bool FAST = decltype(fast_tag)::value;
         const int buf = t & 1;
-#ifndef ATTN_ABL_NO_GLOAD
-#ifdef ATTN_DMA
         if (t + 1 < nt && !skip_dma) dma(t + 1, buf ^ 1);  // that buffer was last read in tile t-1: every wave is behind its barrier
-#else
-        if (t + 1 < nt && !skip_dma) gload(t + 1);
-#endif
-#endif
         if (wave_active) {
-            const char* Kb = Ks + buf * KT_BYTES;
+            const char* Kb = Ks + buf * KV_TILE_BYTES;
             const char* Vb = Vs + buf * KV_TILE_BYTES;
             f32x16 s[2];
             const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -284,17 +205,11 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
                         continue;
                     }
                     s[kb] = with_ref ? mfma32(kone, qneg, zero16) : zero16;      // -r[q] in every key row
-#ifndef ATTN_ABL_NO_QK
 #pragma unroll
                     for (int ds = 0; ds < 4; ++ds) {
-#ifdef ATTN_DMA
                         const vec8 a = *reinterpret_cast<const vec8*>(Kb + k_off4[ds] + kb * 4096);
-#else
-                        const vec8 a = *reinterpret_cast<const vec8*>(Kb + k_lane_off + kb * 32 * K_ROW + ds * 32);
-#endif
                         s[kb] = mfma32(a, bq[ds], s[kb]);
                     }
-#endif
                 }
                 if constexpr (MASK) {
 #pragma unroll
@@ -314,55 +229,31 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-#ifdef ATTN_ABL_NO_EXP
-                        float p = s[kb][r];
-                        asm volatile("" : "+v"(p));
-#else
                         const float p = __builtin_amdgcn_exp2f(s[kb][r]);
-#endif
                         s[kb][r] = p;
-#if !defined(ATTN_ABL_NO_SUM) && !defined(ATTN_SUM_DOT2)
-                        lsum += p;                       // one chain: four partial sums measured 3 % slower (registers)
-#endif
+                        lsum += p;                       // one chain: four partial sums measured 3 % slower (registers); v_dot2 sums of the rounded
+                        //                                  probabilities (16 instructions for 32 adds) measured 1.5 % slower (0.958 vs 0.944 ms)
                     }
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
                     for (int j = 0; j < 8; ++j) pf[ks][j] = (T)s[ks >> 1][(ks & 1) * 8 + j];
-#if !defined(ATTN_ABL_NO_SUM) && defined(ATTN_SUM_DOT2)
-                // -DATTN_SUM_DOT2: the sum of the probabilities as the P.V MFMA sees them (rounded to 16 bits), two per v_dot2: 16 instructions
-                // instead of 32 adds -- measured 1.5 % SLOWER (0.958 vs 0.944 ms), off
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                    for (int j = 0; j < 8; j += 2) lsum = sum2(pf[ks][j], pf[ks][j + 1], lsum);
-#endif
             };
             auto classic = [&]() {                       // running maximum, reference point, probabilities
-#ifdef ATTN_ABL_NO_MAX
-                float mx = 0.f;
-                asm volatile("" : "+v"(mx));
-                if (t < 0) {
-#else
                 float mx = s[0][0];
 #pragma unroll
                 for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
-#ifdef ATTN_BPERMUTE
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-#else
                 {   // the other half of the query's keys sits 32 lanes away: one v_permlane32_swap instead of an LDS round trip
                     // (ds_bpermute + a wait for every outstanding LDS operation) in the middle of every tile
                     const unsigned mu = __float_as_uint(mx);
                     const auto sw = __builtin_amdgcn_permlane32_swap(mu, mu, false, false);
                     mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
                 }
-#endif
-                if (t == 0 && fast_allowed && __all(fabsf(mx) <= TH0)) {
+                if (t == 0 && __all(fabsf(mx) <= TH0)) {
                     fast = true;                          // the reference point stays 0
                 } else if (t == 0 || !__all(mx <= RT)) {   // rare after the first tiles: move the reference point
-#endif
                     const bool mv = (t == 0) || (mx > RT);
                     const float r_new = mv ? (float)(T)(r_ref + mx) : r_ref;   // 16-bit representable
                     const float delta = r_new - r_ref;
@@ -391,30 +282,16 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 if (MASK && ks >= 2 && !upper) continue;  // p = 0 for all of those keys
-#ifdef ATTN_ABL_NO_PV
-                asm volatile("" : "+v"(oT[0]), "+v"(oT[1]) : "v"(pf[ks]));
-#else
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
                     const char* p = Vb + ks * 16 * 128 + v_lane_off + (((db * 4 + vchunk) ^ vsw) * 16);
                     const vec8 vf = tr_pair<T>(p, p + 8 * 128);
                     oT[db] = mfma32(vf, pf[ks], oT[db]);
                 }
-#endif
             }
         }
-#ifndef ATTN_ABL_NO_GLOAD
-#ifdef ATTN_DMA
-#ifndef ATTN_ABL_NO_WAIT
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of tile t+1 have landed
-#endif
-#else
-        if (t + 1 < nt) lstore(buf ^ 1);
-#endif
-#endif
-#ifndef ATTN_ABL_NO_BARRIER
         __syncthreads();
-#endif
         return true;
     };
     const int nt_full = (N & 63) ? nt - 1 : nt;
@@ -427,12 +304,6 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
     if (fast) {
         for (; t < nt_full; ++t)
             if (!tile_step(FULL, FASTM, t, false)) { resume = true; break; }
-#ifdef ATTN_FAST_RAGGED
-        if (!resume && t < nt) {
-            if (tile_step(RAGGED, FASTM, t, false)) t = nt;
-            else resume = true;
-        }
-#endif
     }
     for (; t < nt_full; ++t) {
         tile_step(FULL, CLASSIC, t, resume);

@@ -42,9 +42,7 @@ constexpr int BP_OFF = B1_OFF + HID * 4;                // fp32 b_proj [384]  (l
 constexpr int B2_OFF = BP_OFF + E * 4;                  // fp32 b2     [384]  (ls2 folded)
 constexpr int LDS_BYTES = B2_OFF + E * 4;               // 156,672
 constexpr int NF = 24;                                  // fragments (= MFMAs) per phase
-#ifndef BLOCKS_DEPTH
-#define BLOCKS_DEPTH 4
-#endif
+constexpr int BLOCKS_DEPTH = 4;
 constexpr int D = BLOCKS_DEPTH;                         // fragment reads in flight ahead of the MFMAs
 // Register sets of the fragment ring: D + 2, not D + 1.  The read issued in slot i must not target the set MFMA i-1 took its A
 // operand from: that MFMA is still executing, and the in-order wave then stalls AT THE READ until it has finished (write-after-read
@@ -54,11 +52,7 @@ static_assert(NF % R == 0, "fragment ring must tile the phase");
 // Slot i of an out-projection / GEMM2 phase takes fragment FRAG(i) = (tile t = i % 12, k-step p = i / 12): consecutive MFMAs go to
 // DIFFERENT accumulator tiles.  A dependent 32x32x16 MFMA (same accumulator as its predecessor) issued 48 cycles after it, an
 // independent one 32 (stamps: 48.5 cycles per slot in the GEMM1 chain, 44 with dependent pairs; profiles/r04b_*).
-#ifdef BLOCKS_PAIRS
-constexpr int frag_of(int i) { return i; }
-#else
 constexpr int frag_of(int i) { return 2 * (i % 12) + i / 12; }
-#endif
 // Out-projection phases consume the stream pair-major: ring element (P, H) holds, for accumulator tiles 2P and 2P + 1, the K-chunks
 // j = 6H .. 6H + 5 as fragment n = 4 (j - 6H) + 2 (t - 2P) + p.  Slot i takes tile 2P + i % 2 and k-step i / 2 of the twelve
 // (j, p) in ascending order: the two tiles alternate (a tile's own MFMAs are 64 cycles apart) and every accumulator element sees the
@@ -69,13 +63,7 @@ constexpr int frag_in_order(int i, int ord) { return ord == ORD_PAIR ? pair_frag
 constexpr int BIAS_SLOT = 8;                            // slot of a phase in which the next chunk's b1 is read
 
 template <int OFF, typename V> __device__ __forceinline__ void lds_read_b128(V& dst, unsigned addr) {
-#if defined(BLOCKS_WACC)
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(dst) : "v"(addr), "i"(OFF));
-#elif !defined(BLOCKS_NOREADS)
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
-#else
-    asm volatile("" : "=v"(dst) : "v"(addr));            // timing-only ablation: fragments are whatever the registers hold
-#endif
 }
 template <int OFF, typename V> __device__ __forceinline__ void lds_read_b128_acc(V& dst, unsigned addr) {   // into the accumulator file
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(dst) : "v"(addr), "i"(OFF));
@@ -181,11 +169,9 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     char* const wdst_wave = smem + wave * 6144;
     auto dma_piece = [&](int src_off, int slot, auto u_tag) {
         constexpr int u = decltype(u_tag)::value;
-#ifndef BLOCKS_NODMA
         // (the 12-bit immediate moves the source AND the LDS address: pieces 4 and 5 take a second base 4 KiB further on both sides)
         constexpr int hi = u >= 4 ? 4096 : 0;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, wlane_off, src_off + hi, u * 1024 - hi, 0);
-#endif
     };
     // Out-projection element (P, H) is gathered from the unchanged stream: piece n = 6 wave + u of the ring element is fragment
     // (4P + n % 4) of stream element 6H + n / 4.  Same lane address form, the per-piece source offset rides in an SGPR.
@@ -197,10 +183,8 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     }
     auto dma_pair_piece = [&](auto pe_tag, int slot, auto u_tag) {
         constexpr int u = decltype(u_tag)::value, pe = decltype(pe_tag)::value, hi = u >= 4 ? 4096 : 0;
-#ifndef BLOCKS_NODMA
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, (int)lane16,
                                                  pair_piece_off[u] + ((pe & 1) * 6 * ELEM_BYTES + (pe >> 1) * 4096), u * 1024 - hi, 0);
-#endif
     };
     static_for<0, AHEAD>([&](auto e0) { static_for<0, 6>([&](auto u) { dma_pair_piece(e0, decltype(e0)::value, u); }); });
     int dsrc = AHEAD * ELEM_BYTES, dslot = AHEAD;         // stream byte offset / ring slot of the next element to request
@@ -211,9 +195,6 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     vec8 hB[2][2];                                       // [chunk parity][k-step]: GELU outputs as GEMM2 B fragments
     vec8 w[R];                                           // weight fragment ring
     float ga[8], gb[8], gc[8];                           // GELU scratch of the eight values in flight
-#ifdef BLOCKS_NOFILL
-    hB[0][0] = hB[0][1] = hB[1][0] = hB[1][1] = vec8{};
-#endif
 
     int slot = 0;                                        // ring slot of the element the next phase consumes
     // LDS addresses of the bias tables: lane part + a wave-uniform offset, added where they are used (volatile: kept as loop
@@ -274,9 +255,9 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
                 lds_read_b128_acc<64>(bt2, baddr);
                 lds_read_b128_acc<96>(bt3, baddr);
             }
-#ifndef BLOCKS_WAIT1                                       // default since r04j: -1 % kernel time (1.074 -> 1.062 ms in the bench pipeline)
             // ONE counted wait per two slots: at an even slot fragments i and i + 1 have landed once only the reads behind
-            // fragment i + 1 are outstanding (fragments i + 2 .. last issued, plus the four b1 reads where they are younger)
+            // fragment i + 1 are outstanding (fragments i + 2 .. last issued, plus the four b1 reads where they are younger).
+            // A wait in every slot measured 1 % more kernel time (1.074 vs 1.062 ms in the bench pipeline).
             if constexpr (i % 2 == 0) {
                 constexpr int last = TAIL ? i + D : (i + D < NF - 1 ? i + D : NF - 1);
                 constexpr int younger_frags = last - (i + 1) > 0 ? last - (i + 1) : 0;
@@ -285,11 +266,6 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
             } else {
                 __builtin_amdgcn_sched_barrier(0);
             }
-#else
-            constexpr int younger_frags = TAIL ? D : (NF - 1 - i < D ? NF - 1 - i : D);
-            constexpr int younger_bias = (BQ >= 0 && i >= BIAS_SLOT && i <= BIAS_SLOT + D) ? 4 : 0;
-            wait_lgkm<younger_frags + younger_bias>();
-#endif
             if constexpr (BQ >= 0 && i == BIAS_SLOT + D + 1) {
                 // this slot's counted wait covers the four b1 reads: only now do the values exist for hipcc (an asm output it may
                 // copy at once -- it moved the in-flight registers into the accumulator file right behind the reads otherwise)
@@ -363,13 +339,7 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     auto gelu_fill = [&](auto hs_tag, auto part_tag) {
         return [&, hs_tag, part_tag](auto it) {
             constexpr int i = decltype(it)::value;
-#ifdef BLOCKS_NOFILL
-            // timing-only ablation: GELU = identity (the packs stay, so GEMM1 stays live)
-            if constexpr (i == 12) static_for<0, 8>([&](auto e) { hB[decltype(hs_tag)::value][decltype(part_tag)::value][decltype(e)::value] = (T)hq[decltype(hs_tag)::value][2 * decltype(part_tag)::value + (decltype(e)::value >> 2)][decltype(e)::value & 3]; });
-            if constexpr (false)
-#else
             if constexpr (i >= 1)
-#endif
                 static_for<0, OPS_PER_SLOT>([&](auto o) { gelu_op(hs_tag, part_tag, std::integral_constant<int, (i - 1) * OPS_PER_SLOT + decltype(o)::value>{}); });
         };
     };

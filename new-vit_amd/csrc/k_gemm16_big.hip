@@ -119,9 +119,7 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
             if (rem >= 2) wait_vm_barrier<2 * PS>();
             else if (rem == 1) wait_vm_barrier<PS>();
             else wait_vm_barrier<0>();
-#ifndef ABL_NOLOAD
             if (t + NSTAGE - 1 < nk) stage((t + NSTAGE - 1) & (NSTAGE - 1), t + NSTAGE - 1);
-#endif
             const char* sb = smem + (t & (NSTAGE - 1)) * STAGE_BYTES;
             vec8 wf[NI];
 #pragma unroll
@@ -129,17 +127,9 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const vec8 af = *reinterpret_cast<const vec8*>(sb + a_frag_off + j * 16 * 64);
-#ifndef ABL_NOMFMA
 #pragma unroll
                 for (int i = 0; i < NI; ++i) acc[i][j] = mfma16(wf[i], af, acc[i][j]);
-#else
-                asm volatile("" ::"v"(af));
-#endif
             }
-#ifdef ABL_NOMFMA
-#pragma unroll
-            for (int i = 0; i < NI; ++i) asm volatile("" ::"v"(wf[i]));
-#endif
         }
 
         // Every wave is past its last LDS read of this tile once it arrives here.  The next tile's first
@@ -207,10 +197,6 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
                         const int row = q / CPR, ch = q - row * CPR;
                         const int m = m_w + j * 16 + row;
                         const u32x4 t = *reinterpret_cast<const u32x4*>(stg + row * ROWB + ch * 16);
-#ifdef ABL_NOSTORE
-                        asm volatile("" ::"v"(t));
-                        continue;
-#endif
                         if (!FULL && m >= M) continue;
                         OutT* cp = C + (int64_t)m * ldc + n_w + ch * (16 / OB);
                         if constexpr (EPI == MST_EPI_RESIDUAL) {

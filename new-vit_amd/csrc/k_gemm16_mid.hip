@@ -17,15 +17,11 @@
 
 namespace {
 
-#ifndef MID_BK
-#define MID_BK 32         // 64: whole 128-byte lines per row and stage (8-row LDS-DMA pieces, 128-byte LDS rows, slot = chunk ^ ((row>>1)&7))
-#endif
+constexpr int MID_BK = 32;       // 64: whole 128-byte lines per row and stage (8-row LDS-DMA pieces, 128-byte LDS rows, slot = chunk ^ ((row>>1)&7))
 constexpr int BM = 128, BN = 384, BK = MID_BK;
 constexpr int A_BYTES = BM * BK * 2;              // 8 KiB
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;   // 32 KiB
-#ifndef MID_NSTAGE
-#define MID_NSTAGE 2      // 2 and 4 stages measured the same (0.58 ms on the QKV shape): the fill latency is not the limit
-#endif
+constexpr int MID_NSTAGE = 2;    // 2 and 4 stages measured the same (0.58 ms on the QKV shape): the fill latency is not the limit
 constexpr int NSTAGE = MID_NSTAGE;
 constexpr int STG_OFF = NSTAGE * STAGE_BYTES;     // epilogue staging behind the ring
 constexpr int LDS_BYTES = STG_OFF + 4 * 16 * (96 * 4 + 16);   // ring + staging (25.6 KiB covers fp32 rows)
@@ -33,9 +29,7 @@ constexpr int NI = 6, NJ = 8;                     // 16-wide sub-tiles per wave:
 constexpr int PA = BK / 16, PW = 3 * BK / 16, PS = PA + PW;   // LDS-DMA pieces (1 KiB) per wave per stage: A, W, total
 constexpr int RPP = 1024 / (BK * 2);              // rows per piece (16 / 8)
 constexpr int ROWB_K = BK * 2;                    // LDS row bytes (64 / 128)
-#ifndef MID_NBLK
-#define MID_NBLK 0        // 0 = one workgroup per compute unit of the device
-#endif
+constexpr int MID_NBLK = 0;      // 0 = one workgroup per compute unit of the device
 constexpr int NBLK = MID_NBLK;
 
 template <typename T, int EPI, typename OutT>
@@ -136,13 +130,7 @@ __global__ __launch_bounds__(256) void gemm16_mid_kernel(const T* __restrict__ A
             for (int j = 0; j < NJ; ++j) {
                 const vec8 af = *reinterpret_cast<const vec8*>(sb + ((a_frag_off + j * 16 * ROWB_K) ^ (h * 64)));
 #pragma unroll
-                for (int i = 0; i < NI; ++i) {
-#ifdef MID_ABL_NO_MFMA
-                    asm volatile("" : "+v"(acc[i][j]) : "v"(wf[i]), "v"(af));
-#else
-                    acc[i][j] = mfma16(wf[i], af, acc[i][j]);
-#endif
-                }
+                for (int i = 0; i < NI; ++i) acc[i][j] = mfma16(wf[i], af, acc[i][j]);
             }
             }
         }
@@ -158,38 +146,6 @@ __global__ __launch_bounds__(256) void gemm16_mid_kernel(const T* __restrict__ A
                 if (u < nk) stage((ring + u) % NSTAGE, u);
         }
 
-#ifdef MID_ABL_NO_STORE
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" ::"v"(acc[i][j]));
-        if (next >= ntiles) break;
-        tile = next;
-        continue;
-#endif
-#ifdef MID_ABL_DIRECT                                  // 8-byte lane pieces straight from the accumulators (32 B per token per instruction)
-        if constexpr (sizeof(OutT) == 2) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int m = m0 + j * 16 + (lane & 15);
-#pragma unroll
-                for (int i = 0; i < NI; ++i) {
-                    typedef __attribute__((ext_vector_type(4))) OutT o4;
-                    o4 pk;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float v = acc[i][j][r];
-                        if (nb + i * 16 + r < scale_cols) v *= col_scale;
-                        pk[r] = (OutT)v;
-                    }
-                    if (m < M) *reinterpret_cast<o4*>(C + (int64_t)m * ldc + nb + i * 16) = pk;
-                }
-            }
-            if (next >= ntiles) break;
-            tile = next;
-            continue;
-        }
-#endif
         // ---- epilogue: each wave transposes one 16-row x 96-column slab at a time through its private staging area and
         // moves it to / from global memory as 16-byte lane accesses along whole row segments (fp32: 384 B = three lines)
         {

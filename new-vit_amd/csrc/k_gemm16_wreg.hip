@@ -22,7 +22,8 @@
 // Measured (tools/wreg_clock.py, steady state after 2 s of launches, M = 350,720): 0.297 ms against 0.523 ms for the mid-tile
 // kernel.  The launch is power-limited: MFMAs + LDS reads alone hold 2.26 GHz (0.221 ms), the 808 MB store stream alone 2.36 GHz
 // (0.161 ms), both together 1.75-1.9 GHz -- 11 % more cycles than the arithmetic alone, 35 % more time
-// (profiles/r02v_qkv_wreg.txt).  Spreading the stores over the k-steps (-DWREG_SPREAD_ST) changes nothing.
+// (profiles/r02v_qkv_wreg.txt; the in-kernel clock stamps behind those figures are gone).  Spreading the stores over the k-steps
+// changed nothing.
 // XCD x (= blockIdx & 7) sweeps the x-th eighth of the chunks; inside it CU g works on column tile g % tiles_n.
 #include <cstdlib>
 
@@ -33,9 +34,7 @@ namespace {
 constexpr int KD = 384, BN = 384, CH = 32;
 constexpr int ROWB = KD * 2;                       // 768-byte LDS rows
 constexpr int SLOT = CH * ROWB;                    // 24 KiB per chunk
-#ifndef WREG_NSLOT
-#define WREG_NSLOT 4
-#endif
+constexpr int WREG_NSLOT = 4;
 constexpr int NSLOT = WREG_NSLOT;                  // chunks it+1 .. it+NSLOT-1 are in flight while chunk it is multiplied
 constexpr int STG_PITCH = ROWB + 16;                // staging rows: 784 bytes (a row shifts by 4 banks)
 constexpr int STG_BYTES = CH * STG_PITCH;          // one 32 x 384 output tile of the workgroup, 16-bit
@@ -104,11 +103,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const int64_t chunk_bytes = BLK ? (int64_t)SLOT : (int64_t)CH * lda * 2;
     auto issue_piece = [&](int chunk, int slot, int u) {
-#ifdef WREG_ABL_SAME_A
-        const char* base = reinterpret_cast<const char*>(A) + (int64_t)(chunk & 7) * chunk_bytes;
-#else
         const char* base = reinterpret_cast<const char*>(A) + (int64_t)chunk * chunk_bytes;
-#endif
         unsigned off = dma_off[u];
         const int valid = M - chunk * CH;
         if (!BLK && valid < CH) {                   // ragged last chunk: clamp the row (blocked: whole groups are allocated, rows past M are never stored)
@@ -118,11 +113,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             r = r < valid ? r : valid - 1;
             off = (unsigned)(r * (int)lda * 2 + ck * 16);
         }
-#ifdef WREG_ABL_NO_DMA
-        asm volatile("" ::"v"(off), "s"(base));
-#else
         __builtin_amdgcn_global_load_lds(GLB_PTR(base + off), LDS_PTR(smem + slot * SLOT + (wave * PPW + u) * 1024), 16, 0, 0);
-#endif
     };
 
     // ---- fragment reads: row 16 mt + frow, chunk 4 kt + kq  ->  byte r*768 + (kt >> 2)*256 + (((4 (kt & 3) + kq) ^ frow) << 4)
@@ -163,17 +154,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         char* cb = reinterpret_cast<char*>(C) + (int64_t)chunk * CH * ldc * 2;
         const int valid = M - chunk * CH;
         const u32x4 v = *reinterpret_cast<const u32x4*>(stg + fl_lds[j]);
-#ifdef WREG_ABL_NO_STORE
-        asm volatile("" ::"v"(v));
-#else
         if (valid >= CH || fl_row[j] < valid) {
-#ifdef WREG_PLAIN_ST
-            *reinterpret_cast<u32x4*>(cb + fl_glb[j]) = v;
-#else
             __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(cb + fl_glb[j]));   // write-once stream: 0.297 vs 0.310 ms
-#endif
         }
-#endif
     };
     auto flush = [&](int chunk, int it) {
 #pragma unroll
@@ -182,9 +165,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     int c = lo + jcu;
     if (c >= hi) return;
-#ifdef WREG_CLOCK                                   // diagnostic build: shader clock of this launch (s_memtime / s_memrealtime)
-    const uint64_t clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
 #pragma unroll
     for (int d = 0; d < NSLOT - 1; ++d)
         if (c + d * c_nt < hi) {
@@ -204,9 +184,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // lgkmcnt: this wave's staging writes
-#ifndef WREG_SPREAD_ST
         if (prev >= 0) flush(prev, it - 1);
-#endif
 
         const int slot = it % NSLOT;
         const int nxt = c + (NSLOT - 1) * c_nt, nslot = (it + NSLOT - 1) % NSLOT;
@@ -249,25 +227,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const vec8 a0 = __builtin_bit_cast(vec8, a[cur][0]), a1 = __builtin_bit_cast(vec8, a[cur][1]);
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-#ifdef WREG_ABL_NO_MFMA
-                asm volatile("" : "+v"(acc[0][t]), "+v"(acc[1][t]) : "v"(w[t][kt]), "v"(a0), "v"(a1));
-#else
                 acc[0][t] = mfma16(w[t][kt], a0, acc[0][t]);
                 acc[1][t] = mfma16(w[t][kt], a1, acc[1][t]);
-#endif
             }
             if ((kt & 3) == 1) {                    // k-steps 1, 5, 9: one piece of the chunk three ahead
                 __builtin_amdgcn_sched_barrier(0);
                 if (more) issue_piece(nxt, nslot, kt >> 2);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#ifdef WREG_SPREAD_ST
-            if ((kt & 3) == 3) {                    // k-steps 3, 7, 11: one 1 KiB store of the previous chunk
-                __builtin_amdgcn_sched_barrier(0);
-                if (prev >= 0) flush_piece(prev, it - 1, kt >> 2);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
         }
         put(it);
         prev = c;
@@ -275,14 +242,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // lgkmcnt: this wave's staging writes         // every wave's put of the last chunk (the compiler waits for its own LDS writes)
     flush(prev, last_it);
-#ifdef WREG_CLOCK
-    if (threadIdx.x == 0) {                         // overwrites the first 16 bytes of this workgroup's first output row: diagnostic only
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        uint64_t* o = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(C) + (int64_t)(lo + jcu) * CH * ldc * 2 + nt * BN * 2);
-        o[0] = __builtin_amdgcn_s_memtime() - clk_t0;
-        o[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-    }
-#endif
 }
 
 template <typename T, bool BLK>

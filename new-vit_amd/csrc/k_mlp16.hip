@@ -42,9 +42,7 @@ constexpr int NT = E / 16;                              // 24 output tiles (16 c
 constexpr int PC_CONS = 12;                             // LDS-DMA pieces per step issued by each consumer wave (of 12 per wave pair)
 constexpr int PC_PROD = 12 - PC_CONS;
 constexpr int DEPTH = 4;                                // fragment reads in flight ahead of the MFMAs
-#ifndef TILE_CYCLES
-#define TILE_CYCLES 150000                              // ~one 128-row tile (48 steps) in shader clocks: the de-phasing window
-#endif
+constexpr int TILE_CYCLES = 150000;                     // ~one 128-row tile (48 steps) in shader clocks: the de-phasing window
 
 template <int OFF, typename V> __device__ __forceinline__ void lds_read_b128(V& dst, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
@@ -59,23 +57,6 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
         static_for<I + 1, N>(f);
     }
 }
-
-#ifdef MLP_STAMPS
-// diagnostic build only (never shipped): per-wave cycle sums of the step phases, read back by mst_debug_mlp_stamps
-__device__ unsigned long long g_stamps[256 * 8 * 4];
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define STAMP(var) const unsigned long long var = stamp()
-#define ACCUM(slot, a, b) st[slot] += (b) - (a)
-#else
-#define STAMP(var)
-#define ACCUM(slot, a, b)
-#endif
 
 template <typename T>
 __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __restrict__ xn_out,
@@ -156,9 +137,6 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
         f32x4 bias_next[2];
         bias_next[0] = *reinterpret_cast<const f32x4*>(b1f + 4 * g);
         bias_next[1] = *reinterpret_cast<const f32x4*>(b1f + 16 + 4 * g);
-#ifdef MLP_STAMPS
-        unsigned long long st[4] = {0, 0, 0, 0};
-#endif
         f32x4 hp[2][2] = {};                             // pre-activations of the previous chunk [hidden tile][row tile]
         auto store_h = [&](const float (&gv)[16], int sc) {   // k order of GEMM2 = (hidden tile, register) order of GEMM1
 #pragma unroll
@@ -171,15 +149,12 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
         };
 #pragma unroll 1
         for (int s = 0; s <= last + 1; ++s) {
-            STAMP(t0);
             // this wave's pieces of group s-2 have landed; group s-1 (the newest PC_PROD VMEM ops) may stay in flight
             if constexpr (PC_PROD > 0) {
                 if (s <= last) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PC_PROD) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // H(s-2) writes drained before the hand-off
-            STAMP(t1);
-            ACCUM(0, t0, t1);
             if (s < last) {
                 const int c = s % NCHUNK;
                 if (c == 0) {
@@ -227,8 +202,6 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
                         }
                     }
                 }
-                STAMP(t2);
-                ACCUM(1, t1, t2);                        // LayerNorm prologue (c == 0 only)
                 // ---- GEMM1 of chunk c: 32 hidden units x 32 rows (accumulators start at b1), GELU, hand-off
                 const f32x4 b0 = bias_next[0], b1v = bias_next[1];
                 {
@@ -254,15 +227,11 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
                         gv[e] = gelu_sig<T>(hp[(e >> 2) & 1][e >> 3][e & 3]);
                     }
                 });
-                STAMP(t3);
-                ACCUM(2, t2, t3);                        // GEMM1 (+ GELU of the previous chunk)
                 store_h(gv, s - 1);                      // H(s-1); at s == 0 a dummy into the parity nobody reads yet
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) hp[i][j] = h[i][j];
-                STAMP(t4);
-                ACCUM(3, t3, t4);                        // hand-off
             } else if (s == last) {                      // drain: GELU + hand-off of the last chunk
                 float gv[16];
 #pragma unroll
@@ -270,27 +239,16 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
                 store_h(gv, s - 1);
             }
         }
-#ifdef MLP_STAMPS
-        if (lane == 0) for (int i = 0; i < 4; ++i) g_stamps[(blockIdx.x * 8 + wave) * 4 + i] = st[i];
-#endif
     } else {
         u32x4 R[2 * NT];                                 // acc[t][mt]: y^T accumulators
-#ifdef MLP_STAMPS
-        unsigned long long st[4] = {0, 0, 0, 0};
-#endif
 #pragma unroll 1
         for (int s = 0; s <= last + 1; ++s) {
-            STAMP(t0);
             // this wave's pieces of group s-2 have landed (group s-1, the newest PC_CONS VMEM ops, may stay in flight; at a tile
             // boundary the epilogue's stores are newer still, which only makes this wait stricter)
             if (s >= 2 && s <= last - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PC_CONS) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            STAMP(t1);
-            ACCUM(0, t0, t1);                            // DMA wait + barrier
             dma_group(s);
-            STAMP(t2);
-            ACCUM(1, t1, t2);                            // DMA addresses
             if (s >= 2) {
                 const int sc = s - 2, c = sc % NCHUNK;
                 if (c == 0) {
@@ -326,8 +284,6 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
                     ACC(q, 0) = __builtin_bit_cast(u32x4, mfma16(w[q], hf0, __builtin_bit_cast(f32x4, ACC(q, 0))));
                     ACC(q, 1) = __builtin_bit_cast(u32x4, mfma16(w[q], hf1, __builtin_bit_cast(f32x4, ACC(q, 1))));
                 });
-                STAMP(t3);
-                ACCUM(2, t2, t3);                        // GEMM2
                 if (c == NCHUNK - 1) {
                     // ---- epilogue of tile sc/48: store x (residual already inside), next LayerNorm from registers
                     const int tile = blockIdx.x + (sc / NCHUNK) * gridDim.x;
@@ -378,13 +334,8 @@ __global__ __launch_bounds__(512) void mlp16_kernel(float* __restrict__ x, T* __
                         }
                     }
                 }
-                STAMP(t4);
-                ACCUM(3, t3, t4);                        // epilogue (c == 47 only)
             }
         }
-#ifdef MLP_STAMPS
-        if (lane == 0) for (int i = 0; i < 4; ++i) g_stamps[(blockIdx.x * 8 + wave) * 4 + i] = st[i];
-#endif
     }
 }
 
@@ -402,12 +353,6 @@ int launch_t(float* x, void* xn_out, const void* wpack, const float* b1f, const 
 }
 
 }  // namespace
-
-#ifdef MLP_STAMPS
-extern "C" int mst_debug_mlp_stamps(unsigned long long* host, int n) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * n);
-}
-#endif
 
 int launch_mlp16(float* x, void* xn_out, int dt, const void* wpack, const float* b1f, const float* b2, int64_t M, int E_,
                  float eps, hipStream_t s) {

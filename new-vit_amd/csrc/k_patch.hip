@@ -14,9 +14,7 @@ namespace {
 
 constexpr int PATCH = 14, KP = 224;
 // tile = (2*TW*16)^2: 128x128 for 16-bit operands, 64x64 in fp32 mode (LDS: 116 KB / 113 KB)
-#ifndef PATCH_TILEW
-#define PATCH_TILEW 2      // 64-patch tiles: 59 KB of LDS, two workgroups per CU (0.42 ms vs 0.455 ms with 128-patch tiles)
-#endif
+constexpr int PATCH_TILEW = 2;      // 64-patch tiles: 59 KB of LDS, two workgroups per CU (0.42 ms vs 0.455 ms with 128-patch tiles)
 template <typename T> struct TileW { static constexpr int v = PATCH_TILEW; };
 template <> struct TileW<float> { static constexpr int v = 2; };
 

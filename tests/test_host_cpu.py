@@ -258,6 +258,35 @@ def test_csrc_environment_reads_are_thresholds_only():
             assert not re.search(name + r"(?![A-Z0-9_])", text), f"{f.relative_to(ROOT)} still names {name}"
 
 
+def test_csrc_has_no_compile_time_ablation_switches():
+    """The kernel files say what runs: the 54 `-D` switches that once selected a rejected or timing-only variant are gone from code,
+    tools and user documents (profiles/ and DESIGN.md keep the history), and the one conditional left in csrc/ is the per-phase cycle
+    counter of the single-role block kernel (BLOCKS_STAMPS, tools/blocks_stamps.py), a measurement and not an A/B path."""
+    removed = ("ATTN_DMA", "ATTN_NO_DMA", "ATTN_DMA_VADDR", "ATTN_NO_FAST", "ATTN_FAST_RAGGED", "ATTN_BPERMUTE", "ATTN_SUM_DOT2",
+               "ATTN_ABL_HALF_DMA", "ATTN_ABL_NO_GLOAD", "ATTN_ABL_NO_QK", "ATTN_ABL_NO_EXP", "ATTN_ABL_NO_SUM", "ATTN_ABL_NO_MAX",
+               "ATTN_ABL_NO_PV", "ATTN_ABL_NO_WAIT", "ATTN_ABL_NO_BARRIER",
+               "BLOCK_STAMPS", "BLOCK_DEBUG", "BLOCK_DMA_STRIDED", "BLOCK_NODMA", "BLOCK_DMA_LATE", "BLOCK_CONS_PRIO", "BLOCK_PROD_PRIO",
+               "BLOCK_WARM", "BLOCK_GELU_FIRST", "BLOCK_GELU_GROUP", "BLOCK_NT", "BLOCK_NT_XLD", "BLOCK_NT_XST", "BLOCK_NT_XN",
+               "ABL_NO_READS", "ABL_NO_GELU", "ABL_NO_MFMA_P", "ABL_NO_MFMA_C",
+               "BLOCKS_PAIRS", "BLOCKS_WACC", "BLOCKS_NOREADS", "BLOCKS_NODMA", "BLOCKS_NOFILL", "BLOCKS_WAIT1",
+               "WREG_ABL_SAME_A", "WREG_ABL_NO_DMA", "WREG_ABL_NO_STORE", "WREG_ABL_NO_MFMA", "WREG_PLAIN_ST", "WREG_SPREAD_ST", "WREG_CLOCK",
+               "MID_ABL_NO_MFMA", "MID_ABL_NO_STORE", "MID_ABL_DIRECT", "ABL_NOLOAD", "ABL_NOMFMA", "ABL_NOSTORE", "MLP_STAMPS")
+    assert len(set(removed)) == 54
+    for f in sorted((ROOT / "new-vit_amd" / "csrc").iterdir()):
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", f.read_text(), flags=re.M):
+            names = set(re.findall(r"[A-Za-z_]\w*", m.group(1).split("//")[0])) - {"defined"}
+            assert names == {"BLOCKS_STAMPS"} and f.name == "k_block16s.hip", f"{f.name}: {m.group(0).strip()}"
+    built = {".so", ".o", ".a", ".pyc", ".hsaco", ".co"}
+    texts = [ROOT / "README.md", ROOT / "INTEGRATION.md"]
+    for top in ("new-vit_amd", "include", "tools"):
+        texts += [f for f in (ROOT / top).rglob("*") if f.is_file() and f.suffix not in built
+                  and not any(part == "build" or part.startswith("build_") for part in f.relative_to(ROOT).parts)]
+    for f in texts:
+        text = f.read_text(errors="ignore")
+        for name in removed:
+            assert not re.search(r"(?<![A-Za-z0-9_])" + name + r"(?![A-Z0-9_])", text), f"{f.relative_to(ROOT)} still names {name}"
+
+
 def test_bench_flop_model_matches_the_oracle_and_survey():
     """bench.py owns its FLOP model (SURVEY.md 8d formula); the oracle's restatement of it must agree."""
     sys.path.insert(0, str(ROOT))
