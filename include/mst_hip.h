@@ -129,6 +129,16 @@ int mst_attention_train_fwd(const void* qkv16, int dtype, int n_seq, int N, int 
 int mst_attention_train_bwd(const void* qkv16, int dtype, const float* out, const float* dout, const float* lse, int n_seq, int N,
                             int heads, int head_dim, float dq_scale, float* dqkv, void* workspace, size_t workspace_bytes,
                             mst_stream_t stream);
+/* The same pair with `out` in qkv16's own 16-bit type (train_storage='16bit': the reference's autocast keeps the attention output in
+ * 16 bits, attention.py:56-66 under main_train.py:110-123).  mst_attention_train_fwd16: the same kernel, the normalised fp32 output
+ * rounded to nearest even in the epilogue -- out16 [n_seq*N, heads*64] holds the bits of T(out of mst_attention_train_fwd), lse is
+ * identical.  mst_attention_train_bwd16: D = rowsum(dout o float(out16)); everything else as mst_attention_train_bwd (same workspace
+ * size, same argument rules, same determinism). */
+int mst_attention_train_fwd16(const void* qkv16, int dtype, int n_seq, int N, int heads, int head_dim, void* out16, float* lse,
+                              mst_stream_t stream);
+int mst_attention_train_bwd16(const void* qkv16, int dtype, const void* out16, const float* dout, const float* lse, int n_seq, int N,
+                              int heads, int head_dim, float dq_scale, float* dqkv, void* workspace, size_t workspace_bytes,
+                              mst_stream_t stream);
 
 /* Bicubic resampling of the patch position grid: vision_transformer.py:179-211 (F.interpolate bicubic).
  * offset = interpolate_offset (l.194-202): != 0 -> scale_factor = (g + offset) / M, the vendored default 0.1; 0 -> the
@@ -341,6 +351,35 @@ int mst_pos_embed_interp_bwd(const float* dout, int M, int E, int gh, int gw, do
  * dx and wsum 16-byte aligned.  Exact fp32 MFMA, no atomics: bit-reproducible, one entry point for both determinism modes. */
 int mst_patch_embed_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wsum, int n, int H, int W, int E,
                           float* dvol, mst_stream_t stream);
+
+/* 16-bit storage mode of the training step (mst/train.py, train_storage='16bit'): under the reference's Trainer(precision='16-mixed')
+ * (scripts/main_train.py:110-123) autocast keeps what a block saves for its backward (block.py:89-114) in the 16-bit type T = dtype
+ * (MST_BF16 / MST_F16); the residual stream and every gradient stay fp32.  Conversions to T round to nearest even.  Any other dtype,
+ * a misaligned base or a shape outside the rules below returns MST_EINVAL.
+ * mst_residual_layernorm16: one pass over `rows` contiguous rows of `cols` elements (block.py:108-113 residual + layer_scale.py:26-27
+ *   + the next nn.LayerNorm, block.py:63,75):  x_out[r][c] = x_in[r][c] + gamma[c] * float(br[r][c])  (fp32, one rounding; gamma NULL:
+ *   no LayerScale),  y[r] = T(LayerNorm(x_out[r]; ln_w, ln_b, eps)).  y NULL: the residual only (ln_w, ln_b unused).  x_out must not alias x_in.
+ *   cols a multiple of 8 (every row 16-byte aligned in both types), <= 2048; all bases 16-byte aligned.
+ * mst_act_fwd16 / mst_act_bwd16: y[i] = T(act(float(h[i]))) and dy[i] (fp32, in place) *= act'(float(h[i])), kind as mst_act_fwd (mlp.py:22):
+ *   the fp32 formulas of mst_act_fwd / mst_act_bwd, so the results are theirs on the upcast h bit for bit.  n may be ANY positive
+ *   count (whole groups of 8, then a scalar tail); h, y, dy 16-byte aligned.
+ * mst_colsum_b16 / mst_colsum_b16_ordered: out[c] += sum_r a[r][c] * float(b[r][c]) -- the LayerScale gradient (layer_scale.py:25-27) with
+ *   the saved branch output in T; mst_colsum's `b` form.  cols and both row strides multiples of 4, strides >= cols, a 16-byte and b 8-byte
+ *   aligned.  The ordered form follows the ORDER CONTRACT below with the plan, the order and the workspace of mst_colsum_ordered
+ *   (mst_colsum_ordered_workspace_bytes(rows, cols) bytes): its result has the bits of mst_colsum_ordered on the upcast b.
+ * mst_transpose16: out[c][r] = x[r][c] for r < rows, 0 for rows <= r < rows_pad (x [rows, cols] T with row stride ldx, out [cols, rows_pad] T
+ *   with row stride ldo >= rows_pad): the 16-bit-input counterpart of mst_cvt16(transpose = 1), the operand image of d weight = dY^T . X
+ *   above 12,288 tokens (mst_gemm16_splitk). */
+int mst_residual_layernorm16(const float* x_in, const void* br, int dtype, const float* gamma, float* x_out, const float* ln_w,
+                             const float* ln_b, void* y, int64_t rows, int cols, float eps, mst_stream_t stream);
+int mst_act_fwd16(const void* h, void* y, int dtype, int64_t n, int kind, mst_stream_t stream);
+int mst_act_bwd16(const void* h, int dtype, float* dy, int64_t n, int kind, mst_stream_t stream);
+int mst_colsum_b16(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
+                   mst_stream_t stream);
+int mst_colsum_b16_ordered(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
+                           void* workspace, size_t workspace_bytes, mst_stream_t stream);
+int mst_transpose16(const void* x, int dtype, int64_t ldx, int64_t rows, int cols, void* out, int64_t ldo, int64_t rows_pad,
+                    mst_stream_t stream);
 
 /* Fixed-order (deterministic) forms of every floating-point reduction of the training steps and of mst_znorm: what the Python layer calls
  * while torch.are_deterministic_algorithms_enabled().  ORDER CONTRACT: for fixed shape arguments (rows, cols, n, H, W, C, M, E, gh, gw,

@@ -98,9 +98,10 @@ struct Stage2 {
     }
 };
 
-// ---- forward: O fp32 [n*N, heads*64], LSE fp32 [n, heads, N] (natural log)
-template <typename T>
-__global__ __launch_bounds__(WGT) void attn_train_fwd_kernel(const T* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
+// ---- forward: O [n*N, heads*64] in OT (fp32, or T itself: the 16-bit storage mode rounds the normalised output in the epilogue),
+// LSE fp32 [n, heads, N] (natural log)
+template <typename T, typename OT>
+__global__ __launch_bounds__(WGT) void attn_train_fwd_kernel(const T* __restrict__ qkv, OT* __restrict__ out, float* __restrict__ lse,
                                                             int N, int heads) {
     typedef typename V8<T>::type vec8;
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE];      // [buffer][K | V]
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(WGT) void attn_train_fwd_kernel(const T* __restrict
         const float inv = 1.0f / l_tot;
         if (q < N) {
             const int64_t R = (int64_t)seq * N + q;
-            float* op = out + R * E + h * 64 + 4 * h2;                     // O^T[d = 32 db + 8 g + 4 h2 + e][q]
+            OT* op = out + R * E + h * 64 + 4 * h2;                        // O^T[d = 32 db + 8 g + 4 h2 + e][q]
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -199,7 +200,14 @@ __global__ __launch_bounds__(WGT) void attn_train_fwd_kernel(const T* __restrict
                     f32x4 v;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = o[db][4 * g + e] * inv;
-                    *reinterpret_cast<f32x4*>(op + db * 32 + g * 8) = v;
+                    if constexpr (sizeof(OT) == 4) {
+                        *reinterpret_cast<f32x4*>(op + db * 32 + g * 8) = v;
+                    } else {
+                        typename V8<T>::half_type v16;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v16[e] = (T)f32_rounded(v[e]);   // the bits of T(the fp32 output)
+                        *reinterpret_cast<typename V8<T>::half_type*>(op + db * 32 + g * 8) = v16;
+                    }
                 }
             if (h2 == 0) lse[((int64_t)seq * heads + h) * N + q] = (m + __log2f(l_tot)) * LN2;
         }
@@ -207,9 +215,10 @@ __global__ __launch_bounds__(WGT) void attn_train_fwd_kernel(const T* __restrict
 }
 
 // ---- backward preprocess: one workgroup per (sequence, head).  Pass 1: m = max |dO| -> scale c = 2^(6 - e), m in [2^(e-1), 2^e).
-// Pass 2 (8 lanes per row): Dv[seq][h][q] = c sum_d dO o O (fp32 operands), do16 = 16-bit image of c dO; cs[seq][h] = c.
-template <typename T>
-__global__ __launch_bounds__(256) void attn_train_pre_kernel(const float* __restrict__ O, const float* __restrict__ dO, T* __restrict__ do16,
+// Pass 2 (8 lanes per row): Dv[seq][h][q] = c sum_d dO o O (fp32 products; O fp32, or T as the 16-bit storage mode keeps it), do16 =
+// 16-bit image of c dO; cs[seq][h] = c.
+template <typename T, typename OT>
+__global__ __launch_bounds__(256) void attn_train_pre_kernel(const OT* __restrict__ O, const float* __restrict__ dO, T* __restrict__ do16,
                                                             float* __restrict__ Dv, float* __restrict__ cs, int N, int heads) {
     typedef typename V8<T>::type vec8;
     __shared__ float red[4];
@@ -232,7 +241,15 @@ __global__ __launch_bounds__(256) void attn_train_pre_kernel(const float* __rest
     for (int q = tid >> 3; q < N; q += 32) {
         const int64_t off = (row0 + q) * E + h * 64 + sub * 8;
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(dO + off), a1 = *reinterpret_cast<const f32x4*>(dO + off + 4);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(O + off), b1 = *reinterpret_cast<const f32x4*>(O + off + 4);
+        f32x4 b0, b1;
+        if constexpr (sizeof(OT) == 4) {
+            b0 = *reinterpret_cast<const f32x4*>(O + off);
+            b1 = *reinterpret_cast<const f32x4*>(O + off + 4);
+        } else {
+            const vec8 o8 = *reinterpret_cast<const vec8*>(O + off);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { b0[k] = (float)o8[k]; b1[k] = (float)o8[4 + k]; }
+        }
         float acc = 0.f;
         vec8 v;
 #pragma unroll
@@ -467,18 +484,20 @@ size_t attn_train_workspace_bytes(int n_seq, int N, int heads) {
     return align256(rows * heads * 64 * 2) + align256(rows * heads * 4) + align256((size_t)n_seq * heads * 4);
 }
 
-int launch_attn_train_fwd(const void* qkv, int dt, int n_seq, int N, int heads, float* out, float* lse, hipStream_t s) {
+int launch_attn_train_fwd(const void* qkv, int dt, int n_seq, int N, int heads, void* out, int out16, float* lse, hipStream_t s) {
     MST_CHECK_ARG(n_seq > 0 && N > 0 && heads > 0, "attention_train_fwd: bad sizes n_seq=%d N=%d heads=%d", n_seq, N, heads);
     const int64_t nwg = (int64_t)((N + 127) / 128) * heads * n_seq;
     MST_CHECK_ARG(nwg < (1ll << 31), "attention_train_fwd: grid too large");
     const dim3 grid((unsigned)nwg), block(WGT);
-    if (dt == MST_BF16) attn_train_fwd_kernel<bf16_t><<<grid, block, 0, s>>>((const bf16_t*)qkv, out, lse, N, heads);
-    else if (dt == MST_F16) attn_train_fwd_kernel<f16_t><<<grid, block, 0, s>>>((const f16_t*)qkv, out, lse, N, heads);
+    if (dt == MST_BF16 && out16) attn_train_fwd_kernel<bf16_t, bf16_t><<<grid, block, 0, s>>>((const bf16_t*)qkv, (bf16_t*)out, lse, N, heads);
+    else if (dt == MST_BF16) attn_train_fwd_kernel<bf16_t, float><<<grid, block, 0, s>>>((const bf16_t*)qkv, (float*)out, lse, N, heads);
+    else if (dt == MST_F16 && out16) attn_train_fwd_kernel<f16_t, f16_t><<<grid, block, 0, s>>>((const f16_t*)qkv, (f16_t*)out, lse, N, heads);
+    else if (dt == MST_F16) attn_train_fwd_kernel<f16_t, float><<<grid, block, 0, s>>>((const f16_t*)qkv, (float*)out, lse, N, heads);
     else { mst_set_error("attention_train_fwd: dtype %d unsupported (bf16 or fp16 qkv)", dt); return MST_EINVAL; }
     return mst_check_launch("attention_train_fwd");
 }
 
-int launch_attn_train_bwd(const void* qkv, int dt, const float* out, const float* dout, const float* lse, int n_seq, int N, int heads,
+int launch_attn_train_bwd(const void* qkv, int dt, const void* out, int out16, const float* dout, const float* lse, int n_seq, int N, int heads,
                           float dq_scale, float* dqkv, void* ws, size_t ws_bytes, hipStream_t s) {
     MST_CHECK_ARG(n_seq > 0 && N > 0 && heads > 0, "attention_train_bwd: bad sizes n_seq=%d N=%d heads=%d", n_seq, N, heads);
     MST_CHECK_ARG(dt == MST_BF16 || dt == MST_F16, "attention_train_bwd: dtype %d unsupported (bf16 or fp16 qkv)", dt);
@@ -494,12 +513,14 @@ int launch_attn_train_bwd(const void* qkv, int dt, const float* out, const float
     const dim3 grid((unsigned)nwg), block(WGT);
     if (dt == MST_BF16) {
         bf16_t* o16 = (bf16_t*)w;
-        attn_train_pre_kernel<bf16_t><<<dim3((unsigned)pre_blocks), dim3(256), 0, s>>>(out, dout, o16, Dv, cs, N, heads);
+        if (out16) attn_train_pre_kernel<bf16_t, bf16_t><<<dim3((unsigned)pre_blocks), dim3(256), 0, s>>>((const bf16_t*)out, dout, o16, Dv, cs, N, heads);
+        else attn_train_pre_kernel<bf16_t, float><<<dim3((unsigned)pre_blocks), dim3(256), 0, s>>>((const float*)out, dout, o16, Dv, cs, N, heads);
         attn_train_dkv_kernel<bf16_t><<<grid, block, 0, s>>>((const bf16_t*)qkv, o16, lse, Dv, cs, dqkv, N, heads);
         attn_train_dq_kernel<bf16_t><<<grid, block, 0, s>>>((const bf16_t*)qkv, o16, lse, Dv, cs, dqkv, N, heads, dq_scale);
     } else {
         f16_t* o16 = (f16_t*)w;
-        attn_train_pre_kernel<f16_t><<<dim3((unsigned)pre_blocks), dim3(256), 0, s>>>(out, dout, o16, Dv, cs, N, heads);
+        if (out16) attn_train_pre_kernel<f16_t, f16_t><<<dim3((unsigned)pre_blocks), dim3(256), 0, s>>>((const f16_t*)out, dout, o16, Dv, cs, N, heads);
+        else attn_train_pre_kernel<f16_t, float><<<dim3((unsigned)pre_blocks), dim3(256), 0, s>>>((const float*)out, dout, o16, Dv, cs, N, heads);
         attn_train_dkv_kernel<f16_t><<<grid, block, 0, s>>>((const f16_t*)qkv, o16, lse, Dv, cs, dqkv, N, heads);
         attn_train_dq_kernel<f16_t><<<grid, block, 0, s>>>((const f16_t*)qkv, o16, lse, Dv, cs, dqkv, N, heads, dq_scale);
     }

@@ -159,7 +159,14 @@ int mst_attention_train_fwd(const void* qkv16, int dtype, int n_seq, int N, int 
                             mst_stream_t stream) {
     MST_CHECK_ARG(qkv16 && out && lse, "attention_train_fwd: null pointer");
     MST_CHECK_ARG(head_dim == 64, "attention_train_fwd: head_dim=%d unsupported (64)", head_dim);
-    return launch_attn_train_fwd(qkv16, dtype, n_seq, N, heads, out, lse, (hipStream_t)stream);
+    return launch_attn_train_fwd(qkv16, dtype, n_seq, N, heads, out, 0, lse, (hipStream_t)stream);
+}
+
+int mst_attention_train_fwd16(const void* qkv16, int dtype, int n_seq, int N, int heads, int head_dim, void* out16, float* lse,
+                              mst_stream_t stream) {
+    MST_CHECK_ARG(qkv16 && out16 && lse, "attention_train_fwd16: null pointer");
+    MST_CHECK_ARG(head_dim == 64, "attention_train_fwd16: head_dim=%d unsupported (64)", head_dim);
+    return launch_attn_train_fwd(qkv16, dtype, n_seq, N, heads, out16, 1, lse, (hipStream_t)stream);
 }
 
 int mst_attention_train_bwd(const void* qkv16, int dtype, const float* out, const float* dout, const float* lse, int n_seq, int N,
@@ -167,7 +174,16 @@ int mst_attention_train_bwd(const void* qkv16, int dtype, const float* out, cons
                             mst_stream_t stream) {
     MST_CHECK_ARG(qkv16 && out && dout && lse && dqkv, "attention_train_bwd: null pointer");
     MST_CHECK_ARG(head_dim == 64, "attention_train_bwd: head_dim=%d unsupported (64)", head_dim);
-    return launch_attn_train_bwd(qkv16, dtype, out, dout, lse, n_seq, N, heads, dq_scale, dqkv, workspace, workspace_bytes,
+    return launch_attn_train_bwd(qkv16, dtype, out, 0, dout, lse, n_seq, N, heads, dq_scale, dqkv, workspace, workspace_bytes,
+                                 (hipStream_t)stream);
+}
+
+int mst_attention_train_bwd16(const void* qkv16, int dtype, const void* out16, const float* dout, const float* lse, int n_seq, int N,
+                              int heads, int head_dim, float dq_scale, float* dqkv, void* workspace, size_t workspace_bytes,
+                              mst_stream_t stream) {
+    MST_CHECK_ARG(qkv16 && out16 && dout && lse && dqkv, "attention_train_bwd16: null pointer");
+    MST_CHECK_ARG(head_dim == 64, "attention_train_bwd16: head_dim=%d unsupported (64)", head_dim);
+    return launch_attn_train_bwd(qkv16, dtype, out16, 1, dout, lse, n_seq, N, heads, dq_scale, dqkv, workspace, workspace_bytes,
                                  (hipStream_t)stream);
 }
 
@@ -227,6 +243,34 @@ int mst_act_fwd(const float* h, float* y, int64_t n, int kind, mst_stream_t stre
 int mst_act_bwd(const float* h, float* dy, int64_t n, int kind, mst_stream_t stream) {
     MST_CHECK_ARG(h && dy && n > 0 && (kind == 0 || kind == 1), "act_bwd: bad arguments");
     return launch_act_bwd(h, dy, n, kind, (hipStream_t)stream);
+}
+// ---- 16-bit storage mode of the training step (k_train16.hip)
+int mst_residual_layernorm16(const float* x_in, const void* br, int dtype, const float* gamma, float* x_out, const float* ln_w,
+                             const float* ln_b, void* y, int64_t rows, int cols, float eps, mst_stream_t stream) {
+    MST_CHECK_ARG(x_in && br && x_out && (!y || (ln_w && ln_b)), "residual_layernorm16: null pointer");
+    return launch_residual_layernorm16(x_in, br, dtype, gamma, x_out, ln_w, ln_b, y, rows, cols, eps, (hipStream_t)stream);
+}
+int mst_act_fwd16(const void* h, void* y, int dtype, int64_t n, int kind, mst_stream_t stream) {
+    MST_CHECK_ARG(h && y && n > 0 && (kind == 0 || kind == 1), "act_fwd16: bad arguments");
+    return launch_act_fwd16(h, y, dtype, n, kind, (hipStream_t)stream);
+}
+int mst_act_bwd16(const void* h, int dtype, float* dy, int64_t n, int kind, mst_stream_t stream) {
+    MST_CHECK_ARG(h && dy && n > 0 && (kind == 0 || kind == 1), "act_bwd16: bad arguments");
+    return launch_act_bwd16(h, dtype, dy, n, kind, (hipStream_t)stream);
+}
+int mst_colsum_b16(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
+                   mst_stream_t stream) {
+    MST_CHECK_ARG(a && b && out, "colsum_b16: null pointer");
+    return launch_colsum_b16(a, a_stride, b, b_dtype, b_stride, rows, cols, out, (hipStream_t)stream);
+}
+int mst_colsum_b16_ordered(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
+                           void* workspace, size_t workspace_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(a && b && out, "colsum_b16_ordered: null pointer");
+    return launch_colsum_b16_ordered(a, a_stride, b, b_dtype, b_stride, rows, cols, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int mst_transpose16(const void* x, int dtype, int64_t ldx, int64_t rows, int cols, void* out, int64_t ldo, int64_t rows_pad,
+                    mst_stream_t stream) {
+    return launch_transpose16(x, dtype, ldx, rows, cols, out, ldo, rows_pad, (hipStream_t)stream);
 }
 int mst_colsum(const float* a, int64_t a_stride, const float* b, int64_t b_stride, int64_t rows, int cols, float* out,
                mst_stream_t stream) {

@@ -47,6 +47,14 @@ __device__ __forceinline__ float to_f32(bf16_t v) { return (float)v; }
 __device__ __forceinline__ float to_f32(f16_t v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return (T)v; }
 
+// v as an fp32 register the compiler cannot look through: a conversion to 16 bits behind it rounds the ROUNDED fp32 value.  Without it
+// hipcc folds a product and its conversion into one v_fma_mixlo_f16 (a single rounding), and a 16-bit output is no longer the rounded
+// fp32 output of the same kernel bit for bit.
+__device__ __forceinline__ float f32_rounded(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -180,9 +188,19 @@ int launch_conv_wgrad16(const void* dz, const void* x, int dt, int n, int H, int
                         int nsplit, int64_t rows_per_split, hipStream_t s);
 // memory-efficient training attention (k_attn16_train.hip)
 size_t attn_train_workspace_bytes(int n_seq, int N, int heads);
-int launch_attn_train_fwd(const void* qkv, int dt, int n_seq, int N, int heads, float* out, float* lse, hipStream_t s);
-int launch_attn_train_bwd(const void* qkv, int dt, const float* out, const float* dout, const float* lse, int n_seq, int N, int heads,
+// out16: `out` is in qkv's 16-bit type instead of fp32 (the 16-bit storage mode of the training step)
+int launch_attn_train_fwd(const void* qkv, int dt, int n_seq, int N, int heads, void* out, int out16, float* lse, hipStream_t s);
+int launch_attn_train_bwd(const void* qkv, int dt, const void* out, int out16, const float* dout, const float* lse, int n_seq, int N, int heads,
                           float dq_scale, float* dqkv, void* ws, size_t ws_bytes, hipStream_t s);
+// row kernels of the 16-bit storage mode (k_train16.hip)
+int launch_residual_layernorm16(const float* xin, const void* br, int dt, const float* gamma, float* xout, const float* w, const float* b,
+                                void* y, int64_t rows, int cols, float eps, hipStream_t s);
+int launch_act_fwd16(const void* h, void* y, int dt, int64_t n, int kind, hipStream_t s);
+int launch_act_bwd16(const void* h, int dt, float* dy, int64_t n, int kind, hipStream_t s);
+int launch_colsum_b16(const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out, hipStream_t s);
+int launch_colsum_b16_ordered(const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out, void* ws,
+                              size_t ws_bytes, hipStream_t s);
+int launch_transpose16(const void* x, int dt, int64_t ldx, int64_t rows, int cols, void* out, int64_t ldo, int64_t rows_pad, hipStream_t s);
 int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const float* freqs, float sign, hipStream_t s);
 int launch_im2col_nhwc16(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, void* col, int dt, hipStream_t s);
 int launch_maxpool_nhwc16(const void* x, int dt, int n, int H, int W, int C, void* y, hipStream_t s);

@@ -69,6 +69,8 @@ SIGNATURES = {
     "mst_attention_train_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mst_attention_train_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mst_attention_train_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "mst_attention_train_fwd16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mst_attention_train_bwd16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "mst_pos_embed_interp": (_i, [_vp, _i, _i, _i, _i, _d, _i, _vp, _vp]),
     "mst_mlp_fused": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "mst_block_fused_scratch_bytes": (_sz, []),
@@ -85,6 +87,13 @@ SIGNATURES = {
     "mst_im2col14": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_pos_embed_interp_bwd": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp]),
     "mst_patch_embed_dgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # 16-bit storage mode of the training step (csrc/k_train16.hip)
+    "mst_residual_layernorm16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
+    "mst_act_fwd16": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
+    "mst_act_bwd16": (_i, [_vp, _i, _vp, _i64, _i, _vp]),
+    "mst_colsum_b16": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp]),
+    "mst_colsum_b16_ordered": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
+    "mst_transpose16": (_i, [_vp, _i, _i64, _i64, _i, _vp, _i64, _i64, _vp]),
     "mst_im2col_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_cvt16": (_i, [_vp, _i64, _i64, _i, _f, _vp, _i, _i64, _i, _i64, _vp]),
     "mst_gemm16_splitk": (_i, [_vp, _i, _i64, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i64, _vp]),
@@ -322,25 +331,38 @@ def _f32_like(t: torch.Tensor, shape, dev, what: str, name: str):
         raise ValueError(f"{what}: {name} must be fp32 {tuple(shape)} on {dev} (got {t.dtype} {tuple(t.shape)} on {t.device})")
 
 
-def attention_train_fwd(qkv16: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int = 64) -> Tuple[torch.Tensor, torch.Tensor]:
+def attention_train_fwd(qkv16: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int = 64,
+                        out_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
     """mst_attention_train_fwd: (out fp32 [n_seq*N, heads*head_dim], lse fp32 [n_seq, heads, N], natural log) of the training step's
-    memory-efficient attention on 16-bit packed q | k | v rows (q pre-scaled)."""
+    memory-efficient attention on 16-bit packed q | k | v rows (q pre-scaled).  out_dtype = qkv16's own type: mst_attention_train_fwd16,
+    the same output rounded to that type by the kernel's epilogue."""
     _train_attn_args(qkv16, n_seq, N, heads, head_dim, "attention_train_fwd")
-    out = torch.empty((n_seq * N, heads * head_dim), dtype=torch.float32, device=qkv16.device)
+    if out_dtype not in (torch.float32, qkv16.dtype):
+        raise ValueError(f"attention_train_fwd: out_dtype must be fp32 or qkv16's {qkv16.dtype} (got {out_dtype})")
+    out = torch.empty((n_seq * N, heads * head_dim), dtype=out_dtype, device=qkv16.device)
     lse = torch.empty((n_seq, heads, N), dtype=torch.float32, device=qkv16.device)
-    _check(load().mst_attention_train_fwd(ptr(qkv16), dt_of(qkv16), n_seq, N, heads, head_dim, ptr(out), ptr(lse), stream_of(qkv16)),
-           "mst_attention_train_fwd")
+    lib = load()
+    fn, what = (lib.mst_attention_train_fwd, "mst_attention_train_fwd") if out_dtype == torch.float32 else \
+               (lib.mst_attention_train_fwd16, "mst_attention_train_fwd16")
+    _check(fn(ptr(qkv16), dt_of(qkv16), n_seq, N, heads, head_dim, ptr(out), ptr(lse), stream_of(qkv16)), what)
     return out, lse
 
 
 def attention_train_bwd(qkv16: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, n_seq: int, N: int, heads: int,
                         dq_scale: float = 1.0, head_dim: int = 64, dqkv: Optional[torch.Tensor] = None) -> torch.Tensor:
     """mst_attention_train_bwd: the gradient of the packed rows, dqkv fp32 [n_seq*N, 3*heads*head_dim] (dQ times dq_scale), from the
-    forward's qkv16 / out / lse and dout = d out.  Every element of dqkv is written; no [N, N] tensor is allocated."""
+    forward's qkv16 / out / lse and dout = d out.  Every element of dqkv is written; no [N, N] tensor is allocated.  `out` is fp32, or in
+    qkv16's own type as attention_train_fwd(out_dtype=...) wrote it (mst_attention_train_bwd16)."""
     what = "attention_train_bwd"
     _train_attn_args(qkv16, n_seq, N, heads, head_dim, what)
     dev = qkv16.device
-    _f32_like(out, (n_seq * N, heads * head_dim), dev, what, "out")
+    out16 = out.dtype == qkv16.dtype
+    if out16:
+        _dev(out, what)
+        if tuple(out.shape) != (n_seq * N, heads * head_dim) or out.device != dev:
+            raise ValueError(f"{what}: out must be [{n_seq * N}, {heads * head_dim}] on {dev} (got {tuple(out.shape)} on {out.device})")
+    else:
+        _f32_like(out, (n_seq * N, heads * head_dim), dev, what, "out")
     _f32_like(dout, (n_seq * N, heads * head_dim), dev, what, "dout")
     _f32_like(lse, (n_seq, heads, N), dev, what, "lse")
     if dqkv is None:
@@ -349,8 +371,9 @@ def attention_train_bwd(qkv16: torch.Tensor, out: torch.Tensor, dout: torch.Tens
     lib = load()
     nb = int(lib.mst_attention_train_bwd_workspace_bytes(n_seq, N, heads, head_dim))
     ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    _check(lib.mst_attention_train_bwd(ptr(qkv16), dt_of(qkv16), ptr(out), ptr(dout), ptr(lse), n_seq, N, heads, head_dim, dq_scale,
-                                       ptr(dqkv), ptr(ws), nb, stream_of(qkv16)), "mst_attention_train_bwd")
+    fn = lib.mst_attention_train_bwd16 if out16 else lib.mst_attention_train_bwd
+    _check(fn(ptr(qkv16), dt_of(qkv16), ptr(out), ptr(dout), ptr(lse), n_seq, N, heads, head_dim, dq_scale, ptr(dqkv), ptr(ws), nb,
+              stream_of(qkv16)), "mst_attention_train_bwd16" if out16 else "mst_attention_train_bwd")
     return dqkv
 
 
@@ -719,14 +742,83 @@ def act_bwd(h: torch.Tensor, dy: torch.Tensor, kind: int) -> torch.Tensor:
     return dy
 
 
+def _is16(t: torch.Tensor, what: str, name: str):
+    if t.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what}: {name} must be bf16 or fp16 (got {t.dtype})")
+    _dev(t, what)
+
+
+def residual_layernorm16(x_in: torch.Tensor, br: torch.Tensor, gamma: Optional[torch.Tensor], ln_w: Optional[torch.Tensor],
+                         ln_b: Optional[torch.Tensor], eps: float, x_out: Optional[torch.Tensor] = None,
+                         y: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """mst_residual_layernorm16: (x_out fp32 = x_in + gamma * br, y = LayerNorm(x_out; ln_w, ln_b) in br's 16-bit type) in one pass over
+    [rows, cols]; gamma None: no LayerScale; ln_w None: the residual alone, y is None.  x_out / y: caller-given outputs (every element
+    is written)."""
+    what = "residual_layernorm16"
+    _dev(x_in, what)
+    _is16(br, what, "br")
+    if x_in.dtype != torch.float32 or x_in.dim() != 2 or br.shape != x_in.shape or br.device != x_in.device:
+        raise ValueError(f"{what}: x_in must be fp32 [rows, cols] and br a 16-bit tensor of that shape on its device")
+    rows, cols = x_in.shape
+    if x_out is None:
+        x_out = torch.empty_like(x_in)
+    if ln_w is None:
+        y = None
+    elif y is None:
+        y = torch.empty_like(br)
+    for t, like, name in ((x_out, x_in, "x_out"), (y, br, "y")):
+        if t is not None and (t.dtype != like.dtype or t.shape != like.shape or t.device != like.device or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be contiguous {like.dtype} {tuple(like.shape)} on {like.device}")
+    _check(load().mst_residual_layernorm16(ptr(x_in), ptr(br), dt_of(br), ptr(gamma), ptr(x_out), ptr(ln_w), ptr(ln_b), ptr(y), rows, cols,
+                                           eps, stream_of(x_in)), "mst_residual_layernorm16")
+    return x_out, y
+
+
+def act_fwd16(h: torch.Tensor, kind: int) -> torch.Tensor:
+    """mst_act_fwd16: act(h) of a 16-bit tensor in its own type (fp32 arithmetic, one rounding)."""
+    _is16(h, "act_fwd16", "h")
+    y = torch.empty_like(h)
+    _check(load().mst_act_fwd16(ptr(h), ptr(y), dt_of(h), h.numel(), kind, stream_of(h)), "mst_act_fwd16")
+    return y
+
+
+def act_bwd16(h: torch.Tensor, dy: torch.Tensor, kind: int) -> torch.Tensor:
+    """mst_act_bwd16: dy (fp32, in place) *= act'(h) with the pre-activation h in 16 bits."""
+    _is16(h, "act_bwd16", "h")
+    _dev(dy, "act_bwd16")
+    if dy.dtype != torch.float32 or dy.numel() != h.numel() or dy.device != h.device:
+        raise ValueError("act_bwd16: dy must be fp32 with h's element count on its device")
+    _check(load().mst_act_bwd16(ptr(h), dt_of(h), ptr(dy), h.numel(), kind, stream_of(h)), "mst_act_bwd16")
+    return dy
+
+
+def transpose16(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
+    """mst_transpose16: the transposed image [cols, rows_pad] of a 16-bit matrix [rows, cols], zero columns for rows .. rows_pad."""
+    _is16(x, "transpose16", "x")
+    rows, cols = x.shape
+    rp = rows_pad or rows
+    out = torch.empty((cols, rp), dtype=x.dtype, device=x.device)
+    _check(load().mst_transpose16(ptr(x), dt_of(x), cols, rows, cols, ptr(out), rp, rp, stream_of(x)), "mst_transpose16")
+    return out
+
+
 def colsum(a: torch.Tensor, out: torch.Tensor, b: Optional[torch.Tensor] = None):
     """out[c] += sum_r a[r][c] * (b ? b[r][c] : 1); a (and b) 2-D with unit column stride (any row stride: a column block of a wider
-    matrix), out contiguous."""
+    matrix), out contiguous.  b may be bf16 / fp16 (the 16-bit storage mode's saved branch output)."""
     rows, cols = a.shape
     if a.stride(1) != 1 or (b is not None and (b.shape != a.shape or b.stride(1) != 1)) or not out.is_contiguous():
         raise ValueError("colsum: a / b need unit column strides and equal shapes, out must be contiguous")
     as_ = a.stride(0) if rows > 1 else cols
     bs = (b.stride(0) if rows > 1 else cols) if b is not None else cols
+    if b is not None and b.dtype != torch.float32:       # a factor saved in 16 bits (train_storage='16bit'): mst_colsum_b16 / _ordered
+        lib = load()
+        if deterministic():
+            ws = workspace(lib.mst_colsum_ordered_workspace_bytes(rows, cols), a.device)
+            _check(lib.mst_colsum_b16_ordered(ptr(a), as_, ptr(b), dt_of(b), bs, rows, cols, ptr(out), ptr(ws), 0 if ws is None else ws.numel(),
+                                              stream_of(a)), "mst_colsum_b16_ordered")
+        else:
+            _check(lib.mst_colsum_b16(ptr(a), as_, ptr(b), dt_of(b), bs, rows, cols, ptr(out), stream_of(a)), "mst_colsum_b16")
+        return out
     if deterministic():
         lib = load()
         ws = workspace(lib.mst_colsum_ordered_workspace_bytes(rows, cols), a.device)

@@ -16,6 +16,17 @@ reference's Trainer(precision='16-mixed'), scripts/main_train.py:110-123) runs t
 encoder blocks keep the 16-bit q | k | v (written so by the QKV GEMM), the fp32 output and the per-row log-sum-exp instead, and the
 backward recomputes the probabilities per tile (csrc/k_attn16_train.hip: 16-bit flash forward, FlashAttention-2 backward with a
 separate deterministic dQ pass); no [N, N] tensor exists.  The across-slice transformer's attention always stays on the stored path.
+``train_storage='16bit'`` (16-bit train_precision and 'flash' only, ValueError otherwise; re-checked at every call) keeps what the 12 encoder
+blocks save for the backward in that 16-bit type, as the reference's autocast does: per token and block x0, x1 (the fp32 residual stream,
+what mst_layernorm_bwd reads; x0 of block i + 1 is x2 of block i), xn1, xn2, a, br1, br2 [E] and qkv16 [3E], hpre, hact [4E] in 16 bits
+-- 40 E bytes plus the log-sum-exp instead of 66 E, and no 16-bit operand images beside them.  Each is written in 16 bits by its producer
+(the LayerNorm, the GEMM epilogue, the attention epilogue, the GELU) and is itself the operand of the forward product behind it, of that
+product's weight gradient and of the elementwise backward kernels (csrc/k_train16.hip: residual + LayerScale + LayerNorm in one pass, GELU
+16 -> 16 and its derivative, the LayerScale gradient with a 16-bit factor, the transposed operand image above 12,288 tokens; the flash
+kernels with a 16-bit output).  Gradients stay fp32 (they are ~1e-6: csrc/k_attn16_train.hip).
+Autocast: a model whose train_precision was given neither by keyword nor by environment takes the dtype of an enabled CUDA autocast region
+(fp16 / bf16) around the forward; the resolved precision and storage mode travel in the saved state, so the backward follows the forward's
+choice after the region has ended.
 RoPE slice transformers and register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn``
 inside a training forward.
 
@@ -52,8 +63,16 @@ _MP = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
 def _mp(model) -> Optional[torch.dtype]:
     """MFMA operand type of the per-slice encoder's nn.Linear products in the training step: None = exact fp32 MFMA (default),
     bf16 / fp16 = mixed precision -- what the reference's Trainer(precision='16-mixed') (scripts/main_train.py:110-123) does to
-    F.linear: 16-bit operands, fp32 accumulation, fp32 everywhere else (LayerNorm, softmax, GELU, residuals, gradients in memory)."""
-    return _MP[getattr(model, "train_precision", "fp32")]
+    F.linear: 16-bit operands, fp32 accumulation, fp32 everywhere else (LayerNorm, softmax, GELU, residuals, gradients in memory).
+    A model whose train_precision was given neither by keyword nor by MST_TRAIN_PRECISION (and still reads 'fp32') follows an enabled
+    CUDA autocast region of fp16 / bf16 around the forward.  Called in the forward only: the backward reads the answer from the saved
+    state, the region may have ended by then."""
+    tp = getattr(model, "train_precision", "fp32")
+    if tp == "fp32" and not getattr(model, "_train_precision_given", True) and torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        if dt in (torch.float16, torch.bfloat16):
+            return dt
+    return _MP[tp]
 
 
 def _flash(model, mp: Optional[torch.dtype]) -> bool:
@@ -66,6 +85,41 @@ def _flash(model, mp: Optional[torch.dtype]) -> bool:
     if ta == "flash" and mp is None:
         raise ValueError("train_attention='flash' needs train_precision 'bf16' or 'fp16' (the fp32 step keeps the stored probabilities)")
     return ta == "flash"
+
+
+def _storage16(model, mp: Optional[torch.dtype], flash: bool) -> bool:
+    """train_storage of the encoder blocks: 'fp32' (default) or '16bit' -- what a block keeps for its backward lives in the 16-bit type
+    (csrc/k_train16.hip); needs a 16-bit train_precision and train_attention='flash'.  Re-checked here like `_flash`."""
+    ts = getattr(model, "train_storage", "fp32")
+    if ts not in ("fp32", "16bit"):
+        raise ValueError(f"train_storage must be 'fp32' or '16bit' (got {ts!r})")
+    if ts == "16bit" and (mp is None or not flash):
+        raise ValueError("train_storage='16bit' needs train_precision 'bf16' or 'fp16' and train_attention='flash' (the saved tensors are "
+                         "the 16-bit operands of those kernels)")
+    return ts == "16bit"
+
+
+def _w16(lin, mp: torch.dtype) -> torch.Tensor:
+    return hip.cvt16(lin.weight.detach(), mp)
+
+
+def _block_fwd_16(blk, nxt, xt: torch.Tensor, xn: torch.Tensor, mp: torch.dtype, n: int, N: int, heads: int, E: int):
+    """One encoder block (block.py:89-114) of the 16-bit storage mode.  xt: the fp32 residual stream, xn = norm1(xt) in `mp` (written by the
+    LayerNorm that closed the previous block).  Every tensor kept is the one the next kernel reads: no fp32 copy, no second 16-bit image.
+    Returns (saved state, x2 fp32, norm(x2) of the next block `nxt` in `mp` -- None behind the last block)."""
+    g1 = blk.ls1.gamma.detach() if hasattr(blk, "ls1") else None
+    g2 = blk.ls2.gamma.detach() if hasattr(blk, "ls2") else None
+    s = {"x0": xt, "x16": {}, "xn1": xn}
+    s["qkv16"] = hip.gemm(xn, _w16(blk.attn.qkv, mp), blk.attn.qkv.bias.detach(), col_scale=0.125, scale_cols=E)
+    s["a"], s["lse"] = hip.attention_train_fwd(s["qkv16"], n, N, heads, out_dtype=mp)
+    s["br1"] = hip.gemm(s["a"], _w16(blk.attn.proj, mp), blk.attn.proj.bias.detach())
+    s["x1"], s["xn2"] = hip.residual_layernorm16(xt, s["br1"], g1, blk.norm2.weight.detach(), blk.norm2.bias.detach(), 1e-6)
+    s["hpre"] = hip.gemm(s["xn2"], _w16(blk.mlp.fc1, mp), blk.mlp.fc1.bias.detach())
+    s["hact"] = hip.act_fwd16(s["hpre"], 0)
+    s["br2"] = hip.gemm(s["hact"], _w16(blk.mlp.fc2, mp), blk.mlp.fc2.bias.detach())
+    x2, xn_next = hip.residual_layernorm16(s["x1"], s["br2"], g2, nxt.norm1.weight.detach() if nxt is not None else None,
+                                           nxt.norm1.bias.detach() if nxt is not None else None, 1e-6)
+    return s, x2, xn_next
 
 
 def _lin_fwd(x: torch.Tensor, lin, mp: Optional[torch.dtype] = None, keep: Optional[dict] = None,
@@ -103,6 +157,8 @@ class _Grads:
         dev = dY.device
         if self.mp is not None and N % 128 == 0 and K % 128 == 0 and M >= 64:
             return self._lin_bwd_16(dY, X, lin, need_dx, X16)
+        if X.dtype != torch.float32:                     # an activation saved in 16 bits behind a product too small for the 16-bit kernels
+            X = hip.cvt32(X)
         if self.need(lin.weight):
             self._dw(dY, X, lin)
         if self.need(getattr(lin, "bias", None)):
@@ -143,7 +199,10 @@ class _Grads:
             # d weight = dY^T . X is the weight gradient of a 1 x 1 "convolution" over M one-pixel images: mst_conv_wgrad16 reads both operands
             # row-major (token-major) and transposes the fragments in the LDS read -- no transposed operand images, token-split partial
             # products (1 x 16 x 224^2: 14.4 -> 10.9 ms per step against the form below)
-            x16 = X16 if (X16 is not None and X16.dtype == mp and X16.shape == X.shape) else hip.cvt16(X, mp)   # the forward's image, if it was kept
+            if X.dtype == mp:
+                x16 = X                                  # train_storage='16bit': the saved activation IS the operand image
+            else:
+                x16 = X16 if (X16 is not None and X16.dtype == mp and X16.shape == X.shape) else hip.cvt16(X, mp)   # the forward's image, if it was kept
             self.put(lin.weight, hip.conv_wgrad(dY16, x16.view(M, 1, 1, K), 1, 1, 0))
         elif want_dw:
             # many tokens: TRANSPOSED operand images (both operands contiguous along the token index) through the 128 x 128 x 64 GEMM with
@@ -151,7 +210,8 @@ class _Grads:
             tiles = (N // 128) * (K // 128)
             sp = max(1, min(64, 512 // tiles))
             kc = -(-M // (sp * 64)) * 64                                 # token rows per split, a multiple of the K-step
-            part = hip.gemm16_splitk(hip.cvt16(dY, mp, transpose=True, rows_pad=kc * sp), hip.cvt16(X, mp, transpose=True, rows_pad=kc * sp), sp)
+            xT = hip.transpose16(X, rows_pad=kc * sp) if X.dtype == mp else hip.cvt16(X, mp, transpose=True, rows_pad=kc * sp)
+            part = hip.gemm16_splitk(hip.cvt16(dY, mp, transpose=True, rows_pad=kc * sp), xT, sp)
             self.put(lin.weight, hip.colsum(part.view(sp, N * K), torch.zeros(N * K, dtype=torch.float32, device=dev)).view(N, K))
         if self.need(getattr(lin, "bias", None)):
             self.put(lin.bias, hip.colsum(dY, torch.zeros(N, dtype=torch.float32, device=dev)))
@@ -328,7 +388,16 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     blocks = []
     mp = _mp(model)
     flash = _flash(model, mp)
-    for blk in enc.block_list():
+    st16 = _storage16(model, mp, flash)
+    sv["mp"], sv["storage16"] = mp, st16                  # the backward reads the resolved modes from here (an autocast region may have ended)
+    blist = list(enc.block_list())
+    if st16:
+        xn = hip.layernorm(xt, blist[0].norm1.weight.detach(), blist[0].norm1.bias.detach(), 1e-6, out_dtype=mp)
+        for i, blk in enumerate(blist):
+            s, xt, xn = _block_fwd_16(blk, blist[i + 1] if i + 1 < len(blist) else None, xt, xn, mp, n, N, heads, E)
+            blocks.append(s)
+        blist = []
+    for blk in blist:
         s = {"x0": xt, "x16": {}}
         k16 = s["x16"] if mp is not None else None
         s["xn1"] = hip.layernorm(xt, blk.norm1.weight.detach(), blk.norm1.bias.detach(), 1e-6)
@@ -412,7 +481,8 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
     if not need_src and not any(p.requires_grad for p in enc.parameters()):
         return G.by_param, None                                                  # frozen encoder (dino.py:65-67)
     # ---- encoder
-    G.mp = _mp(model)                                    # the blocks' nn.Linear products on 16-bit operands, if asked for
+    G.mp = sv["mp"]                                      # the blocks' nn.Linear products on 16-bit operands, as the forward resolved them
+    act_bwd = hip.act_bwd16 if sv["storage16"] else hip.act_bwd
     E, heads = enc.embed_dim, enc.num_heads
     n = B * D
     gh, gw = H // PATCH, W // PATCH
@@ -432,7 +502,7 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
             hip.axpby_cols(dx, dbr, g=blk.ls2.gamma.detach(), beta=0.0)
         x16 = s.get("x16", {})
         dh = G.lin_bwd(dbr, s["hact"], blk.mlp.fc2, X16=x16.get(id(blk.mlp.fc2)))
-        hip.act_bwd(s["hpre"], dh, 0)
+        act_bwd(s["hpre"], dh, 0)
         dxn2 = G.lin_bwd(dh, s["xn2"], blk.mlp.fc1, X16=x16.get(id(blk.mlp.fc1)))
         dx1 = torch.empty_like(dx)
         G.ln_bwd(s["x1"], E, blk.norm2, dxn2, E, dx, E, dx1, E, M, E, 1e-6)

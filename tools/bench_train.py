@@ -3,7 +3,9 @@
 HIP kernels + AdamW) of both model families, and the ViT-B forward on the unfused path.  One JSON line per case.
 --deterministic: torch.use_deterministic_algorithms(True) for every case (the fixed-order reductions; DESIGN.md "Determinism");
 --no-fill on top: torch.utils.deterministic.fill_uninitialized_memory = False, to tell torch's NaN fill from the kernels' cost.
---input-grad: the source-gradient timings (input_grad_cases)."""
+--input-grad: the source-gradient timings (input_grad_cases).
+--train-storage 16bit (beside --train-attention flash and a 16-bit precision): the encoder blocks' saved activations in 16 bits.  A comma
+list (fp32,16bit,fp32) times those modes one after the other in this process: the repeated mode gives the spread the other is read against."""
 import json
 import sys
 import time
@@ -215,17 +217,20 @@ def main():
         return
     # --train-attention flash: the encoder blocks' attention without stored probabilities (16-bit precisions only; fp32 cases keep 'stored')
     attn = sys.argv[sys.argv.index("--train-attention") + 1] if "--train-attention" in sys.argv else "stored"
-    dino_shapes = ((1, 1, 16, 224, 224),) if "--only-dino-c1" in sys.argv else ((2, 1, 32, 224, 224),) if "--only-dino-2x32" in sys.argv else \
-        ((1, 1, 64, 518, 518),) if "--only-dino-518" in sys.argv else ((1, 1, 16, 224, 224), (2, 1, 32, 224, 224), (1, 1, 64, 518, 518))
+    # --train-storage 16bit | fp32,16bit,fp32: the blocks' saved activations (16-bit precisions with flash attention only; others keep 'fp32')
+    storages = sys.argv[sys.argv.index("--train-storage") + 1].split(",") if "--train-storage" in sys.argv else ["fp32"]
+    all_shapes = (("--only-dino-c1", (1, 1, 16, 224, 224)), ("--only-dino-2x32", (2, 1, 32, 224, 224)), ("--only-dino-518", (1, 1, 64, 518, 518)))
+    dino_shapes = tuple(sh for flag, sh in all_shapes if flag in sys.argv) or tuple(sh for _, sh in all_shapes)    # several --only-dino-* add up
     for shape in (() if "--only-resnet" in sys.argv else dino_shapes):
         for prec in (("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("fp32",)):
             a = attn if prec != "fp32" else "stored"
-            m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, train_precision=prec, train_attention=a)
-            m.load_state_dict(synth.synth_state_dict("s", 0))
-            train_case(f"DinoV2ClassifierSlice training step ({prec} linear products, {a} attention, HIP backward)", m, shape,
-                       n=3 if shape[2] >= 64 else 5)
-            del m
-            torch.cuda.empty_cache()
+            for st in (storages if a == "flash" else ["fp32"]):
+                m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, train_precision=prec, train_attention=a, train_storage=st)
+                m.load_state_dict(synth.synth_state_dict("s", 0))
+                train_case(f"DinoV2ClassifierSlice training step ({prec} linear products, {a} attention, {st} storage, HIP backward)", m, shape,
+                           n=3 if shape[2] >= 64 else 5)
+                del m
+                torch.cuda.empty_cache()
     if "--only-dino-c1" in sys.argv or "--only-dino-2x32" in sys.argv or "--only-dino-518" in sys.argv:
         return
     for shape in (() if "--c3-only" in sys.argv else ((2, 1, 32, 224, 224),)):
