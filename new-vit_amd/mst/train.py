@@ -8,7 +8,7 @@ backward produces the gradient of every parameter with the kernels of csrc/k_tra
 [B, out_ch] logits (host code).  torch is used for memory only (allocation, views, concatenation / copies of whole tensors).
 
 Default: everything in exact fp32 (fp32 MFMA), whatever ``compute_dtype`` the inference path uses -- the mode the gradient parity bar
-(1e-3 against autograd of the CPU oracle on every parameter, tests/test_train_gpu.py) is on.  ``train_precision='fp16' | 'bf16'`` (the
+(1e-4 against float64 autograd of the CPU oracle on every parameter, tests/test_train_gpu.py, tests/test_train_parity_gpu.py) is on.  ``train_precision='fp16' | 'bf16'`` (the
 reference's Trainer(precision='16-mixed'), scripts/main_train.py:110-123) runs the blocks' nn.Linear products -- forward, d input, d weight
 -- on 16-bit MFMA operands with fp32 accumulation; every other op and everything stored stays fp32.  By default
 (``train_attention='stored'``) the attention probabilities of every block are kept ([n, heads, N, N] fp32: 2.9 GB per block at

@@ -1,7 +1,9 @@
 """the training step on the HIP path.  The gradient of EVERY parameter, produced by the kernels of
 csrc/k_train.hip behind one torch.autograd.Function, against torch.autograd through the CPU oracle (which the reference
 fixtures pin) on the same seeded weights and inputs: what the reference's `_step` (base_model.py:148-181) + autograd compute.
-Bar: max |dP_hip - dP_ref| <= 1e-3 * max |dP_ref| per parameter (fp32 path; fp32 atomics make the last bits run-dependent)."""
+The reference runs in float64.  Bar: max |dP_hip - dP_ref| <= 1e-4 * max |dP_ref| per parameter (fp32 path; fp32 atomics make the last
+bits run-dependent; where the bar comes from: tests/train_parity.py, which covers the larger shapes).  MEASURED holds what each case
+measured on the MI355X."""
 import numpy as np
 import pytest
 import torch
@@ -13,14 +15,24 @@ from test_model_gpu import CASES, build
 pytestmark = pytest.mark.gpu
 
 
-def _oracle_grads(name, kw, seed, src, mask, target, without_linear=False):
+RTOL = 1e-4
+# worst parameter's max |dP_hip - dP_ref| / max |dP_ref| against the float64 oracle, measured on the MI355X
+MEASURED = {
+    "c1_1x16x224": 8.0e-6, "b2_mask": 1.2e-5, "registers": 1.3e-5,
+    "bottleneck_pos": 9.2e-6, "average": 5.8e-6, "linear32": 8.4e-6, "rope": 1.1e-5,
+    "features": 1.1e-5, "frozen encoder": 8.2e-6,
+}   # all <= 3e-5: every case is held to RTOL
+
+
+def _oracle_grads(name, kw, seed, src, mask, target, without_linear=False, dtype=torch.float64):
     from oracle import mst_oracle as O
     sd = synth.synth_state_dict(kw.get("model_size", "s"), seed, use_bottleneck=kw.get("use_bottleneck", False),
                                 use_slice_pos_emb=kw.get("use_slice_pos_emb", False),
                                 slice_fusion=kw.get("slice_fusion", "transformer"), rotary=kw.get("rotary_positional_encoding"))
     # (RoPE's frequencies are a buffer-like Parameter with requires_grad = False in the reference: rotary_embedding_torch.py learned_freq = False)
-    sd = {k: v.clone().requires_grad_(v.is_floating_point() and not k.endswith("rotary_positional_encoding.freqs")) for k, v in sd.items()}
-    out = O.forward(sd, src, model_size=kw.get("model_size", "s"), slice_fusion_type=kw.get("slice_fusion", "transformer"),
+    sd = {k: (v.to(dtype).requires_grad_(not k.endswith("rotary_positional_encoding.freqs")) if v.is_floating_point() else v.clone())
+          for k, v in sd.items()}
+    out = O.forward(sd, src.to(dtype), model_size=kw.get("model_size", "s"), slice_fusion_type=kw.get("slice_fusion", "transformer"),
                     src_key_padding_mask=mask, without_linear=without_linear, rotary=kw.get("rotary_positional_encoding"))
     y = out["features"] if without_linear else out["logits"]
     loss = y.square().sum() if without_linear else torch.nn.functional.cross_entropy(y, target)
@@ -28,7 +40,7 @@ def _oracle_grads(name, kw, seed, src, mask, target, without_linear=False):
     return float(loss.detach()), {k: v.grad for k, v in sd.items()}, y.detach()
 
 
-def _check_all(model, ref_grads, rtol=1e-3):
+def _check_all(model, ref_grads, rtol=RTOL, label=None):
     worst = {}
     for k, p in model.named_parameters():
         r = ref_grads.get(k)
@@ -39,9 +51,11 @@ def _check_all(model, ref_grads, rtol=1e-3):
         g = p.grad.detach().cpu()
         assert g.shape == r.shape, k
         scale = float(r.abs().max())
-        err = float((g - r).abs().max())
+        err = float((g.double() - r.double()).abs().max())
         worst[k] = err / max(scale, 1e-30)
         assert err <= rtol * scale + 1e-9, (k, err, scale)
+    if label:
+        print(label, "worst relative gradient error:", max(worst.values()), max(worst, key=worst.get))
     return worst
 
 
@@ -62,8 +76,7 @@ def test_every_parameter_gradient_matches_oracle_autograd(name):
     assert loss.requires_grad
     assert abs(float(loss) - loss_ref) < 1e-4
     loss.backward()
-    worst = _check_all(model, ref)
-    print(name, "worst relative gradient error:", max(worst.values()), max(worst, key=worst.get))
+    _check_all(model, ref, label=name)
     # the forward of the training path is the reference forward too
     with torch.enable_grad():
         logits = model(src, src_key_padding_mask=mask)
@@ -85,15 +98,14 @@ def test_register_token_encoder_gradients_at_the_stored_grid():
     model = model.cuda().train()
     src = synth.synth_volume((2, 1, 3, 56, 56), seed + 100)
     target = torch.tensor([1, 0])
-    sdg = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
-    ref_logits = O.forward(sdg, src)["logits"]
+    sdg = {k: v.double().requires_grad_() for k, v in sd.items()}
+    ref_logits = O.forward(sdg, src.double())["logits"]
     torch.nn.functional.cross_entropy(ref_logits, target).backward()
     logits = model(src)
     assert float((logits.detach().cpu() - ref_logits.detach()).abs().max()) < 1e-4
     torch.nn.functional.cross_entropy(logits, target.cuda()).backward()
-    worst = _check_all(model, {k: v.grad for k, v in sdg.items()})
+    worst = _check_all(model, {k: v.grad for k, v in sdg.items()}, label="registers")
     assert "encoder.register_tokens" in worst and float(model.encoder.register_tokens.grad.abs().max()) > 0
-    print("registers: worst relative gradient error", max(worst.values()), max(worst, key=worst.get))
     with pytest.raises(NotImplementedError, match="stored position grid"):
         model(synth.synth_volume((1, 1, 2, 70, 70), 1))
 
@@ -109,7 +121,7 @@ def test_fusion_variants_gradients(name):
     _, ref, _ = _oracle_grads(name, kw, int(g["seed"]), src, None, target)
     loss = torch.nn.functional.cross_entropy(model(src), target.cuda())
     loss.backward()
-    _check_all(model, ref)
+    _check_all(model, ref, label=name)
 
 
 def test_rope_rotation_is_orthogonal_and_liere_training_raises():
@@ -186,7 +198,7 @@ def test_operand_images_and_split_k_product(dt):
 def test_mixed_precision_step_gradients_against_the_fp32_step(prec, bar, gbar):
     """train_precision = fp16 / bf16 (the reference's Trainer(precision='16-mixed'), scripts/main_train.py:110-123): the blocks' nn.Linear
     products on 16-bit MFMA operands, everything else as in the fp32 step.  Every parameter gradient against the fp32 step (which the
-    oracle pins at 1e-3), relative L2 norm per parameter <= bar and over all parameters together <= gbar: 2x the worst measured at this
+    float64 oracle pins at 1e-4), relative L2 norm per parameter <= bar and over all parameters together <= gbar: 2x the worst measured at this
     shape (fp16 4.3e-3 / 3.6e-3, bf16 6.3e-2 / 3.5e-2; the max-norm of single parameters is not used: under bf16 a ReLU of the across-slice
     layer's feed-forward flips on the perturbed embeddings and moves one entry of linear1's gradient by 27 %)."""
     from mst.models import DinoV2ClassifierSlice
@@ -225,7 +237,7 @@ def test_features_path_frozen_encoder_and_an_optimizer_step():
     for k, p in model.named_parameters():
         if k.startswith("linear."):
             assert p.grad is None
-    _check_all(model, {**ref, "linear.weight": None, "linear.bias": None})
+    _check_all(model, {**ref, "linear.weight": None, "linear.bias": None}, label="features")
     # freeze=True (dino.py:65-67): encoder parameters get no gradient, the rest is unchanged
     from mst.models import DinoV2ClassifierSlice
     fm = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, compute_dtype="fp32", freeze=True)
@@ -234,12 +246,15 @@ def test_features_path_frozen_encoder_and_an_optimizer_step():
     target = torch.tensor([0, 1])
     _, ref2, _ = _oracle_grads("b2_mask", {}, int(g["seed"]), src, mask, target)
     torch.nn.functional.cross_entropy(fm(src, src_key_padding_mask=mask), target.cuda()).backward()
+    worst = {}
     for k, p in fm.named_parameters():
         if k.startswith("encoder."):
             assert p.grad is None, k
         else:
             r = ref2[k]
-            assert float((p.grad.cpu() - r).abs().max()) <= 1e-3 * float(r.abs().max()) + 1e-9, k
+            worst[k] = float((p.grad.cpu().double() - r).abs().max()) / float(r.abs().max())
+            assert worst[k] * float(r.abs().max()) <= RTOL * float(r.abs().max()) + 1e-9, (k, worst[k])
+    print("frozen encoder worst relative gradient error:", max(worst.values()), max(worst, key=worst.get))
     # AdamW (dino.py:41) on the HIP gradients lowers the loss
     from oracle import mst_oracle as O
     model = build({}, int(g["seed"]), "fp32")
