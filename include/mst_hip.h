@@ -381,6 +381,39 @@ int mst_colsum_b16_ordered(const float* a, int64_t a_stride, const void* b, int 
 int mst_transpose16(const void* x, int dtype, int64_t ldx, int64_t rows, int cols, void* out, int64_t ldo, int64_t rows_pad,
                     mst_stream_t stream);
 
+/* 16-bit storage mode of the ResNet training step (mst/train_resnet.py, train_storage='16bit'; csrc/k_bn16.hip): the convolution output z
+ * and the unit's output y of a convolution + BatchNorm2d (+ residual, ReLU) unit live in T = dtype (MST_BF16 / MST_F16), as the reference's
+ * autocast keeps them; statistics, gradients and every sum are fp32 and all arithmetic is fp32 on the upcast values.  Activations are
+ * [rows, C] NHWC.  C must be a multiple of 8 and EVERY pointer 16-byte aligned; anything else, another dtype or a short workspace returns
+ * MST_EINVAL.  The reductions follow the ORDER CONTRACT below whatever the determinism flag says: a workgroup sums a block of rows for 64
+ * columns, stores its partial into the workspace with plain stores, and the partials are added in ascending block order -- no
+ * floating-point atomic, bit-identical results run to run for fixed (rows, C).  The library never allocates: workspace of at least
+ * ..._workspace_bytes(shape) bytes.  Conversions to T round the fp32 result to nearest even.
+ * mst_batchnorm_train16: mst_batchnorm_train on z in T: the column mean, then the centred sum of squares (two passes), mean / rstd [C] kept
+ *   for the backward, running_mean / running_var (nullable) updated as there;  y = T(relu?(gamma (z - mean) rstd + beta + float(residual)))
+ *   (residual T [rows, C] or NULL).
+ * mst_batchnorm_bwd16: the ReLU mask, both column sums, the input gradient and its rounding in one call.  m = float(y) > 0 (y NULL: no ReLU,
+ *   m = 1);  dbeta = sum_r m dy,  dgamma = sum_r m dy xhat  (OVERWRITTEN, not accumulated);
+ *   dz = T(gamma rstd (m dy - dbeta / rows - xhat dgamma / rows)), unscaled.  mask_dy_in_place != 0: dy <- m dy as well (for the shortcut
+ *   branch that shares this gradient); pass 0 where nothing reads it.
+ * mst_maxpool_bwd_nhwc16: mst_maxpool_bwd_nhwc_gather (dx +=, zero it first; fp32 dy / dx) with the pool INPUT x in T: the same
+ *   first-maximum rule (ties included) and the same one-byte-per-window workspace, so the result has the bits of the fp32 form on the
+ *   upcast x.
+ * mst_avgpool_nhwc16: mst_avgpool_nhwc on x [n, HW, C] in T -> y [n, C] fp32, positions summed in that kernel's order (the same bits on
+ *   the upcast x). */
+size_t mst_batchnorm_train16_workspace_bytes(int64_t rows, int C);
+int mst_batchnorm_train16(const void* z, int dtype, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
+                          const void* residual, int relu, void* y, float* mean, float* rstd, float* running_mean, float* running_var,
+                          void* workspace, size_t workspace_bytes, mst_stream_t stream);
+size_t mst_batchnorm_bwd16_workspace_bytes(int64_t rows, int C);
+int mst_batchnorm_bwd16(const void* z, const void* y, int dtype, const float* mean, const float* rstd, const float* gamma, float* dy,
+                        int mask_dy_in_place, int64_t rows, int C, float* dgamma, float* dbeta, void* dz, void* workspace, size_t workspace_bytes,
+                        mst_stream_t stream);
+size_t mst_maxpool_bwd_nhwc16_workspace_bytes(int n, int H, int W, int C);
+int mst_maxpool_bwd_nhwc16(const void* x, int dtype, const float* dy, int n, int H, int W, int C, float* dx, void* workspace, size_t workspace_bytes,
+                           mst_stream_t stream);
+int mst_avgpool_nhwc16(const void* x, int dtype, int n, int HW, int C, float* y, mst_stream_t stream);
+
 /* Fixed-order (deterministic) forms of every floating-point reduction of the training steps and of mst_znorm: what the Python layer calls
  * while torch.are_deterministic_algorithms_enabled().  ORDER CONTRACT: for fixed shape arguments (rows, cols, n, H, W, C, M, E, gh, gw,
  * kernel geometry) the summation order is fixed -- it does not depend on timing, occupancy, which XCD runs a workgroup, strides or pointer

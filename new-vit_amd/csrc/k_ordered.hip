@@ -346,14 +346,21 @@ int launch_maxpool_bwd_gather(const float* x, const float* dy, int n, int H, int
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const size_t need = maxpool_bwd_gather_workspace_bytes(n, H, W, C);
     MST_CHECK_ARG(ws && ws_bytes >= need, "maxpool_bwd_gather: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    const int64_t windows = (int64_t)n * Ho * Wo * C, total = (int64_t)n * H * W * C;
+    const int64_t windows = (int64_t)n * Ho * Wo * C;
     maxpool_arg_kernel<<<dim3(ogrid(windows)), dim3(256), 0, s>>>(x, H, W, C, Ho, Wo, windows, (uint8_t*)ws);
     int rc = mst_check_launch("maxpool_arg");
     if (rc) return rc;
+    return launch_maxpool_bwd_from_args((const uint8_t*)ws, dy, n, H, W, C, dx, s);
+}
+
+// pass 2 alone, on first-maximum codes some pass 1 stored (maxpool_arg_kernel here, its 16-bit-input twin in k_bn16.hip)
+int launch_maxpool_bwd_from_args(const uint8_t* ws, const float* dy, int n, int H, int W, int C, float* dx, hipStream_t s) {
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int64_t total = (int64_t)n * H * W * C;
     const bool v4 = C % 4 == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (reinterpret_cast<uintptr_t>(dy) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(ws) & 3) == 0;            // the same sums in the same order either way
-    if (v4) maxpool_bwd_gather_kernel<true><<<dim3(ogrid(total / 4)), dim3(256), 0, s>>>((const uint8_t*)ws, dy, H, W, C, Ho, Wo, total, dx);
-    else maxpool_bwd_gather_kernel<false><<<dim3(ogrid(total)), dim3(256), 0, s>>>((const uint8_t*)ws, dy, H, W, C, Ho, Wo, total, dx);
+    if (v4) maxpool_bwd_gather_kernel<true><<<dim3(ogrid(total / 4)), dim3(256), 0, s>>>(ws, dy, H, W, C, Ho, Wo, total, dx);
+    else maxpool_bwd_gather_kernel<false><<<dim3(ogrid(total)), dim3(256), 0, s>>>(ws, dy, H, W, C, Ho, Wo, total, dx);
     return mst_check_launch("maxpool_bwd_gather");
 }
 

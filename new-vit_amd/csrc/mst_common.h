@@ -316,6 +316,7 @@ int launch_col2im_gather(const float* dcol, int n, int H, int W, int C, int kh, 
                          hipStream_t s);
 size_t maxpool_bwd_gather_workspace_bytes(int n, int H, int W, int C);
 int launch_maxpool_bwd_gather(const float* x, const float* dy, int n, int H, int W, int C, float* dx, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_maxpool_bwd_from_args(const uint8_t* arg, const float* dy, int n, int H, int W, int C, float* dx, hipStream_t s);
 size_t pos_interp_bwd_ordered_workspace_bytes(int M, int E, int gh, int gw);
 int launch_pos_interp_bwd_ordered(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, void* ws, size_t ws_bytes,
                                   hipStream_t s);

@@ -94,6 +94,14 @@ SIGNATURES = {
     "mst_colsum_b16": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp]),
     "mst_colsum_b16_ordered": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
     "mst_transpose16": (_i, [_vp, _i, _i64, _i64, _i, _vp, _i64, _i64, _vp]),
+    # 16-bit storage mode of the ResNet training step (csrc/k_bn16.hip)
+    "mst_batchnorm_train16_workspace_bytes": (_sz, [_i64, _i]),
+    "mst_batchnorm_train16": (_i, [_vp, _i, _i64, _i, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mst_batchnorm_bwd16_workspace_bytes": (_sz, [_i64, _i]),
+    "mst_batchnorm_bwd16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mst_maxpool_bwd_nhwc16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mst_maxpool_bwd_nhwc16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mst_avgpool_nhwc16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_im2col_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_cvt16": (_i, [_vp, _i64, _i64, _i, _f, _vp, _i, _i64, _i, _i64, _vp]),
     "mst_gemm16_splitk": (_i, [_vp, _i, _i64, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i64, _vp]),
@@ -1000,6 +1008,9 @@ def avgpool_nhwc(x: torch.Tensor) -> torch.Tensor:
     _dev(x, "avgpool_nhwc")
     n, H, W, Cc = x.shape
     y = torch.empty((n, Cc), dtype=torch.float32, device=x.device)
+    if x.dtype != torch.float32:                         # train_storage='16bit' of the ResNet step: the last unit's output in bf16 / fp16
+        _check(load().mst_avgpool_nhwc16(ptr(x), dt_of(x), n, H * W, Cc, ptr(y), stream_of(x)), "mst_avgpool_nhwc16")
+        return y
     _check(load().mst_avgpool_nhwc(ptr(x), n, H * W, Cc, ptr(y), stream_of(x)), "mst_avgpool_nhwc")
     return y
 
@@ -1043,6 +1054,45 @@ def batchnorm_bwd(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma
     return dz, dg, db
 
 
+def batchnorm_train16(z: torch.Tensor, bn, residual: Optional[torch.Tensor], relu: bool, momentum: float = 0.1):
+    """mst_batchnorm_train16: batchnorm_train on z [rows, C] in bf16 / fp16 (+ residual of the same type, ReLU): returns (y in z's type, mean,
+    rstd); updates bn.running_* in place.  Fixed summation order in both determinism modes."""
+    _is16(z, "batchnorm_train16", "z")
+    if residual is not None and (residual.dtype != z.dtype or residual.numel() != z.numel()):
+        raise ValueError(f"batchnorm_train16: residual {tuple(residual.shape)} {residual.dtype} does not match z {tuple(z.shape)} {z.dtype}")
+    rows, Cc = z.shape
+    dev = z.device
+    y = torch.empty_like(z)
+    mean = torch.empty(Cc, dtype=torch.float32, device=dev)
+    rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
+    lib = load()
+    ws = workspace(lib.mst_batchnorm_train16_workspace_bytes(rows, Cc), dev)
+    _check(lib.mst_batchnorm_train16(ptr(z), dt_of(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum, ptr(residual),
+                                     1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var), ptr(ws),
+                                     0 if ws is None else ws.numel(), stream_of(z)), "mst_batchnorm_train16")
+    return y, mean, rstd
+
+
+def batchnorm_bwd16(z: torch.Tensor, y: Optional[torch.Tensor], mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor,
+                    mask_dy_in_place: bool):
+    """mst_batchnorm_bwd16 on the saved z (and y: the ReLU mask, None without ReLU) in bf16 / fp16 and the fp32 dy: returns
+    (dz in z's type, dgamma, dbeta); mask_dy_in_place also leaves dy * (y > 0) in dy."""
+    _is16(z, "batchnorm_bwd16", "z")
+    _dev(dy, "batchnorm_bwd16")
+    rows, Cc = z.shape
+    if dy.dtype != torch.float32 or dy.numel() != z.numel() or (y is not None and (y.dtype != z.dtype or y.numel() != z.numel())):
+        raise ValueError(f"batchnorm_bwd16: dy must be fp32 and y {z.dtype}, both of z's shape {tuple(z.shape)}")
+    dev = z.device
+    dg = torch.empty(Cc, dtype=torch.float32, device=dev)
+    db = torch.empty(Cc, dtype=torch.float32, device=dev)
+    dz = torch.empty_like(z)
+    lib = load()
+    ws = workspace(lib.mst_batchnorm_bwd16_workspace_bytes(rows, Cc), dev)
+    _check(lib.mst_batchnorm_bwd16(ptr(z), ptr(y), dt_of(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), 1 if mask_dy_in_place else 0, rows, Cc,
+                                   ptr(dg), ptr(db), ptr(dz), ptr(ws), 0 if ws is None else ws.numel(), stream_of(z)), "mst_batchnorm_bwd16")
+    return dz, dg, db
+
+
 def col2im_nhwc(dcol: torch.Tensor, dx: torch.Tensor, kh: int, kw: int, stride: int, pad: int):
     """dx [n,H,W,C] += adjoint of im2col_nhwc applied to dcol [n*Ho*Wo, Kpad]."""
     n, H, W, Cc = dx.shape
@@ -1056,6 +1106,13 @@ def col2im_nhwc(dcol: torch.Tensor, dx: torch.Tensor, kh: int, kw: int, stride: 
 
 def maxpool_bwd_nhwc(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     n, H, W, Cc = x.shape
+    if x.dtype != torch.float32:                         # the pool input saved in bf16 / fp16: the gather form in both determinism modes
+        dx = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+        lib = load()
+        ws = workspace(lib.mst_maxpool_bwd_nhwc16_workspace_bytes(n, H, W, Cc), x.device)
+        _check(lib.mst_maxpool_bwd_nhwc16(ptr(x), dt_of(x), ptr(dy), n, H, W, Cc, ptr(dx), ptr(ws), 0 if ws is None else ws.numel(), stream_of(x)),
+               "mst_maxpool_bwd_nhwc16")
+        return dx
     dx = torch.zeros_like(x)
     if deterministic():
         lib = load()

@@ -14,12 +14,24 @@ forward runs the model op by op through the C ABI and whose backward produces ev
                    stored tensors fp32
   BatchNorm2d      batch statistics + running-stat update (mst_batchnorm_train), residual add and ReLU in the same pass
      backward      mst_batchnorm_bwd (ReLU mask first: mst_act_bwd on the saved output)
+     16-bit stored train_storage = '16bit' (opt-in, needs a 16-bit train_precision; csrc/k_bn16.hip): z and y of every unit live in that type,
+                   as the reference's autocast keeps them.  A unit takes its input in T, writes z in T (mst_conv_gemm16) and y in T
+                   (mst_batchnorm_train16); that y IS the next unit's convolution operand, the operand of its weight gradient and the
+                   residual of the unit that closes the block, so the record holds z, y (ReLU units), the [C] statistics and a reference
+                   to the caller's input -- no fp32 activation, no second 16-bit copy.  Backward: ONE mst_batchnorm_bwd16 per unit (ReLU
+                   mask, both sums, dz rounded to T, the masked dy for the shortcut).  The gradient stream (dy, dx, shortcut sums), the
+                   weight-gradient partials, the slice transformer and the head stay fp32.  Its BatchNorm sums are fixed-order always.
   max / avg pool   mst_maxpool_bwd_nhwc / mst_avgpool_bwd_nhwc
   slice fusion     mst.train.fusion_fwd / fusion_bwd with 16 heads over 512-wide tokens
 
 BatchNorm in train mode normalises over ALL (B D) images of the step, so the step is not chunked: activations of the whole batch stay
 resident (fp32 NHWC; about 60 MB per 224^2 image for resnet34 -- sized for 288 GB of HBM; the mixed mode keeps a 16-bit image of every
 convolution input beside it).  Checked against torch.autograd of oracle/resnet_oracle.py on every parameter (tests/test_resnet_gpu.py).
+
+Autocast: a model whose train_precision was given neither by keyword nor by MST_TRAIN_PRECISION follows an enabled CUDA autocast region of
+fp16 / bf16 around the forward (mst.train._mp, the rule of DinoV2ClassifierSlice); an explicit value, 'fp32' included, is never overridden
+and train_storage is never inferred.  The resolved type and the storage mode travel in the saved state: backward() may run after the
+region has ended.
 
 Determinism: under ``torch.use_deterministic_algorithms(True)`` (read at every call) the BatchNorm statistics and their gradients
 (mst_batchnorm_train_ordered / mst_batchnorm_bwd_ordered), the weight-gradient partial sums (mst_colsum_ordered), col2im and the max-pool
@@ -36,7 +48,7 @@ import torch.nn as nn
 
 from . import hip
 from .models.resnet import _conv
-from .train import _Grads, fusion_bwd, fusion_fwd
+from .train import _Grads, _mp, fusion_bwd, fusion_fwd
 
 
 def _gemm_weight(conv, sum_in: bool) -> torch.Tensor:
@@ -52,11 +64,46 @@ def _gemm_weight(conv, sum_in: bool) -> torch.Tensor:
     return w.contiguous()
 
 
+def _conv_bn_fwd16(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_in: bool, residual: Optional[torch.Tensor], relu: bool,
+                   mp: torch.dtype):
+    """The unit in train_storage='16bit': x [n,H,W,Cin] ALREADY in mp (the producer's y; the stem: the fp32 source images), residual
+    [rows, Cout] in mp -> y [n,Ho,Wo,Cout] in mp.  The record keeps z and y (ReLU units) in mp and a reference to x: nothing fp32 but the
+    [C] statistics, no copy of the input."""
+    n, H, W, Cin = x.shape
+    wg = _gemm_weight(conv, sum_in)
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Cout, K = wg.shape[0], k * k * Cin
+    col16 = None
+    if x.dtype == mp and Cin % 64 == 0 and Cout % 64 == 0:
+        z = hip.conv_gemm16(x, hip.cvt16(wg[:, :K].contiguous(), mp), None, k, k, stride, pad, epilogue=hip.EPI_BIAS, out_dtype=mp)
+    elif x.dtype == torch.float32 and Cout % 64 == 0:
+        # the stem (fp32 source images; 49 taps after the gray fold, 147 for three channels): its 16-bit im2col rows, padded to a multiple
+        # of 64 columns, are the "pixels" of a 1 x 1 convolution -- for the forward and for the weight gradient
+        kp = (K + 63) // 64 * 64
+        w64 = torch.zeros((Cout, kp), dtype=torch.float32, device=x.device)
+        w64[:, :K] = wg[:, :K]
+        col16 = hip.im2col_nhwc(x, k, k, stride, pad, kp, out_dtype=mp).view(n * Ho * Wo, 1, 1, kp)
+        z = hip.conv_gemm16(col16, hip.cvt16(w64, mp), None, 1, 1, 1, 0, epilogue=hip.EPI_BIAS, out_dtype=mp)
+    else:
+        raise ValueError(f"train_storage='16bit': a {k} x {k} convolution {Cin} -> {Cout} on a {x.dtype} input cannot take the 16-bit products "
+                         "(behind the stem Cin and Cout must be multiples of 64 and the input already in the 16-bit type)")
+    y, mean, rstd = hip.batchnorm_train16(z, bn, residual, relu)
+    bn.num_batches_tracked += 1
+    rec = {"x": x, "z": z, "y": y if relu else None, "mean": mean, "rstd": rstd, "k": k, "stride": stride, "pad": pad, "sum_in": sum_in,
+           "relu": relu, "conv": conv, "bn": bn, "mp": mp, "col16": col16, "storage16": True}
+    return y.view(n, Ho, Wo, Cout), rec
+
+
 def _conv_bn_fwd(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_in: bool, residual: Optional[torch.Tensor],
-                 relu: bool, mp: Optional[torch.dtype] = None):
+                 relu: bool, mp: Optional[torch.dtype] = None, storage16: bool = False):
     """x [n,H,W,C] -> y [n,Ho,Wo,Cout] plus the record the backward needs.  mp (train_precision bf16 / fp16): the convolution and its
     two gradients on 16-bit MFMA operands (fp32 accumulation; activations, BatchNorm and everything stored stay fp32) --
-    the reference's Trainer(precision='16-mixed') for F.conv2d."""
+    the reference's Trainer(precision='16-mixed') for F.conv2d.  storage16 (train_storage='16bit', needs mp): _conv_bn_fwd16."""
+    if storage16:
+        if mp is None:
+            raise ValueError("train_storage='16bit' needs train_precision 'bf16' or 'fp16' (the saved tensors are the 16-bit operands of the "
+                             "mixed-precision kernels)")
+        return _conv_bn_fwd16(x, conv, bn, k, stride, pad, sum_in, residual, relu, mp)
     n, H, W, Cin = x.shape
     wg = _gemm_weight(conv, sum_in)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
@@ -90,9 +137,38 @@ def _split(n: int, hw: int):
     return n, s2
 
 
-def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool) -> Optional[torch.Tensor]:
+def _conv_bn_bwd16(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool) -> Optional[torch.Tensor]:
+    """The unit's backward on a train_storage='16bit' record: ONE BatchNorm call (ReLU mask from the saved y, d gamma / d beta, dz rounded
+    to the 16-bit type, dy <- masked dy when mask_dy), then the two 16-bit products on dz and the record's own tensors."""
+    x, z, mp = rec["x"], rec["z"], rec["mp"]
+    conv, bn = rec["conv"], rec["bn"]
+    k, stride, pad = rec["k"], rec["stride"], rec["pad"]
+    n, H, W, Cin = x.shape
+    rows, Cout = z.shape
+    dz16, dg, db = hip.batchnorm_bwd16(z, rec["y"], rec["mean"], rec["rstd"], bn.weight.detach(), dy, mask_dy and rec["relu"])
+    G.put(bn.weight, dg)
+    G.put(bn.bias, db)
+    K = k * k * Cin
+    if rec["col16"] is not None:                                         # the stem: d weight over its 16-bit im2col "pixels"
+        dwg = hip.conv_wgrad(dz16, rec["col16"], 1, 1, 0)
+    else:
+        dwg = hip.conv_wgrad(dz16, x, k, stride, pad)                    # x IS the producer's 16-bit output
+    dw = dwg[:, :K].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
+    if rec["sum_in"]:
+        dw = dw.expand(Cout, conv.weight.shape[1], k, k)
+    G.put(conv.weight, dw.contiguous())
+    if not need_dx:
+        return None
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    return hip.conv_dgrad(dz16.view(n, Ho, Wo, Cout), hip.conv_dgrad_weight(conv.weight, mp), k, stride, pad, H, W)
+
+
+def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool = True) -> Optional[torch.Tensor]:
     """dy [rows, Cout] = gradient of the unit's output (modified in place by the ReLU mask).  Returns dx [n,H,W,C] or None.  The
-    caller routes the masked dy to the residual branch itself."""
+    caller routes the masked dy to the residual branch itself.  mask_dy=False (train_storage='16bit' records only): nobody reads the
+    masked dy, so it is not written back."""
+    if rec.get("storage16"):
+        return _conv_bn_bwd16(G, rec, dy, need_dx, mask_dy)
     x, z, wg = rec["x"], rec["z"], rec["wg"]
     conv, bn = rec["conv"], rec["bn"]
     k, stride, pad = rec["k"], rec["stride"], rec["pad"]
@@ -146,35 +222,36 @@ def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool) -> Optional[to
     return hip.col2im_nhwc(col, dx, k, k, stride, pad)
 
 
-def backbone_fwd(m, x_nhwc: torch.Tensor, sum_in: bool, mp: Optional[torch.dtype] = None):
-    """torchvision resnet{18,34,50,101,152} forward in train mode up to the pooled features [n, 512 or 2048]."""
-    sv = {"units": []}
-    y, sv["stem"] = _conv_bn_fwd(x_nhwc.contiguous(), m.conv1, m.bn1, 7, 2, 3, sum_in, None, True, mp)
+def backbone_fwd(m, x_nhwc: torch.Tensor, sum_in: bool, mp: Optional[torch.dtype] = None, storage16: bool = False):
+    """torchvision resnet{18,34,50,101,152} forward in train mode up to the pooled features [n, 512 or 2048].  storage16: every activation
+    between the stem's im2col and the average pool lives in mp (max pool: mst_maxpool_nhwc16, features: mst_avgpool_nhwc16)."""
+    sv = {"units": [], "mp": mp, "storage": "16bit" if storage16 else "fp32"}
+    y, sv["stem"] = _conv_bn_fwd(x_nhwc.contiguous(), m.conv1, m.bn1, 7, 2, 3, sum_in, None, True, mp, storage16)
     sv["pool_in"] = y
     y = hip.maxpool_nhwc(y)
     for li in range(4):
         for blk in getattr(m, f"layer{li + 1}"):
             n, H, W, Cin = y.shape
             if hasattr(blk, "conv3"):                                    # bottleneck: 1x1 -> 3x3 (stride) -> 1x1 + residual
-                h0, r0 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 1, 1, 0, False, None, True, mp)
-                h1, r1 = _conv_bn_fwd(h0, blk.conv2, blk.bn2, 3, blk.stride, 1, False, None, True, mp)
+                h0, r0 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 1, 1, 0, False, None, True, mp, storage16)
+                h1, r1 = _conv_bn_fwd(h0, blk.conv2, blk.bn2, 3, blk.stride, 1, False, None, True, mp, storage16)
                 rd = None
                 if hasattr(blk, "downsample"):
-                    idt, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp)
+                    idt, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp, storage16)
                     idt = idt.reshape(-1, idt.shape[-1])
                 else:
                     idt = y.reshape(n * H * W, Cin)
-                y, r2 = _conv_bn_fwd(h1, blk.conv3, blk.bn3, 1, 1, 0, False, idt, True, mp)
+                y, r2 = _conv_bn_fwd(h1, blk.conv3, blk.bn3, 1, 1, 0, False, idt, True, mp, storage16)
                 sv["units"].append((r0, r2, rd, r1))
                 continue
-            h1, r1 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 3, blk.stride, 1, False, None, True, mp)
+            h1, r1 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 3, blk.stride, 1, False, None, True, mp, storage16)
             rd = None
             if hasattr(blk, "downsample"):
-                idt, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp)
+                idt, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp, storage16)
                 idt = idt.reshape(-1, idt.shape[-1])
             else:
                 idt = y.reshape(n * H * W, Cin)
-            y, r2 = _conv_bn_fwd(h1, blk.conv2, blk.bn2, 3, 1, 1, False, idt, True, mp)
+            y, r2 = _conv_bn_fwd(h1, blk.conv2, blk.bn2, 3, 1, 1, False, idt, True, mp, storage16)
             sv["units"].append((r1, r2, rd, None))
     sv["last"] = y
     return hip.avgpool_nhwc(y), sv
@@ -187,23 +264,36 @@ def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor):
     for r1, r2, rd, rmid in reversed(sv["units"]):
         dh1 = _conv_bn_bwd(G, r2, dy, True)                               # dy now carries the ReLU mask of the block output
         if rmid is not None:                                              # bottleneck: through the 3x3 unit to the first 1x1's output
-            dh1 = _conv_bn_bwd(G, rmid, dh1.view(-1, dh1.shape[-1]), True)
+            dh1 = _conv_bn_bwd(G, rmid, dh1.view(-1, dh1.shape[-1]), True, False)
         xin = r1["x"]
         if rd is not None:
-            dx = _conv_bn_bwd(G, rd, dy.clone(), True)
+            dx = _conv_bn_bwd(G, rd, dy if rd.get("storage16") else dy.clone(), True)    # (the 16-bit form leaves a unit without ReLU's dy alone)
         else:
             dx = dy.view(xin.shape).clone()
-        d1 = _conv_bn_bwd(G, r1, dh1.view(-1, dh1.shape[-1]), True)
+        d1 = _conv_bn_bwd(G, r1, dh1.view(-1, dh1.shape[-1]), True, False)
         hip.axpby_cols(d1.view(1, -1), dx.view(1, -1))
         dy = dx.view(-1, dx.shape[-1])
     dstem = hip.maxpool_bwd_nhwc(sv["pool_in"], dy.view(sv["units"][0][0]["x"].shape))
-    _conv_bn_bwd(G, sv["stem"], dstem.view(-1, dstem.shape[-1]), False)
+    _conv_bn_bwd(G, sv["stem"], dstem.view(-1, dstem.shape[-1]), False, False)
 
 
 # ---- whole models ------------------------------------------------------------------------------------------------------
+def _storage16(model, mp: Optional[torch.dtype]) -> bool:
+    """train_storage of the backbone: 'fp32' (default) or '16bit'; the latter needs a 16-bit operand type.  Re-checked at every call (the
+    attributes may have been changed after construction); never inferred from an autocast region."""
+    ts = getattr(model, "train_storage", "fp32")
+    if ts not in ("fp32", "16bit"):
+        raise ValueError(f"train_storage must be 'fp32' or '16bit' (got {ts!r})")
+    if ts == "16bit" and mp is None:
+        raise ValueError("train_storage='16bit' needs train_precision 'bf16' or 'fp16' (the saved tensors are the 16-bit operands of the "
+                         "mixed-precision kernels)")
+    return ts == "16bit"
+
+
 def forward_train(model, x_nhwc: torch.Tensor, sum_in: bool, B: Optional[int], D: Optional[int], mask: Optional[torch.Tensor]):
     """B/D given: ResNetSliceTrans (features -> slice transformer -> linear); else plain ResNet (features -> fc)."""
-    feat, sv = backbone_fwd(model.model, x_nhwc, sum_in, {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}[getattr(model, "train_precision", "fp32")])
+    mp = _mp(model)                                      # train_precision, or the enclosing autocast region's type for a defaulted model
+    feat, sv = backbone_fwd(model.model, x_nhwc, sum_in, mp, _storage16(model, mp))
     sv["feat"] = feat
     if B is None:
         fc = model.model.fc

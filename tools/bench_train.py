@@ -5,7 +5,9 @@ HIP kernels + AdamW) of both model families, and the ViT-B forward on the unfuse
 --no-fill on top: torch.utils.deterministic.fill_uninitialized_memory = False, to tell torch's NaN fill from the kernels' cost.
 --input-grad: the source-gradient timings (input_grad_cases).
 --train-storage 16bit (beside --train-attention flash and a 16-bit precision): the encoder blocks' saved activations in 16 bits.  A comma
-list (fp32,16bit,fp32) times those modes one after the other in this process: the repeated mode gives the spread the other is read against."""
+list (fp32,16bit,fp32) times those modes one after the other in this process: the repeated mode gives the spread the other is read against.
+The same list drives the ResNet cases (train_storage of ResNetSliceTrans: --c3 for the configs[3] shape, --only-resnet for 2 x 32 x 224^2; add
+--c3-only to --c3 to leave the smaller shape out)."""
 import json
 import sys
 import time
@@ -233,17 +235,26 @@ def main():
                 torch.cuda.empty_cache()
     if "--only-dino-c1" in sys.argv or "--only-dino-2x32" in sys.argv or "--only-dino-518" in sys.argv:
         return
-    for shape in (() if "--c3-only" in sys.argv else ((2, 1, 32, 224, 224),)):
-        m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34)
-        m.load_state_dict(synth.synth_resnet_state_dict(0, 34, 2), strict=True)
-        train_case("ResNetSliceTrans(resnet34) training step (fp32 HIP backward)", m, shape)
+    # the ResNet arms: --train-storage drives them too (the backbone's saved activations; 16-bit precisions only, fp32 keeps 'fp32'), one
+    # model per arm in the given order in this process
+    precs = ("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("fp32",)
+
+    def resnet_arms(case, shape, precs, n):
+        for prec in precs:
+            for st in (storages if prec != "fp32" else ["fp32"]):
+                m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34, train_precision=prec, train_storage=st)
+                m.load_state_dict(synth.synth_resnet_state_dict(0, 34, 2), strict=True)
+                train_case(case(prec) + (f", {st} storage" if "--train-storage" in sys.argv else ""), m, shape, n=n)
+                del m
+                torch.cuda.empty_cache()
+    if "--c3-only" not in sys.argv:
+        # the fp32 case as before; with --train-storage the 16-bit arms of --fp16 / --mixed instead
+        resnet_arms(lambda prec: "ResNetSliceTrans(resnet34) training step (fp32 HIP backward)" if prec == "fp32" else
+                    f"ResNetSliceTrans(resnet34) training step ({prec} convolutions)", (2, 1, 32, 224, 224),
+                    precs if "--train-storage" in sys.argv else ("fp32",), 5)
     if "--c3" in sys.argv:                               # BASELINE configs[3] per-GPU shape: one LIDC-shaped 128 x 512 x 512 volume
-        for prec in (("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("fp32",)):
-            m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34, train_precision=prec)
-            m.load_state_dict(synth.synth_resnet_state_dict(0, 34, 2), strict=True)
-            train_case(f"ResNetSliceTrans(resnet34) training step ({prec} convolutions), BASELINE configs[3] shape", m, (1, 1, 128, 512, 512), n=3)
-            del m
-            torch.cuda.empty_cache()
+        resnet_arms(lambda prec: f"ResNetSliceTrans(resnet34) training step ({prec} convolutions), BASELINE configs[3] shape",
+                    (1, 1, 128, 512, 512), precs, 3)
         return
     if "--only-resnet" in sys.argv:
         return
