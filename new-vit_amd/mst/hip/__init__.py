@@ -218,6 +218,15 @@ def workspace(nbytes: int, device) -> Optional[torch.Tensor]:
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device) if nbytes else None
 
 
+def _call_ws(name: str, size_args, t: torch.Tensor, *args, sized_by: Optional[str] = None):
+    """Call entry point `name`, whose last three arguments are (workspace, workspace_bytes, stream), with `args` in front of them: the size
+    is `<sized_by or name>_workspace_bytes(*size_args)`, the scratch comes from workspace() on t's device (NULL / 0 for 0 bytes), the
+    stream is t's current one."""
+    lib = load()
+    ws = workspace(getattr(lib, (sized_by or name) + "_workspace_bytes")(*size_args), t.device)
+    _check(getattr(lib, name)(*args, ptr(ws), 0 if ws is None else ws.numel(), stream_of(t)), name)
+
+
 def _dev(t: torch.Tensor, what: str):
     if not t.is_cuda:
         raise RuntimeError(f"{what}: tensor must live on a HIP device (got {t.device}); the MST kernels have no CPU path")
@@ -376,12 +385,10 @@ def attention_train_bwd(qkv16: torch.Tensor, out: torch.Tensor, dout: torch.Tens
     if dqkv is None:
         dqkv = torch.empty((n_seq * N, 3 * heads * head_dim), dtype=torch.float32, device=dev)
     _f32_like(dqkv, (n_seq * N, 3 * heads * head_dim), dev, what, "dqkv")
-    lib = load()
-    nb = int(lib.mst_attention_train_bwd_workspace_bytes(n_seq, N, heads, head_dim))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    fn = lib.mst_attention_train_bwd16 if out16 else lib.mst_attention_train_bwd
-    _check(fn(ptr(qkv16), dt_of(qkv16), ptr(out), ptr(dout), ptr(lse), n_seq, N, heads, head_dim, dq_scale, ptr(dqkv), ptr(ws), nb,
-              stream_of(qkv16)), "mst_attention_train_bwd16" if out16 else "mst_attention_train_bwd")
+    # (0 bytes only for sizes the library refuses before it looks at the workspace: no minimum needed)
+    _call_ws("mst_attention_train_bwd16" if out16 else "mst_attention_train_bwd", (n_seq, N, heads, head_dim), qkv16,
+             ptr(qkv16), dt_of(qkv16), ptr(out), ptr(dout), ptr(lse), n_seq, N, heads, head_dim, dq_scale, ptr(dqkv),
+             sized_by="mst_attention_train_bwd")
     return dqkv
 
 
@@ -729,11 +736,8 @@ def layernorm_rows(x: torch.Tensor, x_stride: int, rows: int, cols: int, weight,
 
 def layernorm_bwd(x, x_stride, gamma, dy, dy_stride, dres, dres_stride, dx, dx_stride, dgamma, dbeta, rows, cols, eps):
     if deterministic():
-        lib = load()
-        ws = workspace(lib.mst_layernorm_bwd_ordered_workspace_bytes(rows, cols), x.device)
-        _check(lib.mst_layernorm_bwd_ordered(ptr(x), x_stride, ptr(gamma), ptr(dy), dy_stride, ptr(dres), dres_stride, ptr(dx), dx_stride,
-                                             ptr(dgamma), ptr(dbeta), rows, cols, eps, ptr(ws), 0 if ws is None else ws.numel(), stream_of(x)),
-               "mst_layernorm_bwd_ordered")
+        _call_ws("mst_layernorm_bwd_ordered", (rows, cols), x, ptr(x), x_stride, ptr(gamma), ptr(dy), dy_stride, ptr(dres), dres_stride,
+                 ptr(dx), dx_stride, ptr(dgamma), ptr(dbeta), rows, cols, eps)
         return
     _check(load().mst_layernorm_bwd(ptr(x), x_stride, ptr(gamma), ptr(dy), dy_stride, ptr(dres), dres_stride, ptr(dx), dx_stride,
                                     ptr(dgamma), ptr(dbeta), rows, cols, eps, stream_of(x)), "mst_layernorm_bwd")
@@ -819,19 +823,14 @@ def colsum(a: torch.Tensor, out: torch.Tensor, b: Optional[torch.Tensor] = None)
     as_ = a.stride(0) if rows > 1 else cols
     bs = (b.stride(0) if rows > 1 else cols) if b is not None else cols
     if b is not None and b.dtype != torch.float32:       # a factor saved in 16 bits (train_storage='16bit'): mst_colsum_b16 / _ordered
-        lib = load()
         if deterministic():
-            ws = workspace(lib.mst_colsum_ordered_workspace_bytes(rows, cols), a.device)
-            _check(lib.mst_colsum_b16_ordered(ptr(a), as_, ptr(b), dt_of(b), bs, rows, cols, ptr(out), ptr(ws), 0 if ws is None else ws.numel(),
-                                              stream_of(a)), "mst_colsum_b16_ordered")
+            _call_ws("mst_colsum_b16_ordered", (rows, cols), a, ptr(a), as_, ptr(b), dt_of(b), bs, rows, cols, ptr(out),
+                     sized_by="mst_colsum_ordered")
         else:
-            _check(lib.mst_colsum_b16(ptr(a), as_, ptr(b), dt_of(b), bs, rows, cols, ptr(out), stream_of(a)), "mst_colsum_b16")
+            _check(load().mst_colsum_b16(ptr(a), as_, ptr(b), dt_of(b), bs, rows, cols, ptr(out), stream_of(a)), "mst_colsum_b16")
         return out
     if deterministic():
-        lib = load()
-        ws = workspace(lib.mst_colsum_ordered_workspace_bytes(rows, cols), a.device)
-        _check(lib.mst_colsum_ordered(ptr(a), as_, ptr(b), bs, rows, cols, ptr(out), ptr(ws), 0 if ws is None else ws.numel(), stream_of(a)),
-               "mst_colsum_ordered")
+        _call_ws("mst_colsum_ordered", (rows, cols), a, ptr(a), as_, ptr(b), bs, rows, cols, ptr(out))
         return out
     _check(load().mst_colsum(ptr(a), as_, ptr(b), bs, rows, cols, ptr(out), stream_of(a)), "mst_colsum")
     return out
@@ -877,10 +876,7 @@ def patch_embed_dgrad(dx: torch.Tensor, wsum: torch.Tensor, n: int, H: int, W: i
 def pos_embed_interp_bwd(dout: torch.Tensor, M: int, gh: int, gw: int, offset: float, dpos: torch.Tensor):
     E = dout.shape[-1]
     if deterministic():
-        lib = load()
-        ws = workspace(lib.mst_pos_embed_interp_bwd_ordered_workspace_bytes(M, E, gh, gw), dout.device)
-        _check(lib.mst_pos_embed_interp_bwd_ordered(ptr(dout), M, E, gh, gw, offset, ptr(dpos), ptr(ws), ws.numel(), stream_of(dout)),
-               "mst_pos_embed_interp_bwd_ordered")
+        _call_ws("mst_pos_embed_interp_bwd_ordered", (M, E, gh, gw), dout, ptr(dout), M, E, gh, gw, offset, ptr(dpos))
         return dpos
     _check(load().mst_pos_embed_interp_bwd(ptr(dout), M, E, gh, gw, offset, ptr(dpos), stream_of(dout)), "mst_pos_embed_interp_bwd")
     return dpos
@@ -1024,11 +1020,8 @@ def batchnorm_train(z: torch.Tensor, bn, residual: Optional[torch.Tensor], relu:
     mean = torch.empty(Cc, dtype=torch.float32, device=dev)
     rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
     if deterministic():
-        lib = load()
-        ws = workspace(lib.mst_batchnorm_train_ordered_workspace_bytes(rows, Cc), dev)
-        _check(lib.mst_batchnorm_train_ordered(ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum,
-                                               ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean),
-                                               ptr(bn.running_var), ptr(ws), ws.numel(), stream_of(z)), "mst_batchnorm_train_ordered")
+        _call_ws("mst_batchnorm_train_ordered", (rows, Cc), z, ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps,
+                 momentum, ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var))
         return y, mean, rstd
     scratch = torch.empty(Cc, dtype=torch.float32, device=dev)
     _check(load().mst_batchnorm_train(ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum, ptr(residual),
@@ -1044,10 +1037,8 @@ def batchnorm_bwd(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma
     db = torch.zeros(Cc, dtype=torch.float32, device=z.device)
     dz = torch.empty_like(z)
     if deterministic():
-        lib = load()
-        ws = workspace(lib.mst_batchnorm_bwd_ordered_workspace_bytes(rows, Cc), z.device)
-        _check(lib.mst_batchnorm_bwd_ordered(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), rows, Cc, ptr(dg), ptr(db), ptr(dz),
-                                             ptr(ws), 0 if ws is None else ws.numel(), stream_of(z)), "mst_batchnorm_bwd_ordered")
+        _call_ws("mst_batchnorm_bwd_ordered", (rows, Cc), z, ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), rows, Cc, ptr(dg), ptr(db),
+                 ptr(dz))
         return dz, dg, db
     _check(load().mst_batchnorm_bwd(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), rows, Cc, ptr(dg), ptr(db), ptr(dz),
                                     stream_of(z)), "mst_batchnorm_bwd")
@@ -1065,11 +1056,8 @@ def batchnorm_train16(z: torch.Tensor, bn, residual: Optional[torch.Tensor], rel
     y = torch.empty_like(z)
     mean = torch.empty(Cc, dtype=torch.float32, device=dev)
     rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
-    lib = load()
-    ws = workspace(lib.mst_batchnorm_train16_workspace_bytes(rows, Cc), dev)
-    _check(lib.mst_batchnorm_train16(ptr(z), dt_of(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum, ptr(residual),
-                                     1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var), ptr(ws),
-                                     0 if ws is None else ws.numel(), stream_of(z)), "mst_batchnorm_train16")
+    _call_ws("mst_batchnorm_train16", (rows, Cc), z, ptr(z), dt_of(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps,
+             momentum, ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var))
     return y, mean, rstd
 
 
@@ -1086,10 +1074,8 @@ def batchnorm_bwd16(z: torch.Tensor, y: Optional[torch.Tensor], mean: torch.Tens
     dg = torch.empty(Cc, dtype=torch.float32, device=dev)
     db = torch.empty(Cc, dtype=torch.float32, device=dev)
     dz = torch.empty_like(z)
-    lib = load()
-    ws = workspace(lib.mst_batchnorm_bwd16_workspace_bytes(rows, Cc), dev)
-    _check(lib.mst_batchnorm_bwd16(ptr(z), ptr(y), dt_of(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), 1 if mask_dy_in_place else 0, rows, Cc,
-                                   ptr(dg), ptr(db), ptr(dz), ptr(ws), 0 if ws is None else ws.numel(), stream_of(z)), "mst_batchnorm_bwd16")
+    _call_ws("mst_batchnorm_bwd16", (rows, Cc), z, ptr(z), ptr(y), dt_of(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy),
+             1 if mask_dy_in_place else 0, rows, Cc, ptr(dg), ptr(db), ptr(dz))
     return dz, dg, db
 
 
@@ -1108,17 +1094,11 @@ def maxpool_bwd_nhwc(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     n, H, W, Cc = x.shape
     if x.dtype != torch.float32:                         # the pool input saved in bf16 / fp16: the gather form in both determinism modes
         dx = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
-        lib = load()
-        ws = workspace(lib.mst_maxpool_bwd_nhwc16_workspace_bytes(n, H, W, Cc), x.device)
-        _check(lib.mst_maxpool_bwd_nhwc16(ptr(x), dt_of(x), ptr(dy), n, H, W, Cc, ptr(dx), ptr(ws), 0 if ws is None else ws.numel(), stream_of(x)),
-               "mst_maxpool_bwd_nhwc16")
+        _call_ws("mst_maxpool_bwd_nhwc16", (n, H, W, Cc), x, ptr(x), dt_of(x), ptr(dy), n, H, W, Cc, ptr(dx))
         return dx
     dx = torch.zeros_like(x)
     if deterministic():
-        lib = load()
-        ws = workspace(lib.mst_maxpool_bwd_nhwc_gather_workspace_bytes(n, H, W, Cc), x.device)
-        _check(lib.mst_maxpool_bwd_nhwc_gather(ptr(x), ptr(dy), n, H, W, Cc, ptr(dx), ptr(ws), ws.numel(), stream_of(x)),
-               "mst_maxpool_bwd_nhwc_gather")
+        _call_ws("mst_maxpool_bwd_nhwc_gather", (n, H, W, Cc), x, ptr(x), ptr(dy), n, H, W, Cc, ptr(dx))
         return dx
     _check(load().mst_maxpool_bwd_nhwc(ptr(x), ptr(dy), n, H, W, Cc, ptr(dx), stream_of(x)), "mst_maxpool_bwd_nhwc")
     return dx

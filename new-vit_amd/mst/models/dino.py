@@ -12,23 +12,7 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
                   TF32-class path (reference GPUs run TF32: main_predict.py:195), fp32 is exact.
                   'fp8' (BASELINE configs[4]): the blocks' four linear layers with OCP e4m3 operands and
                   per-tensor absmax scales (dynamic for activations), everything else as in bf16 mode.
-  train_precision 'fp32' (default) | 'bf16' | 'fp16': MFMA operand type of the blocks' nn.Linear products in the TRAINING step
-                  (forward and backward; fp32 accumulation, fp32 storage and every other op fp32): the reference trains under
-                  Trainer(precision='16-mixed') (scripts/main_train.py:110-123).  fp32 is the exact mode the gradient parity bar is on.
-                  Autocast: when the value was given neither by keyword nor by MST_TRAIN_PRECISION (the attribute then reads 'fp32'),
-                  a training forward inside an enabled ``torch.autocast('cuda', dtype=torch.float16 | torch.bfloat16)`` region runs
-                  the blocks' linear products on that type, as the reference's Lightning trainer makes F.linear do; the backward
-                  follows the forward's choice wherever it runs.  A given value -- an explicit 'fp32' included -- is never overridden,
-                  nothing changes outside a region, the logits stay fp32, and train_attention / train_storage are not inferred.
-  train_attention 'stored' (default) | 'flash' (env MST_TRAIN_ATTENTION): how the encoder blocks' attention trains.  'stored' keeps
-                  the fp32 [n, heads, N, N] probabilities until the backward; 'flash' (needs train_precision 'bf16' / 'fp16', same
-                  16-bit type) keeps the 16-bit q | k | v, the output and the per-row log-sum-exp and recomputes the probabilities
-                  per tile in the backward, like the reference's MemEffAttention.  ValueError with fp32 or an unknown value.
-  train_storage   'fp32' (default) | '16bit' (env MST_TRAIN_STORAGE): the type of what the 12 encoder blocks keep for their backward.
-                  '16bit' (needs a 16-bit train_precision and train_attention='flash', ValueError otherwise) keeps the LayerNorm
-                  outputs, the attention output, the branch outputs and the MLP's hidden activations in train_precision's type, as
-                  the reference's autocast does: at most 40 E bytes per token and block instead of 66 E, and no operand re-rounding
-                  passes.  The residual stream, every gradient, the token stage, the slice transformer and the head stay fp32.
+  train_precision, train_attention, train_storage  the mode of the TRAINING step: see mst/train_mode.py.
   Gradients: under torch.enable_grad() the forward returns logits with one autograd node (mst/train.py) when a parameter requires grad,
                   or when ``source`` is a floating tensor that requires grad (a frozen model: saliency, attribution), ``save_attn`` is off and
                   the model is not slice-sharded.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
@@ -49,7 +33,7 @@ import torch
 import torch.nn as nn
 
 from .base_model import BasicClassifier
-from .. import hip
+from .. import hip, train_mode
 from ..parallel import SliceSharding
 
 PATCH = 14
@@ -214,22 +198,6 @@ class _SliceFusion(_Params):  # nn.TransformerEncoder(num_layers=1, norm=LayerNo
         self.norm = _ln(E)
 
 
-def _check_train_storage(train_storage: str, train_precision: str, train_attention: str) -> None:
-    if train_storage not in ("fp32", "16bit"):
-        raise ValueError(f"train_storage must be 'fp32' or '16bit' (got {train_storage!r})")
-    if train_storage == "16bit" and (train_precision not in ("bf16", "fp16") or train_attention != "flash"):
-        raise ValueError("train_storage='16bit' keeps the 16-bit operands of the mixed-precision kernels: it needs train_precision 'bf16' or "
-                         f"'fp16' and train_attention='flash' (got {train_precision!r}, {train_attention!r})")
-
-
-def _check_train_attention(train_attention: str, train_precision: str) -> None:
-    if train_attention not in ("stored", "flash"):
-        raise ValueError(f"train_attention must be 'stored' or 'flash' (got {train_attention!r})")
-    if train_attention == "flash" and train_precision not in ("bf16", "fp16"):
-        raise ValueError("train_attention='flash' runs on 16-bit MFMA operands: it needs train_precision 'bf16' or 'fp16' "
-                         f"(got {train_precision!r}; the fp32 step is the exact-parity mode and keeps the stored probabilities)")
-
-
 # ------------------------------------------------------------------------------------------------
 class DinoV2ClassifierSlice(BasicClassifier):
     def __init__(self, in_ch, out_ch, spatial_dims=2, pretrained=True, save_attn=False,
@@ -247,19 +215,10 @@ class DinoV2ClassifierSlice(BasicClassifier):
         # tokens): measured on the MI355X box the 16 x 224^2 forward takes 1.083 ms eager and 1.082 ms replayed -- the ~90 launches are
         # not the bound, the under-filled kernels are (profiles/r04d_small_shapes.txt).  Results are the eager ones bit for bit.
         use_graph = str(kwargs.pop("use_graph", os.environ.get("MST_USE_GRAPH", "0"))).lower()
-        # given by keyword or environment?  If not, the training forward follows an enclosing autocast region (mst/train.py::_mp).  The
-        # underscore keeps the flag out of the saved hyper-parameters (they are the constructor's public locals)
-        _precision_given = "train_precision" in kwargs or "MST_TRAIN_PRECISION" in os.environ
-        train_precision = str(kwargs.pop("train_precision", os.environ.get("MST_TRAIN_PRECISION", "fp32"))).lower()
-        if train_precision not in ("fp32", "bf16", "fp16"):
-            raise ValueError("train_precision must be 'fp32', 'bf16' or 'fp16'")
-        # opt-in: the encoder blocks' attention in the TRAINING step without the stored [n, heads, N, N] probabilities (the reference's
-        # MemEffAttention): 16-bit flash forward + FlashAttention-2 backward (csrc/k_attn16_train.hip) on train_precision's type
-        train_attention = str(kwargs.pop("train_attention", os.environ.get("MST_TRAIN_ATTENTION", "stored"))).lower()
-        _check_train_attention(train_attention, train_precision)
-        # opt-in: what the encoder blocks save for the backward in train_precision's 16-bit type (csrc/k_train16.hip)
-        train_storage = str(kwargs.pop("train_storage", os.environ.get("MST_TRAIN_STORAGE", "fp32"))).lower()
-        _check_train_storage(train_storage, train_precision, train_attention)
+        # the training mode (mst/train_mode.py).  The underscore keeps the "was train_precision given" flag out of the saved
+        # hyper-parameters (they are the constructor's public locals)
+        train_precision, train_attention, train_storage, _precision_given = train_mode.from_kwargs(
+            kwargs, storage_env="MST_TRAIN_STORAGE", attention=True)
         if compute_dtype not in hip.DT_NAMES:
             raise ValueError(f"compute_dtype must be one of {sorted(hip.DT_NAMES)}")
         super().__init__(in_ch, out_ch, spatial_dims=spatial_dims, optimizer_kwargs=optimizer_kwargs, **kwargs)

@@ -39,7 +39,7 @@ import torch
 import torch.nn as nn
 
 from .base_model import BasicClassifier
-from .. import hip
+from .. import hip, train_mode
 
 _LAYERS = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}
 _WIDTHS = [64, 128, 256, 512]
@@ -154,14 +154,6 @@ def _fold(conv: _Conv, bn: _BN, sum_in: bool, dev, dtype: torch.dtype = torch.fl
     return w.to(dtype).contiguous(), b.contiguous(), kpad
 
 
-def _check_train_storage(train_storage: str, train_precision: str) -> None:
-    if train_storage not in ("fp32", "16bit"):
-        raise ValueError(f"train_storage must be 'fp32' or '16bit' (got {train_storage!r})")
-    if train_storage == "16bit" and train_precision not in ("bf16", "fp16"):
-        raise ValueError("train_storage='16bit' keeps the 16-bit operands of the mixed-precision kernels: it needs train_precision 'bf16' or "
-                         f"'fp16' (got {train_precision!r})")
-
-
 class ResNet(BasicClassifier):
     def __init__(self, in_ch, out_ch, spatial_dims=3, model=34, pretrained=False, kwargs_resnet={}, **kwargs):
         emb_ch = kwargs.pop("emb_ch", out_ch)
@@ -174,21 +166,9 @@ class ResNet(BasicClassifier):
         if cdt not in ("fp32", "bf16", "fp16"):
             raise ValueError("ResNet: compute_dtype must be 'fp32', 'bf16' or 'fp16'")
         self.compute_dtype_name = cdt
-        # build-specific: MFMA operand type of the TRAINING step's convolutions and their input gradients ('fp32' default | 'bf16' | 'fp16';
-        # fp32 accumulation and storage; the reference trains under Trainer(precision='16-mixed'), scripts/main_train.py:110-123).
-        # Autocast: when the value was given neither by keyword nor by MST_TRAIN_PRECISION (the attribute then reads 'fp32'), a training
-        # forward inside an enabled torch.autocast('cuda', dtype=float16 | bfloat16) region takes that type (mst.train._mp, as
-        # DinoV2ClassifierSlice does); an explicit value, 'fp32' included, is never overridden.
-        precision_given = "train_precision" in kwargs or "MST_TRAIN_PRECISION" in os.environ
-        tp = str(kwargs.pop("train_precision", os.environ.get("MST_TRAIN_PRECISION", "fp32"))).lower()
-        if tp not in ("fp32", "bf16", "fp16"):
-            raise ValueError("ResNet: train_precision must be 'fp32', 'bf16' or 'fp16'")
-        # build-specific, opt-in: what the TRAINING step's convolution + BatchNorm units keep for their backward: 'fp32' (default) | '16bit'
-        # (env MST_RESNET_TRAIN_STORAGE; MST_TRAIN_STORAGE stays DinoV2ClassifierSlice's).  '16bit' keeps the convolution outputs and the
-        # BatchNorm / ReLU outputs in train_precision's type, as the reference's autocast does (csrc/k_bn16.hip): 4 bytes saved per
-        # activation element instead of 10; it needs a 16-bit train_precision and is never inferred from an autocast region.
-        ts = str(kwargs.pop("train_storage", os.environ.get("MST_RESNET_TRAIN_STORAGE", "fp32"))).lower()
-        _check_train_storage(ts, tp)
+        # build-specific: the training mode (mst/train_mode.py): train_precision and train_storage; a ResNet has no train_attention, and
+        # DinoV2ClassifierSlice's MST_TRAIN_STORAGE does not reach it
+        tp, _, ts, precision_given = train_mode.from_kwargs(kwargs, storage_env="MST_RESNET_TRAIN_STORAGE", attention=False)
         self.train_precision = tp
         self.train_storage = ts
         self._train_precision_given = precision_given

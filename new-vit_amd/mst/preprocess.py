@@ -56,9 +56,8 @@ def znormalize(x: torch.Tensor, percentiles: Tuple[float, float] = (0, 100), ret
     state = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     out = torch.empty_like(x)
     if hip.deterministic():                             # torch.use_deterministic_algorithms: the fixed-order moment sums
-        ws = hip.workspace(lib.mst_znorm_ordered_workspace_bytes(x.numel()), x.device)
-        hip._check(lib.mst_znorm_ordered(hip.ptr(x), x.numel(), percentiles[0] / 100.0, percentiles[1] / 100.0, hip.ptr(out), hip.ptr(state),
-                                         hip.ptr(ws), ws.numel(), hip.stream_of(x)), "mst_znorm_ordered")
+        hip._call_ws("mst_znorm_ordered", (x.numel(),), x, hip.ptr(x), x.numel(), percentiles[0] / 100.0, percentiles[1] / 100.0, hip.ptr(out),
+                     hip.ptr(state))
     else:
         hip._check(lib.mst_znorm(hip.ptr(x), x.numel(), percentiles[0] / 100.0, percentiles[1] / 100.0, hip.ptr(out), hip.ptr(state),
                                  hip.stream_of(x)), "mst_znorm")

@@ -7,26 +7,8 @@ backward produces the gradient of every parameter with the kernels of csrc/k_tra
 `mst_softmax_rows_bwd`, `mst_act_bwd`, ...).  The loss itself stays the reference's own ``torch.nn.CrossEntropyLoss`` call on the
 [B, out_ch] logits (host code).  torch is used for memory only (allocation, views, concatenation / copies of whole tensors).
 
-Default: everything in exact fp32 (fp32 MFMA), whatever ``compute_dtype`` the inference path uses -- the mode the gradient parity bar
-(1e-4 against float64 autograd of the CPU oracle on every parameter, tests/test_train_gpu.py, tests/test_train_parity_gpu.py) is on.  ``train_precision='fp16' | 'bf16'`` (the
-reference's Trainer(precision='16-mixed'), scripts/main_train.py:110-123) runs the blocks' nn.Linear products -- forward, d input, d weight
--- on 16-bit MFMA operands with fp32 accumulation; every other op and everything stored stays fp32.  By default
-(``train_attention='stored'``) the attention probabilities of every block are kept ([n, heads, N, N] fp32: 2.9 GB per block at
-64 x 518^2).  ``train_attention='flash'`` (16-bit train_precision only, ValueError otherwise) is the reference's MemEffAttention: the
-encoder blocks keep the 16-bit q | k | v (written so by the QKV GEMM), the fp32 output and the per-row log-sum-exp instead, and the
-backward recomputes the probabilities per tile (csrc/k_attn16_train.hip: 16-bit flash forward, FlashAttention-2 backward with a
-separate deterministic dQ pass); no [N, N] tensor exists.  The across-slice transformer's attention always stays on the stored path.
-``train_storage='16bit'`` (16-bit train_precision and 'flash' only, ValueError otherwise; re-checked at every call) keeps what the 12 encoder
-blocks save for the backward in that 16-bit type, as the reference's autocast does: per token and block x0, x1 (the fp32 residual stream,
-what mst_layernorm_bwd reads; x0 of block i + 1 is x2 of block i), xn1, xn2, a, br1, br2 [E] and qkv16 [3E], hpre, hact [4E] in 16 bits
--- 40 E bytes plus the log-sum-exp instead of 66 E, and no 16-bit operand images beside them.  Each is written in 16 bits by its producer
-(the LayerNorm, the GEMM epilogue, the attention epilogue, the GELU) and is itself the operand of the forward product behind it, of that
-product's weight gradient and of the elementwise backward kernels (csrc/k_train16.hip: residual + LayerScale + LayerNorm in one pass, GELU
-16 -> 16 and its derivative, the LayerScale gradient with a 16-bit factor, the transposed operand image above 12,288 tokens; the flash
-kernels with a 16-bit output).  Gradients stay fp32 (they are ~1e-6: csrc/k_attn16_train.hip).
-Autocast: a model whose train_precision was given neither by keyword nor by environment takes the dtype of an enabled CUDA autocast region
-(fp16 / bf16) around the forward; the resolved precision and storage mode travel in the saved state, so the backward follows the forward's
-choice after the region has ended.
+The mode (train_precision, train_attention, train_storage and the autocast rule) is described, validated and resolved in
+mst/train_mode.py; `forward_train` resolves it once and the saved state carries it to the backward.
 RoPE slice transformers and register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn``
 inside a training forward.
 
@@ -52,61 +34,21 @@ from typing import Dict, List, Optional, Set, Tuple
 
 import torch
 
-from . import hip
+from . import hip, train_mode
+from .train_mode import TrainMode
 
 PATCH = 14
-
-
-_MP = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
-
-
-def _mp(model) -> Optional[torch.dtype]:
-    """MFMA operand type of the per-slice encoder's nn.Linear products in the training step: None = exact fp32 MFMA (default),
-    bf16 / fp16 = mixed precision -- what the reference's Trainer(precision='16-mixed') (scripts/main_train.py:110-123) does to
-    F.linear: 16-bit operands, fp32 accumulation, fp32 everywhere else (LayerNorm, softmax, GELU, residuals, gradients in memory).
-    A model whose train_precision was given neither by keyword nor by MST_TRAIN_PRECISION (and still reads 'fp32') follows an enabled
-    CUDA autocast region of fp16 / bf16 around the forward.  Called in the forward only: the backward reads the answer from the saved
-    state, the region may have ended by then."""
-    tp = getattr(model, "train_precision", "fp32")
-    if tp == "fp32" and not getattr(model, "_train_precision_given", True) and torch.is_autocast_enabled("cuda"):
-        dt = torch.get_autocast_dtype("cuda")
-        if dt in (torch.float16, torch.bfloat16):
-            return dt
-    return _MP[tp]
-
-
-def _flash(model, mp: Optional[torch.dtype]) -> bool:
-    """train_attention of the encoder blocks: 'stored' (default) keeps the fp32 probabilities, 'flash' recomputes them per tile in the
-    backward (mst_attention_train_fwd / _bwd) and needs a 16-bit train_precision.  Re-checked here: the attributes may have been changed
-    after construction."""
-    ta = getattr(model, "train_attention", "stored")
-    if ta not in ("stored", "flash"):
-        raise ValueError(f"train_attention must be 'stored' or 'flash' (got {ta!r})")
-    if ta == "flash" and mp is None:
-        raise ValueError("train_attention='flash' needs train_precision 'bf16' or 'fp16' (the fp32 step keeps the stored probabilities)")
-    return ta == "flash"
-
-
-def _storage16(model, mp: Optional[torch.dtype], flash: bool) -> bool:
-    """train_storage of the encoder blocks: 'fp32' (default) or '16bit' -- what a block keeps for its backward lives in the 16-bit type
-    (csrc/k_train16.hip); needs a 16-bit train_precision and train_attention='flash'.  Re-checked here like `_flash`."""
-    ts = getattr(model, "train_storage", "fp32")
-    if ts not in ("fp32", "16bit"):
-        raise ValueError(f"train_storage must be 'fp32' or '16bit' (got {ts!r})")
-    if ts == "16bit" and (mp is None or not flash):
-        raise ValueError("train_storage='16bit' needs train_precision 'bf16' or 'fp16' and train_attention='flash' (the saved tensors are "
-                         "the 16-bit operands of those kernels)")
-    return ts == "16bit"
 
 
 def _w16(lin, mp: torch.dtype) -> torch.Tensor:
     return hip.cvt16(lin.weight.detach(), mp)
 
 
-def _block_fwd_16(blk, nxt, xt: torch.Tensor, xn: torch.Tensor, mp: torch.dtype, n: int, N: int, heads: int, E: int):
-    """One encoder block (block.py:89-114) of the 16-bit storage mode.  xt: the fp32 residual stream, xn = norm1(xt) in `mp` (written by the
-    LayerNorm that closed the previous block).  Every tensor kept is the one the next kernel reads: no fp32 copy, no second 16-bit image.
-    Returns (saved state, x2 fp32, norm(x2) of the next block `nxt` in `mp` -- None behind the last block)."""
+def _block_fwd_16(blk, nxt, xt: torch.Tensor, xn: torch.Tensor, mode: TrainMode, n: int, N: int, heads: int, E: int):
+    """One encoder block (block.py:89-114) of the 16-bit storage mode.  xt: the fp32 residual stream, xn = norm1(xt) in mode.mp (written by
+    the LayerNorm that closed the previous block).  Every tensor kept is the one the next kernel reads: no fp32 copy, no second 16-bit image.
+    Returns (saved state, x2 fp32, norm(x2) of the next block `nxt` in mode.mp -- None behind the last block)."""
+    mp = mode.mp
     g1 = blk.ls1.gamma.detach() if hasattr(blk, "ls1") else None
     g2 = blk.ls2.gamma.detach() if hasattr(blk, "ls2") else None
     s = {"x0": xt, "x16": {}, "xn1": xn}
@@ -120,6 +62,34 @@ def _block_fwd_16(blk, nxt, xt: torch.Tensor, xn: torch.Tensor, mp: torch.dtype,
     x2, xn_next = hip.residual_layernorm16(s["x1"], s["br2"], g2, nxt.norm1.weight.detach() if nxt is not None else None,
                                            nxt.norm1.bias.detach() if nxt is not None else None, 1e-6)
     return s, x2, xn_next
+
+
+def _block_fwd(blk, nxt, xt: torch.Tensor, xn: Optional[torch.Tensor], mode: TrainMode, n: int, N: int, heads: int, E: int):
+    """The same block with fp32 storage, `_block_fwd_16`'s signature and return: every tensor kept is fp32 (but qkv16 of 'flash'), each
+    16-bit product rounds its operands into images of their own, and the block runs its own norm1 -- xn is not read, xn_next is None."""
+    mp = mode.mp
+    s = {"x0": xt, "x16": {}}
+    k16 = s["x16"] if mp is not None else None
+    s["xn1"] = hip.layernorm(xt, blk.norm1.weight.detach(), blk.norm1.bias.detach(), 1e-6)
+    if mode.flash:
+        # q | k | v straight in the 16-bit type the attention kernels read; kept with the output and the per-row log-sum-exp instead of
+        # the [n, heads, N, N] probabilities (the backward recomputes them per tile)
+        s["qkv16"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, out_dtype=mp, col_scale=0.125, scale_cols=E)
+        s["a"], s["lse"] = hip.attention_train_fwd(s["qkv16"], n, N, heads)
+    else:
+        s["qkv"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, col_scale=0.125, scale_cols=E)        # q * head_dim^-0.5 (attention.py:60)
+        s["a"], s["P"] = _attention_fwd(s["qkv"], n, N, heads, 64, 1.0, None)
+    s["br1"] = _lin_fwd(s["a"], blk.attn.proj, mp, k16)
+    x1 = xt.clone()
+    hip.axpby_cols(s["br1"], x1, g=blk.ls1.gamma.detach() if hasattr(blk, "ls1") else None)
+    s["x1"] = x1
+    s["xn2"] = hip.layernorm(x1, blk.norm2.weight.detach(), blk.norm2.bias.detach(), 1e-6)
+    s["hpre"] = _lin_fwd(s["xn2"], blk.mlp.fc1, mp, k16)
+    s["hact"] = hip.act_fwd(s["hpre"], 0)
+    s["br2"] = _lin_fwd(s["hact"], blk.mlp.fc2, mp, k16)
+    x2 = x1.clone()
+    hip.axpby_cols(s["br2"], x2, g=blk.ls2.gamma.detach() if hasattr(blk, "ls2") else None)
+    return s, x2, None
 
 
 def _lin_fwd(x: torch.Tensor, lin, mp: Optional[torch.dtype] = None, keep: Optional[dict] = None,
@@ -385,42 +355,15 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     sv["wsum"] = wsum                                    # the source gradient's kernel (mst_patch_embed_dgrad) reads the same sum
     xt = hip.patch_embed(vol, wsum, enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
     # ---- blocks (block.py:89-114)
-    blocks = []
-    mp = _mp(model)
-    flash = _flash(model, mp)
-    st16 = _storage16(model, mp, flash)
-    sv["mp"], sv["storage16"] = mp, st16                  # the backward reads the resolved modes from here (an autocast region may have ended)
+    mode = train_mode.resolve(model)
+    sv["mp"], sv["storage16"] = mode.mp, mode.storage16   # the backward reads the resolved mode from here (an autocast region may have ended)
     blist = list(enc.block_list())
-    if st16:
-        xn = hip.layernorm(xt, blist[0].norm1.weight.detach(), blist[0].norm1.bias.detach(), 1e-6, out_dtype=mp)
-        for i, blk in enumerate(blist):
-            s, xt, xn = _block_fwd_16(blk, blist[i + 1] if i + 1 < len(blist) else None, xt, xn, mp, n, N, heads, E)
-            blocks.append(s)
-        blist = []
-    for blk in blist:
-        s = {"x0": xt, "x16": {}}
-        k16 = s["x16"] if mp is not None else None
-        s["xn1"] = hip.layernorm(xt, blk.norm1.weight.detach(), blk.norm1.bias.detach(), 1e-6)
-        if flash:
-            # q | k | v straight in the 16-bit type the attention kernels read; kept with the output and the per-row log-sum-exp instead of
-            # the [n, heads, N, N] probabilities (the backward recomputes them per tile)
-            s["qkv16"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, out_dtype=mp, col_scale=0.125, scale_cols=E)
-            s["a"], s["lse"] = hip.attention_train_fwd(s["qkv16"], n, N, heads)
-        else:
-            s["qkv"] = _lin_fwd(s["xn1"], blk.attn.qkv, mp, k16, col_scale=0.125, scale_cols=E)        # q * head_dim^-0.5 (attention.py:60)
-            s["a"], s["P"] = _attention_fwd(s["qkv"], n, N, heads, 64, 1.0, None)
-        s["br1"] = _lin_fwd(s["a"], blk.attn.proj, mp, k16)
-        x1 = xt.clone()
-        hip.axpby_cols(s["br1"], x1, g=blk.ls1.gamma.detach() if hasattr(blk, "ls1") else None)
-        s["x1"] = x1
-        s["xn2"] = hip.layernorm(x1, blk.norm2.weight.detach(), blk.norm2.bias.detach(), 1e-6)
-        s["hpre"] = _lin_fwd(s["xn2"], blk.mlp.fc1, mp, k16)
-        s["hact"] = hip.act_fwd(s["hpre"], 0)
-        s["br2"] = _lin_fwd(s["hact"], blk.mlp.fc2, mp, k16)
-        x2 = x1.clone()
-        hip.axpby_cols(s["br2"], x2, g=blk.ls2.gamma.detach() if hasattr(blk, "ls2") else None)
+    block_fwd = _block_fwd_16 if mode.storage16 else _block_fwd
+    xn = hip.layernorm(xt, blist[0].norm1.weight.detach(), blist[0].norm1.bias.detach(), 1e-6, out_dtype=mode.mp) if mode.storage16 else None
+    blocks = []
+    for blk, nxt in zip(blist, blist[1:] + [None]):
+        s, xt, xn = block_fwd(blk, nxt, xt, xn, mode, n, N, heads, E)
         blocks.append(s)
-        xt = x2
     sv["blocks"], sv["xL"] = blocks, xt
     emb = hip.layernorm_rows(xt, N * E, n, E, enc.norm.weight.detach(), enc.norm.bias.detach(), 1e-6)     # CLS rows
     sv["emb"] = emb
@@ -568,6 +511,21 @@ def _source_grad(dvol: torch.Tensor, sv, dtype: torch.dtype, device: torch.devic
     return g.to(device=device, dtype=dtype).contiguous()
 
 
+def fp32_device_params(model) -> List[torch.nn.Parameter]:
+    """The model's parameters, the inputs of its autograd node: all fp32 on the device, or RuntimeError."""
+    params = list(model.parameters())
+    for p in params:
+        if p.dtype != torch.float32 or p.device.type != "cuda":
+            raise RuntimeError("training step: parameters must be fp32 on the MI355X (model.float().cuda()); there is no CPU fallback")
+    return params
+
+
+def route_grads(grads: Dict[int, torch.Tensor], params, needs) -> List[Optional[torch.Tensor]]:
+    """{id(param): grad} -> the node's returned gradients in `params` order; None where `needs` (needs_input_grad from the first
+    parameter on) is off or no gradient was produced."""
+    return [grads.get(id(p)) if need else None for p, need in zip(params, needs)]
+
+
 class _MSTFunction(torch.autograd.Function):
     """One autograd node for the whole model: inputs are the parameters (so that autograd, DDP hooks and optimisers see
     ordinary ``.grad`` accumulation) and the source volume, output the logits (or features)."""
@@ -588,15 +546,9 @@ class _MSTFunction(torch.autograd.Function):
             grads, dvol = backward_train(ctx.model, ctx.saved, dout.contiguous().float(), needed, need_src)
             dsrc = _source_grad(dvol, ctx.saved, ctx.src_dtype, ctx.src_device) if need_src else None
         ctx.saved = None
-        out: List[Optional[torch.Tensor]] = []
-        for p, need in zip(ctx.params, ctx.needs_input_grad[4:]):
-            out.append(grads.get(id(p)) if need else None)
-        return (None, dsrc, None, None, *out)
+        return (None, dsrc, None, None, *route_grads(grads, ctx.params, ctx.needs_input_grad[4:]))
 
 
 def forward_with_grad(model, source, mask, without_linear: bool):
-    params = [p for p in model.parameters()]
-    for p in params:
-        if p.dtype != torch.float32 or p.device.type != "cuda":
-            raise RuntimeError("training step: parameters must be fp32 on the MI355X (model.float().cuda()); there is no CPU fallback")
+    params = fp32_device_params(model)
     return _MSTFunction.apply(model, source, mask, without_linear, *params)

@@ -9,18 +9,11 @@ forward runs the model op by op through the C ABI and whose backward produces ev
      backward      dWg = dz^T . im2col(x) as an implicit GEMM too (mst_conv_wgrad: pixel-split partial products reduced by mst_colsum),
                    dx = the stride-1 convolution of the stride-dilated dz with the flipped, transposed weight (mst_conv_dgrad); the
                    stem and MST_CONV_IM2COL=1 keep the explicit forms (mst_im2col_nhwc + mst_gemm_ex, mst_col2im_nhwc)
-     16-bit        train_precision = bf16 / fp16 (the reference's Trainer(precision='16-mixed')): the three products on 16-bit MFMA
-                   operands with fp32 accumulation (mst_conv_gemm16, mst_conv_dgrad, mst_conv_wgrad16); everything else and all
-                   stored tensors fp32
+     16-bit        a 16-bit train_precision: the three products on 16-bit MFMA operands with fp32 accumulation (mst_conv_gemm16,
+                   mst_conv_dgrad, mst_conv_wgrad16)
   BatchNorm2d      batch statistics + running-stat update (mst_batchnorm_train), residual add and ReLU in the same pass
      backward      mst_batchnorm_bwd (ReLU mask first: mst_act_bwd on the saved output)
-     16-bit stored train_storage = '16bit' (opt-in, needs a 16-bit train_precision; csrc/k_bn16.hip): z and y of every unit live in that type,
-                   as the reference's autocast keeps them.  A unit takes its input in T, writes z in T (mst_conv_gemm16) and y in T
-                   (mst_batchnorm_train16); that y IS the next unit's convolution operand, the operand of its weight gradient and the
-                   residual of the unit that closes the block, so the record holds z, y (ReLU units), the [C] statistics and a reference
-                   to the caller's input -- no fp32 activation, no second 16-bit copy.  Backward: ONE mst_batchnorm_bwd16 per unit (ReLU
-                   mask, both sums, dz rounded to T, the masked dy for the shortcut).  The gradient stream (dy, dx, shortcut sums), the
-                   weight-gradient partials, the slice transformer and the head stay fp32.  Its BatchNorm sums are fixed-order always.
+     16-bit stored train_storage='16bit' (csrc/k_bn16.hip): mst_batchnorm_train16, ONE mst_batchnorm_bwd16 per unit
   max / avg pool   mst_maxpool_bwd_nhwc / mst_avgpool_bwd_nhwc
   slice fusion     mst.train.fusion_fwd / fusion_bwd with 16 heads over 512-wide tokens
 
@@ -28,10 +21,8 @@ BatchNorm in train mode normalises over ALL (B D) images of the step, so the ste
 resident (fp32 NHWC; about 60 MB per 224^2 image for resnet34 -- sized for 288 GB of HBM; the mixed mode keeps a 16-bit image of every
 convolution input beside it).  Checked against torch.autograd of oracle/resnet_oracle.py on every parameter (tests/test_resnet_gpu.py).
 
-Autocast: a model whose train_precision was given neither by keyword nor by MST_TRAIN_PRECISION follows an enabled CUDA autocast region of
-fp16 / bf16 around the forward (mst.train._mp, the rule of DinoV2ClassifierSlice); an explicit value, 'fp32' included, is never overridden
-and train_storage is never inferred.  The resolved type and the storage mode travel in the saved state: backward() may run after the
-region has ended.
+The mode (train_precision, train_storage and the autocast rule) is described, validated and resolved in mst/train_mode.py;
+`forward_train` resolves it once and the saved state and every unit's record carry it to the backward.
 
 Determinism: under ``torch.use_deterministic_algorithms(True)`` (read at every call) the BatchNorm statistics and their gradients
 (mst_batchnorm_train_ordered / mst_batchnorm_bwd_ordered), the weight-gradient partial sums (mst_colsum_ordered), col2im and the max-pool
@@ -41,14 +32,14 @@ loss, gradients, running statistics -- is bit-reproducible.  Flag off: the atomi
 from __future__ import annotations
 
 import os
-from typing import List, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, train_mode
 from .models.resnet import _conv
-from .train import _Grads, _mp, fusion_bwd, fusion_fwd
+from .train import _Grads, fp32_device_params, fusion_bwd, fusion_fwd, route_grads
 
 
 def _gemm_weight(conv, sum_in: bool) -> torch.Tensor:
@@ -64,69 +55,45 @@ def _gemm_weight(conv, sum_in: bool) -> torch.Tensor:
     return w.contiguous()
 
 
-def _conv_bn_fwd16(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_in: bool, residual: Optional[torch.Tensor], relu: bool,
-                   mp: torch.dtype):
-    """The unit in train_storage='16bit': x [n,H,W,Cin] ALREADY in mp (the producer's y; the stem: the fp32 source images), residual
-    [rows, Cout] in mp -> y [n,Ho,Wo,Cout] in mp.  The record keeps z and y (ReLU units) in mp and a reference to x: nothing fp32 but the
-    [C] statistics, no copy of the input."""
+def _conv_bn_fwd(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_in: bool, residual: Optional[torch.Tensor],
+                 relu: bool, mp: Optional[torch.dtype] = None, storage16: bool = False):
+    """x [n,H,W,C] -> y [n,Ho,Wo,Cout] plus the record the backward needs.  mp (a 16-bit train_precision): the convolution and its two
+    gradients on 16-bit MFMA operands (fp32 accumulation) -- the reference's Trainer(precision='16-mixed') for F.conv2d.  A unit that
+    cannot take them runs in fp32 and records mp = None.  storage16 (train_storage='16bit', needs mp): x ALREADY in mp (the producer's y;
+    the stem: the fp32 source images), residual [rows, Cout] in mp, z and y in mp; the record then keeps nothing fp32 but the [C]
+    statistics and no copy of the input, and a unit that cannot take the 16-bit products is a ValueError."""
+    if storage16 and mp is None:
+        train_mode.check(False, "stored", "16bit", needs_flash=False)        # raises: 16-bit storage without a 16-bit type
     n, H, W, Cin = x.shape
     wg = _gemm_weight(conv, sum_in)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     Cout, K = wg.shape[0], k * k * Cin
-    col16 = None
-    if x.dtype == mp and Cin % 64 == 0 and Cout % 64 == 0:
-        z = hip.conv_gemm16(x, hip.cvt16(wg[:, :K].contiguous(), mp), None, k, k, stride, pad, epilogue=hip.EPI_BIAS, out_dtype=mp)
-    elif x.dtype == torch.float32 and Cout % 64 == 0:
-        # the stem (fp32 source images; 49 taps after the gray fold, 147 for three channels): its 16-bit im2col rows, padded to a multiple
-        # of 64 columns, are the "pixels" of a 1 x 1 convolution -- for the forward and for the weight gradient
+    zdt = mp if storage16 else torch.float32
+    x16 = col16 = None
+    if mp is not None and Cin % 64 == 0 and Cout % 64 == 0 and (x.dtype == mp or not storage16):
+        # the operand image: x itself, or a 16-bit copy kept for the weight gradient (a third of the step's conversions otherwise)
+        x16 = x if storage16 else hip.cvt16(x.view(-1, Cin), mp).view(x.shape)
+        z = hip.conv_gemm16(x16, hip.cvt16(wg, mp), None, k, k, stride, pad, epilogue=hip.EPI_BIAS, out_dtype=zdt)
+    elif mp is not None and Cout % 64 == 0 and x.dtype == torch.float32 and (storage16 or K <= 64):
+        # the stem (49 taps after the gray fold; with 16-bit storage also the 147 of three channels, which fp32 storage leaves to the fp32
+        # implicit GEMM): its im2col rows, rounded on the way out and padded to a multiple of 64 columns, are the "pixels" of a 1 x 1
+        # convolution -- for the forward and for the weight gradient (no fp32 im2col matrix, no strided fp32 GEMM)
         kp = (K + 63) // 64 * 64
         w64 = torch.zeros((Cout, kp), dtype=torch.float32, device=x.device)
         w64[:, :K] = wg[:, :K]
         col16 = hip.im2col_nhwc(x, k, k, stride, pad, kp, out_dtype=mp).view(n * Ho * Wo, 1, 1, kp)
-        z = hip.conv_gemm16(col16, hip.cvt16(w64, mp), None, 1, 1, 1, 0, epilogue=hip.EPI_BIAS, out_dtype=mp)
-    else:
+        z = hip.conv_gemm16(col16, hip.cvt16(w64, mp), None, 1, 1, 1, 0, epilogue=hip.EPI_BIAS, out_dtype=zdt)
+    elif storage16:
         raise ValueError(f"train_storage='16bit': a {k} x {k} convolution {Cin} -> {Cout} on a {x.dtype} input cannot take the 16-bit products "
                          "(behind the stem Cin and Cout must be multiples of 64 and the input already in the 16-bit type)")
-    y, mean, rstd = hip.batchnorm_train16(z, bn, residual, relu)
-    bn.num_batches_tracked += 1
-    rec = {"x": x, "z": z, "y": y if relu else None, "mean": mean, "rstd": rstd, "k": k, "stride": stride, "pad": pad, "sum_in": sum_in,
-           "relu": relu, "conv": conv, "bn": bn, "mp": mp, "col16": col16, "storage16": True}
-    return y.view(n, Ho, Wo, Cout), rec
-
-
-def _conv_bn_fwd(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_in: bool, residual: Optional[torch.Tensor],
-                 relu: bool, mp: Optional[torch.dtype] = None, storage16: bool = False):
-    """x [n,H,W,C] -> y [n,Ho,Wo,Cout] plus the record the backward needs.  mp (train_precision bf16 / fp16): the convolution and its
-    two gradients on 16-bit MFMA operands (fp32 accumulation; activations, BatchNorm and everything stored stay fp32) --
-    the reference's Trainer(precision='16-mixed') for F.conv2d.  storage16 (train_storage='16bit', needs mp): _conv_bn_fwd16."""
-    if storage16:
-        if mp is None:
-            raise ValueError("train_storage='16bit' needs train_precision 'bf16' or 'fp16' (the saved tensors are the 16-bit operands of the "
-                             "mixed-precision kernels)")
-        return _conv_bn_fwd16(x, conv, bn, k, stride, pad, sum_in, residual, relu, mp)
-    n, H, W, Cin = x.shape
-    wg = _gemm_weight(conv, sum_in)
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    Cout = wg.shape[0]
-    x16 = col16 = None
-    if mp is not None and Cin % 64 == 0 and Cout % 64 == 0:
-        x16 = hip.cvt16(x.view(-1, Cin), mp).view(x.shape)               # kept for the weight gradient (a third of the step's conversions otherwise)
-        z = hip.conv_gemm16(x16, hip.cvt16(wg, mp), None, k, k, stride, pad, epilogue=hip.EPI_BIAS, out_dtype=torch.float32)
-    elif mp is not None and Cout % 64 == 0 and k * k * Cin <= 64:
-        # the stem (one input channel after the gray fold: 49 taps): its im2col rows, rounded on the way out and padded to 64 columns, are the
-        # "pixels" of a 1 x 1 convolution -- for the forward and for the weight gradient (no fp32 im2col matrix, no strided fp32 GEMM)
-        w64 = torch.zeros((Cout, 64), dtype=torch.float32, device=x.device)
-        w64[:, :k * k * Cin] = wg[:, :k * k * Cin]
-        col16 = hip.im2col_nhwc(x, k, k, stride, pad, 64, out_dtype=mp).view(n * Ho * Wo, 1, 1, 64)
-        z = hip.conv_gemm16(col16, hip.cvt16(w64, mp), None, 1, 1, 1, 0, epilogue=hip.EPI_BIAS, out_dtype=torch.float32)
     else:
         mp = None
         z = _conv(x, wg, None, k, stride, pad, wg.shape[1], hip.EPI_BIAS)    # implicit GEMM behind the stem
-    y, mean, rstd = hip.batchnorm_train(z, bn, residual, relu)
+    y, mean, rstd = (hip.batchnorm_train16 if storage16 else hip.batchnorm_train)(z, bn, residual, relu)
     bn.num_batches_tracked += 1
-    rec = {"x": x, "z": z, "y": y if relu else None, "mean": mean, "rstd": rstd, "wg": wg, "k": k, "stride": stride, "pad": pad,
-           "sum_in": sum_in, "relu": relu, "conv": conv, "bn": bn, "mp": mp, "x16": x16, "col16": col16}
-    return y.view(n, Ho, Wo, wg.shape[0]), rec
+    rec = {"x": x, "z": z, "y": y if relu else None, "mean": mean, "rstd": rstd, "wg": None if storage16 else wg, "k": k, "stride": stride,
+           "pad": pad, "sum_in": sum_in, "relu": relu, "conv": conv, "bn": bn, "mp": mp, "x16": x16, "col16": col16, "storage16": storage16}
+    return y.view(n, Ho, Wo, Cout), rec
 
 
 def _split(n: int, hw: int):
@@ -137,62 +104,40 @@ def _split(n: int, hw: int):
     return n, s2
 
 
-def _conv_bn_bwd16(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool) -> Optional[torch.Tensor]:
-    """The unit's backward on a train_storage='16bit' record: ONE BatchNorm call (ReLU mask from the saved y, d gamma / d beta, dz rounded
-    to the 16-bit type, dy <- masked dy when mask_dy), then the two 16-bit products on dz and the record's own tensors."""
-    x, z, mp = rec["x"], rec["z"], rec["mp"]
-    conv, bn = rec["conv"], rec["bn"]
-    k, stride, pad = rec["k"], rec["stride"], rec["pad"]
-    n, H, W, Cin = x.shape
-    rows, Cout = z.shape
-    dz16, dg, db = hip.batchnorm_bwd16(z, rec["y"], rec["mean"], rec["rstd"], bn.weight.detach(), dy, mask_dy and rec["relu"])
-    G.put(bn.weight, dg)
-    G.put(bn.bias, db)
-    K = k * k * Cin
-    if rec["col16"] is not None:                                         # the stem: d weight over its 16-bit im2col "pixels"
-        dwg = hip.conv_wgrad(dz16, rec["col16"], 1, 1, 0)
-    else:
-        dwg = hip.conv_wgrad(dz16, x, k, stride, pad)                    # x IS the producer's 16-bit output
-    dw = dwg[:, :K].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
-    if rec["sum_in"]:
-        dw = dw.expand(Cout, conv.weight.shape[1], k, k)
-    G.put(conv.weight, dw.contiguous())
-    if not need_dx:
-        return None
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    return hip.conv_dgrad(dz16.view(n, Ho, Wo, Cout), hip.conv_dgrad_weight(conv.weight, mp), k, stride, pad, H, W)
-
-
 def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool = True) -> Optional[torch.Tensor]:
-    """dy [rows, Cout] = gradient of the unit's output (modified in place by the ReLU mask).  Returns dx [n,H,W,C] or None.  The
-    caller routes the masked dy to the residual branch itself.  mask_dy=False (train_storage='16bit' records only): nobody reads the
-    masked dy, so it is not written back."""
-    if rec.get("storage16"):
-        return _conv_bn_bwd16(G, rec, dy, need_dx, mask_dy)
-    x, z, wg = rec["x"], rec["z"], rec["wg"]
+    """dy [rows, Cout] = gradient of the unit's output.  Returns dx [n,H,W,C] or None.  The caller routes the masked dy to the residual
+    branch itself: fp32 storage always writes the ReLU mask into dy; 16-bit storage does so only with mask_dy (False: nobody reads the
+    masked dy) and leaves the dy of a unit without ReLU alone."""
+    x, z, wg, mp, st16 = rec["x"], rec["z"], rec["wg"], rec["mp"], rec["storage16"]
     conv, bn = rec["conv"], rec["bn"]
     k, stride, pad = rec["k"], rec["stride"], rec["pad"]
     n, H, W, Cin = x.shape
     rows, Cout = z.shape
-    kpad = wg.shape[1]
     dev = z.device
-    if rec["relu"]:
-        hip.act_bwd(rec["y"], dy, 1)
-    dz, dg, db = hip.batchnorm_bwd(z, rec["mean"], rec["rstd"], bn.weight.detach(), dy)
+    if st16:                                                             # ONE pass: ReLU mask from the saved y, both sums, dz rounded to mp
+        dz = None
+        dz16, dg, db = hip.batchnorm_bwd16(z, rec["y"], rec["mean"], rec["rstd"], bn.weight.detach(), dy, mask_dy and rec["relu"])
+    else:
+        if rec["relu"]:
+            hip.act_bwd(rec["y"], dy, 1)
+        dz, dg, db = hip.batchnorm_bwd(z, rec["mean"], rec["rstd"], bn.weight.detach(), dy)
+        dz16 = hip.cvt16(dz, mp) if mp is not None else None            # shared by the two gradients
     G.put(bn.weight, dg)
     G.put(bn.bias, db)
-    implicit = os.environ.get("MST_CONV_IM2COL", "0") != "1"
+    implicit = st16 or os.environ.get("MST_CONV_IM2COL", "0") != "1"    # the explicit im2col / col2im forms are fp32 storage's
     col = None
-    mp = rec["mp"]
-    dz16 = hip.cvt16(dz, mp) if mp is not None else None                # shared by the two gradients
-    if mp is not None and rec["col16"] is not None:                      # the stem under mixed precision: d weight over its 16-bit im2col "pixels"
-        dwg = torch.zeros((Cout, kpad), dtype=torch.float32, device=dev)
-        dwg[:, :min(kpad, 64)] = hip.conv_wgrad(dz16, rec["col16"], 1, 1, 0)[:, :min(kpad, 64)]
-    elif implicit and mp is not None and rec["x16"] is not None:
+    if rec["col16"] is not None:                                         # the stem's 16-bit product: d weight over its 16-bit im2col "pixels"
+        dwg = hip.conv_wgrad(dz16, rec["col16"], 1, 1, 0)
+        if not st16:                                                     # fp32 storage hands on a [Cout, kpad] matrix like its other forms
+            kpad, dwg64 = wg.shape[1], dwg
+            dwg = torch.zeros((Cout, kpad), dtype=torch.float32, device=dev)
+            dwg[:, :min(kpad, 64)] = dwg64[:, :min(kpad, 64)]
+    elif implicit and rec["x16"] is not None:
         dwg = hip.conv_wgrad(dz16, rec["x16"], k, stride, pad)           # 16-bit operands (the forward's image of x), fp32 partial products
     elif implicit and Cin % 64 == 0 and Cout % 4 == 0:
         dwg = hip.conv_wgrad(dz, x, k, stride, pad)                      # implicit GEMM: no im2col matrix
     else:
+        kpad = wg.shape[1]
         col = hip.im2col_nhwc(x, k, k, stride, pad, kpad)
         hw = rows // n
         s1, s2 = _split(n, hw)
@@ -201,25 +146,32 @@ def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool 
         hip.gemm_ex(dz, col, part, Cout, kpad, ch, sa=(1, Cout), sb=(kpad, 1), sc=(kpad, 1), nb=(s1, s2), ba=(hw * Cout, ch * Cout),
                     bb=(hw * kpad, ch * kpad), bc=(s2 * Cout * kpad, Cout * kpad))
         dwg = hip.colsum(part, torch.zeros(Cout * kpad, dtype=torch.float32, device=dev)).view(Cout, kpad)
-    K = k * k * Cin
-    dw = dwg[:, :K].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
+    dw = dwg[:, :k * k * Cin].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
     if rec["sum_in"]:
         dw = dw.expand(Cout, conv.weight.shape[1], k, k)                  # w_eff = sum over the identical input channels
     G.put(conv.weight, dw.contiguous())
     if not need_dx:
         return None
-    if Cout % 16 == 0 and Cin % 4 == 0 and stride in (1, 2) and implicit:
+    if st16 or (implicit and Cout % 16 == 0 and Cin % 4 == 0 and stride in (1, 2)):
         # d input as a convolution of dz with the flipped, transposed weight (mst_conv_dgrad): no gradient matrix, no atomics
         del col
         Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        if mp is not None:
-            return hip.conv_dgrad(dz16.view(n, Ho, Wo, Cout), hip.conv_dgrad_weight(conv.weight, mp), k, stride, pad, H, W)
-        return hip.conv_dgrad(dz.view(n, Ho, Wo, Cout), hip.conv_dgrad_weight(conv.weight), k, stride, pad, H, W)
+        g = dz if mp is None else dz16
+        return hip.conv_dgrad(g.view(n, Ho, Wo, Cout), hip.conv_dgrad_weight(conv.weight, g.dtype), k, stride, pad, H, W)
+    kpad = wg.shape[1]
     if col is None:
         col = torch.empty((rows, kpad), dtype=torch.float32, device=dev)
     hip.gemm_ex(dz, wg, col, rows, kpad, Cout, sa=(Cout, 1), sb=(kpad, 1), sc=(kpad, 1))      # dcol overwrites col
     dx = torch.zeros_like(x)
     return hip.col2im_nhwc(col, dx, k, k, stride, pad)
+
+
+def _shortcut(y: torch.Tensor, blk, mp: Optional[torch.dtype], storage16: bool):
+    """The residual operand [rows, C] of the unit that closes `blk`, and the downsample unit's record (None: the identity)."""
+    rd = None
+    if hasattr(blk, "downsample"):
+        y, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp, storage16)
+    return y.reshape(-1, y.shape[-1]), rd
 
 
 def backbone_fwd(m, x_nhwc: torch.Tensor, sum_in: bool, mp: Optional[torch.dtype] = None, storage16: bool = False):
@@ -231,28 +183,17 @@ def backbone_fwd(m, x_nhwc: torch.Tensor, sum_in: bool, mp: Optional[torch.dtype
     y = hip.maxpool_nhwc(y)
     for li in range(4):
         for blk in getattr(m, f"layer{li + 1}"):
-            n, H, W, Cin = y.shape
             if hasattr(blk, "conv3"):                                    # bottleneck: 1x1 -> 3x3 (stride) -> 1x1 + residual
                 h0, r0 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 1, 1, 0, False, None, True, mp, storage16)
                 h1, r1 = _conv_bn_fwd(h0, blk.conv2, blk.bn2, 3, blk.stride, 1, False, None, True, mp, storage16)
-                rd = None
-                if hasattr(blk, "downsample"):
-                    idt, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp, storage16)
-                    idt = idt.reshape(-1, idt.shape[-1])
-                else:
-                    idt = y.reshape(n * H * W, Cin)
+                idt, rd = _shortcut(y, blk, mp, storage16)
                 y, r2 = _conv_bn_fwd(h1, blk.conv3, blk.bn3, 1, 1, 0, False, idt, True, mp, storage16)
                 sv["units"].append((r0, r2, rd, r1))
-                continue
-            h1, r1 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 3, blk.stride, 1, False, None, True, mp, storage16)
-            rd = None
-            if hasattr(blk, "downsample"):
-                idt, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp, storage16)
-                idt = idt.reshape(-1, idt.shape[-1])
-            else:
-                idt = y.reshape(n * H * W, Cin)
-            y, r2 = _conv_bn_fwd(h1, blk.conv2, blk.bn2, 3, 1, 1, False, idt, True, mp, storage16)
-            sv["units"].append((r1, r2, rd, None))
+            else:                                                        # basic: 3x3 (stride) -> 3x3 + residual
+                h1, r1 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 3, blk.stride, 1, False, None, True, mp, storage16)
+                idt, rd = _shortcut(y, blk, mp, storage16)
+                y, r2 = _conv_bn_fwd(h1, blk.conv2, blk.bn2, 3, 1, 1, False, idt, True, mp, storage16)
+                sv["units"].append((r1, r2, rd, None))
     sv["last"] = y
     return hip.avgpool_nhwc(y), sv
 
@@ -267,7 +208,7 @@ def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor):
             dh1 = _conv_bn_bwd(G, rmid, dh1.view(-1, dh1.shape[-1]), True, False)
         xin = r1["x"]
         if rd is not None:
-            dx = _conv_bn_bwd(G, rd, dy if rd.get("storage16") else dy.clone(), True)    # (the 16-bit form leaves a unit without ReLU's dy alone)
+            dx = _conv_bn_bwd(G, rd, dy if rd["storage16"] else dy.clone(), True)    # (the 16-bit form leaves a unit without ReLU's dy alone)
         else:
             dx = dy.view(xin.shape).clone()
         d1 = _conv_bn_bwd(G, r1, dh1.view(-1, dh1.shape[-1]), True, False)
@@ -278,22 +219,10 @@ def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor):
 
 
 # ---- whole models ------------------------------------------------------------------------------------------------------
-def _storage16(model, mp: Optional[torch.dtype]) -> bool:
-    """train_storage of the backbone: 'fp32' (default) or '16bit'; the latter needs a 16-bit operand type.  Re-checked at every call (the
-    attributes may have been changed after construction); never inferred from an autocast region."""
-    ts = getattr(model, "train_storage", "fp32")
-    if ts not in ("fp32", "16bit"):
-        raise ValueError(f"train_storage must be 'fp32' or '16bit' (got {ts!r})")
-    if ts == "16bit" and mp is None:
-        raise ValueError("train_storage='16bit' needs train_precision 'bf16' or 'fp16' (the saved tensors are the 16-bit operands of the "
-                         "mixed-precision kernels)")
-    return ts == "16bit"
-
-
 def forward_train(model, x_nhwc: torch.Tensor, sum_in: bool, B: Optional[int], D: Optional[int], mask: Optional[torch.Tensor]):
     """B/D given: ResNetSliceTrans (features -> slice transformer -> linear); else plain ResNet (features -> fc)."""
-    mp = _mp(model)                                      # train_precision, or the enclosing autocast region's type for a defaulted model
-    feat, sv = backbone_fwd(model.model, x_nhwc, sum_in, mp, _storage16(model, mp))
+    mode = train_mode.resolve(model)
+    feat, sv = backbone_fwd(model.model, x_nhwc, sum_in, mode.mp, mode.storage16)
     sv["feat"] = feat
     if B is None:
         fc = model.model.fc
@@ -333,16 +262,10 @@ class _ResNetFunction(torch.autograd.Function):
         with torch.no_grad():
             grads = backward_train(ctx.model, ctx.saved, dout.contiguous().float())
         ctx.saved = None
-        out: List[Optional[torch.Tensor]] = []
-        for p, need in zip(ctx.params, ctx.needs_input_grad[6:]):
-            out.append(grads.get(id(p)) if need else None)
-        return (None, None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, *route_grads(grads, ctx.params, ctx.needs_input_grad[6:]))
 
 
 def forward_with_grad(model, x_nhwc, sum_in: bool, B=None, D=None, mask=None):
     model._invalidate()                                  # a training step follows: the BatchNorm-folded inference weights are stale after it
-    params = [p for p in model.parameters()]
-    for p in params:
-        if p.dtype != torch.float32 or p.device.type != "cuda":
-            raise RuntimeError("training step: parameters must be fp32 on the MI355X (model.float().cuda()); there is no CPU fallback")
+    params = fp32_device_params(model)
     return _ResNetFunction.apply(model, x_nhwc, sum_in, B, D, mask, *params)

@@ -64,34 +64,34 @@ def test_bad_combinations_raise(build, kw):
 
 
 def test_the_step_rechecks_attributes_changed_after_construction():
-    from mst import train, train_resnet
+    from mst.train_mode import check, resolve
     m = _slice(train_precision="fp16", train_storage="16bit")
-    assert train_resnet._storage16(m, train._mp(m)) is True
+    assert resolve(m).storage16 is True
     m.train_precision = "fp32"
     with pytest.raises(ValueError, match="train_storage"):
-        train_resnet._storage16(m, train._mp(m))
+        resolve(m)
     m.train_precision, m.train_storage = "bf16", "8bit"
     with pytest.raises(ValueError, match="train_storage"):
-        train_resnet._storage16(m, train._mp(m))
+        resolve(m)
     m.train_storage = "fp32"
-    assert train_resnet._storage16(m, train._mp(m)) is False
-    assert train_resnet._storage16(m, None) is False
+    assert resolve(m).storage16 is False
+    assert check(False, "stored", m.train_storage, needs_flash=False) == (False, False)     # (no 16-bit type: the arguments by hand)
 
 
 @pytest.mark.parametrize("build", [_slice, _plain])
 def test_whether_train_precision_was_given_is_recorded(build, monkeypatch):
     """The autocast rule applies to a defaulted train_precision only; the attribute still reads 'fp32' then, and outside a region every
     model resolves to its own value."""
-    from mst import train
+    from mst.train_mode import resolve
     m = build()
-    assert m.train_precision == "fp32" and m._train_precision_given is False and train._mp(m) is None
+    assert m.train_precision == "fp32" and m._train_precision_given is False and resolve(m).mp is None
     assert build(train_precision="fp32")._train_precision_given is True
     assert build(train_precision="bf16")._train_precision_given is True
     monkeypatch.setenv("MST_TRAIN_PRECISION", "fp32")
     assert build()._train_precision_given is True
     monkeypatch.setenv("MST_TRAIN_PRECISION", "fp16")
     m = build()
-    assert m._train_precision_given is True and train._mp(m) is torch.float16
+    assert m._train_precision_given is True and resolve(m).mp is torch.float16
 
 
 def test_the_unit_refuses_16_bit_storage_without_a_16_bit_type():

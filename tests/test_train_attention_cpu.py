@@ -39,18 +39,18 @@ def test_bad_combinations_raise(monkeypatch, kw):
 
 
 def test_the_step_rechecks_attributes_changed_after_construction(monkeypatch):
-    from mst import train
+    from mst.train_mode import resolve
     monkeypatch.delenv("MST_TRAIN_ATTENTION", raising=False)
     m = _model(train_precision="fp16", train_attention="flash")
-    assert train._flash(m, train._mp(m)) is True
+    assert resolve(m).flash is True
     m.train_precision = "fp32"
     with pytest.raises(ValueError, match="train_precision"):
-        train._flash(m, train._mp(m))
+        resolve(m)
     m.train_precision, m.train_attention = "bf16", "paged"
     with pytest.raises(ValueError):
-        train._flash(m, train._mp(m))
+        resolve(m)
     m.train_attention = "stored"
-    assert train._flash(m, train._mp(m)) is False
+    assert resolve(m).flash is False
 
 
 def test_wrappers_refuse_host_tensors():

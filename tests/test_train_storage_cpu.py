@@ -49,37 +49,37 @@ def test_bad_combinations_raise(kw):
 
 
 def test_the_step_rechecks_attributes_changed_after_construction():
-    from mst import train
+    from mst.train_mode import check, resolve
     m = _model(train_precision="fp16", train_attention="flash", train_storage="16bit")
-    mp = train._mp(m)
-    assert train._storage16(m, mp, train._flash(m, mp)) is True
+    assert resolve(m).storage16 is True
     m.train_attention = "stored"
-    mp = train._mp(m)
     with pytest.raises(ValueError, match="train_storage"):
-        train._storage16(m, mp, train._flash(m, mp))
+        resolve(m)
     m.train_attention, m.train_storage = "flash", "8bit"
     with pytest.raises(ValueError, match="train_storage"):
-        train._storage16(m, mp, True)
+        resolve(m)
     m.train_storage, m.train_precision = "16bit", "fp32"
     with pytest.raises(ValueError):
-        train._storage16(m, train._mp(m), True)
+        resolve(m)
+    with pytest.raises(ValueError, match="train_storage"):
+        check(False, "stored", m.train_storage, needs_flash=True)                  # the storage check itself, arguments by hand
     m.train_storage = "fp32"
-    assert train._storage16(m, None, False) is False
+    assert check(False, "stored", m.train_storage, needs_flash=True) == (False, False)      # (no 16-bit type, not flash: the arguments by hand)
 
 
 def test_whether_train_precision_was_given_is_recorded(monkeypatch):
     """The autocast rule applies to a defaulted train_precision only; the attribute still reads 'fp32' then.  Outside an autocast region
     every model resolves to its own value."""
-    from mst import train
+    from mst.train_mode import resolve
     m = _model()
-    assert m.train_precision == "fp32" and m._train_precision_given is False and train._mp(m) is None
+    assert m.train_precision == "fp32" and m._train_precision_given is False and resolve(m).mp is None
     assert _model(train_precision="fp32")._train_precision_given is True
     assert _model(train_precision="bf16")._train_precision_given is True
     monkeypatch.setenv("MST_TRAIN_PRECISION", "fp32")
     assert _model()._train_precision_given is True
     monkeypatch.setenv("MST_TRAIN_PRECISION", "fp16")
     m = _model()
-    assert m._train_precision_given is True and train._mp(m) is torch.float16
+    assert m._train_precision_given is True and resolve(m).mp is torch.float16
 
 
 def test_wrappers_refuse_host_tensors_and_wrong_types():

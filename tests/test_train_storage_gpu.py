@@ -409,6 +409,19 @@ def test_a_defaulted_model_follows_the_autocast_region(prec, monkeypatch):
     assert any(not torch.equal(inside[1][k], full[1][k]) for k in full[1])
 
 
+def test_the_resolver_inside_an_autocast_region(monkeypatch):
+    """train_mode.resolve alone (torch opens no CUDA autocast region without a device, so this is not a CPU test): a defaulted model takes
+    the region's type and nothing else, a model built with train_precision='fp32' does not."""
+    from mst.train_mode import TrainMode, resolve
+    for name in ("MST_TRAIN_PRECISION", "MST_TRAIN_ATTENTION", "MST_TRAIN_STORAGE"):
+        monkeypatch.delenv(name, raising=False)
+    defaulted, given = _plain()(), _plain(train_precision="fp32")()
+    with torch.autocast("cuda", torch.bfloat16):
+        assert resolve(defaulted) == TrainMode(mp=torch.bfloat16, flash=False, storage16=False)
+        assert resolve(given).mp is None
+    assert resolve(defaulted).mp is None                                           # nothing changes outside a region
+
+
 def test_an_explicit_fp32_model_ignores_the_autocast_region(monkeypatch):
     monkeypatch.delenv("MST_TRAIN_PRECISION", raising=False)
     src = synth.synth_volume((1, 1, 2, 224, 224), 3).cuda()
