@@ -20,12 +20,12 @@ namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand per stage
-// TN: the N extent of the tile, 128 (default) or 64.  64 halves a workgroup's work and doubles the grid: taken when the 128-wide grid
-// would leave CUs idle (a few thousand token rows against N = 384: 99 workgroups on 256 CUs), wave tile 64 x 32.
+// Stages of the LDS ring: a double buffer, the K-loop waits for the one stage in flight.  A 4-stage ring behind a COUNTED vmcnt (the newer
+// stages stay in flight) for the one-workgroup-per-CU grids of TN = 64 was measured: 0.994 vs 0.992 ms per 16 x 224^2 forward -- no gain.
+constexpr int NS = 2;
 
-// NS: stages of the LDS ring (2 = double buffer, what every launch uses).  A 4-stage ring behind a COUNTED vmcnt (the newer stages stay in
-// flight) for the one-workgroup-per-CU grids of TN = 64 was measured: 0.994 vs 0.992 ms per 16 x 224^2 forward -- no gain, not dispatched.
-template <typename T, int EPI, typename OutT, int TN = 128, int NS = 2>
+// TN: the N extent of the tile, 128 (default) or 64.  64 halves a workgroup's work and doubles the grid (wave tile 64 x 32): gemm16_route.
+template <typename T, int EPI, typename OutT, int TN = 128>
 __global__ __launch_bounds__(256) void gemm16_kernel(const T* __restrict__ A, int64_t lda,
                                                      const T* __restrict__ W, int64_t ldw,
                                                      const float* __restrict__ bias, OutT* C,
@@ -98,10 +98,7 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const T* __restrict__ A, in
     for (int p = 0; p < NS - 1; ++p)
         if (p < nk) stage(p);
     for (int t = 0; t < nk; ++t) {
-        // stage t has landed once at most the NS - 2 stages behind it are outstanding (LDS-DMA completes in issue order); near the
-        // end fewer are in flight: wait for everything
-        if (NS > 2 && t + NS - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * (4 + NI)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stage t has landed (the only one in flight)
         __syncthreads();  // stage t is visible to every wave; every wave is done reading the buffer the next stage overwrites
         if (t + NS - 1 < nk) stage((t + NS - 1) % NS);
         const char* Ab = As + (t % NS) * TILE_BYTES;
@@ -180,109 +177,118 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const T* __restrict__ A, in
     else epilogue(std::false_type{});
 }
 
-template <typename T, int EPI, typename OutT>
-int launch_t(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
-             int64_t ldc, int64_t M, int N, int K, const float* gamma, float col_scale, int scale_cols,
-             hipStream_t s) {
-    const int tiles_m = (int)((M + BM - 1) / BM);
-    if (tiles_m * (N / BN) < 224) {          // the 128-wide grid would leave CUs idle: 128 x 64 tiles, twice the workgroups
-        const int tiles_n = N / 64, nwg = tiles_m * tiles_n;
-        static mst_lds_once lds_once_n;
-        auto kern = gemm16_kernel<T, EPI, OutT, 64, 2>;
-        constexpr int lds = 2 * TILE_BYTES + 2 * 64 * BK * 2;
-        mst_allow_lds((const void*)kern, lds, &lds_once_n);
-        kern<<<dim3(nwg), dim3(256), lds, s>>>((const T*)A, lda, (const T*)W, ldw, bias, (OutT*)C, ldc, (int)M, N, K, gamma, col_scale,
-                                                scale_cols, tiles_n, nwg, 0);
-        return mst_check_launch("gemm16 (128 x 64)");
+// The 128 x 128 kernel (narrow: its 128 x 64 form) for every epilogue and both output types; the residual one is fp32 read-modify-write.
+struct tile_launcher {
+    bool narrow;
+    template <typename T, int EPI, typename OutT> static constexpr bool has() {
+        constexpr bool t16 = std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value, f32out = std::is_same<OutT, float>::value;
+        return t16 && (EPI == MST_EPI_RESIDUAL ? f32out : EPI <= MST_EPI_BIAS_RELU && (f32out || std::is_same<OutT, T>::value));
     }
-    static mst_lds_once lds_once;
-    auto kern = gemm16_kernel<T, EPI, OutT>;
-    mst_allow_lds((const void*)kern, 4 * TILE_BYTES, &lds_once);
-    const int tiles_n = N / BN;
-    const int nwg = tiles_m * tiles_n;
-    kern<<<dim3(nwg), dim3(256), 4 * TILE_BYTES, s>>>((const T*)A, lda, (const T*)W, ldw, bias, (OutT*)C, ldc,
-                                                       (int)M, N, K, gamma, col_scale, scale_cols, tiles_n, nwg, 0);
-    return mst_check_launch("gemm16");
-}
+    template <typename T, int EPI, typename OutT> int launch(const gemm_args& g) const {
+        const int tiles_m = (int)((g.M + BM - 1) / BM);
+        if (narrow) {
+            const int tiles_n = g.N / 64, nwg = tiles_m * tiles_n;
+            static mst_lds_once lds_once_n;
+            auto kern = gemm16_kernel<T, EPI, OutT, 64>;
+            constexpr int lds = 2 * TILE_BYTES + 2 * 64 * BK * 2;
+            mst_allow_lds((const void*)kern, lds, &lds_once_n);
+            kern<<<dim3(nwg), dim3(256), lds, g.s>>>((const T*)g.A, g.lda, (const T*)g.W, g.ldw, g.bias, (OutT*)g.C, g.ldc, (int)g.M, g.N, g.K,
+                                                      g.gamma, g.col_scale, g.scale_cols, tiles_n, nwg, 0);
+            return mst_check_launch("gemm16 (128 x 64)");
+        }
+        static mst_lds_once lds_once;
+        auto kern = gemm16_kernel<T, EPI, OutT>;
+        mst_allow_lds((const void*)kern, 4 * TILE_BYTES, &lds_once);
+        const int tiles_n = g.N / BN, nwg = tiles_m * tiles_n;
+        kern<<<dim3(nwg), dim3(256), 4 * TILE_BYTES, g.s>>>((const T*)g.A, g.lda, (const T*)g.W, g.ldw, g.bias, (OutT*)g.C, g.ldc, (int)g.M, g.N,
+                                                             g.K, g.gamma, g.col_scale, g.scale_cols, tiles_n, nwg, 0);
+        return mst_check_launch("gemm16");
+    }
+};
 
 template <typename T>
-int launch_split(const void* A, int64_t lda, const void* W, int64_t ldw, float* Cpart, int64_t ldc, int64_t M, int N, int Kc, int splits,
-                 int64_t split_stride, hipStream_t s) {
+int launch_split(const gemm_args& g, int splits, int64_t split_stride) {
     static mst_lds_once lds_once;
     auto kern = gemm16_kernel<T, MST_EPI_BIAS, float>;
     mst_allow_lds((const void*)kern, 4 * TILE_BYTES, &lds_once);
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = N / BN;
+    const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = g.N / BN;
     const int nwg = tiles_m * tiles_n;
-    kern<<<dim3(nwg, splits), dim3(256), 4 * TILE_BYTES, s>>>((const T*)A, lda, (const T*)W, ldw, nullptr, Cpart, ldc, (int)M, N, Kc, nullptr,
-                                                               1.f, 0, tiles_n, nwg, split_stride);
+    kern<<<dim3(nwg, splits), dim3(256), 4 * TILE_BYTES, g.s>>>((const T*)g.A, g.lda, (const T*)g.W, g.ldw, nullptr, (float*)g.C, g.ldc, (int)g.M,
+                                                                 g.N, g.K / splits, nullptr, 1.f, 0, tiles_n, nwg, split_stride);
     return mst_check_launch("gemm16_splitk");
 }
 
-template <typename T>
-int dispatch(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int cdt,
-             int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma, float cs, int sc,
-             hipStream_t s) {
-    const bool f32out = (cdt == MST_F32);
-    switch (epi) {
-        case MST_EPI_BIAS:
-            return f32out ? launch_t<T, MST_EPI_BIAS, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s)
-                          : launch_t<T, MST_EPI_BIAS, T>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-        case MST_EPI_BIAS_GELU:
-            return f32out ? launch_t<T, MST_EPI_BIAS_GELU, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s)
-                          : launch_t<T, MST_EPI_BIAS_GELU, T>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-        case MST_EPI_BIAS_RELU:
-            return f32out ? launch_t<T, MST_EPI_BIAS_RELU, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s)
-                          : launch_t<T, MST_EPI_BIAS_RELU, T>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-        case MST_EPI_RESIDUAL:
-            return launch_t<T, MST_EPI_RESIDUAL, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-    }
-    mst_set_error("gemm16: bad epilogue %d", epi);
-    return MST_EINVAL;
+// Which kernel a 16-bit GEMM runs.  Every threshold is here, beside the measurement behind it (MI355X, tools/bench_gemm.py unless named).
+enum gemm16_kernel_id { GEMM16_WREG, GEMM16_MID, GEMM16_BIG, GEMM16_TILE128, GEMM16_TILE64 };
+
+int64_t tiles_of(const gemm_tile& t, const gemm_args& g) { return ((g.M + t.bm - 1) / t.bm) * (int64_t)(g.N / t.bn); }
+bool divides(const gemm_tile& t, const gemm_args& g) { return g.N % t.bn == 0 && g.K % t.bk == 0; }
+
+gemm16_kernel_id gemm16_route(const gemm_args& g) {
+    // weights in registers (k_gemm16_wreg.hip).  It moves 16-byte pieces on every operand (LDS-DMA of A, vector loads of W, vector stores
+    // of C): a caller of the C ABI with an odd row pitch or a sliced pointer falls back to the tiled kernels.
+    const bool al16 = g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 8 == 0 && ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.W & 15) == 0 &&
+                      ((uintptr_t)g.C & 15) == 0;
+    if (al16 && gemm16_wreg_applicable(g)) return GEMM16_WREG;
+    // 128 x 384, one 4-wave workgroup per CU (k_gemm16_mid.hip): 16-bit output of the operand type, shallow K (the epilogue weighs as much
+    // as the K-loop), enough tiles to fill the chip twice.  0.58 ms on the QKV shape against 0.65 ms for both kernels below.  Its residual
+    // (fp32 read-modify-write) form measured the same as the 128 x 128 kernel on the HBM-bound proj GEMM (0.33 ms) and was removed.
+    if (g.dt == g.cdt && (g.epi == MST_EPI_BIAS || g.epi == MST_EPI_BIAS_RELU) && divides(GEMM16_MID_TILE, g) && g.K <= 512 &&
+        tiles_of(GEMM16_MID_TILE, g) >= 512)
+        return GEMM16_MID;
+    // persistent 256 x 384 (k_gemm16_big.hip) once its tiles fill the chip: 153 FLOP per staged byte against 64.  Never the residual
+    // epilogue: its read-modify-write is HBM-bound and overlaps better with two small workgroups per CU; the big kernel's form was removed.
+    if (g.epi != MST_EPI_RESIDUAL && divides(GEMM16_BIG_TILE, g) && tiles_of(GEMM16_BIG_TILE, g) >= 192) return GEMM16_BIG;
+    // 128 x 128; below 224 workgroups that grid would leave CUs idle (a few thousand token rows against N = 384: 99 workgroups on 256
+    // CUs), so 128 x 64 tiles, twice the workgroups
+    return (int64_t)((g.M + BM - 1) / BM) * (g.N / BN) < 224 ? GEMM16_TILE64 : GEMM16_TILE128;
 }
 
 }  // namespace
 
+// K = 384 exactly (the register-resident weight slice), 384-column tiles with at most one per CU of an XCD, plain bias epilogue into the
+// operand type, the scaled column range aligned to the tiles, at least 8,192 rows (profiles/r02v_qkv_wreg.txt, r03v)
+bool gemm16_wreg_applicable(const gemm_args& g) {
+    constexpr gemm_tile t = GEMM16_WREG_TILE;
+    const int G = mst_persistent_grid() >> 3;
+    const char* e = getenv("MST_GEMM_WREG_MIN_M");    // tests lower the threshold to reach the few-chunks-per-CU paths
+    const int64_t min_m = e ? atoll(e) : 8192;        // measured crossover against the tiled kernels: faster from ~10 k rows (0.047 vs 0.080 ms at 43,840)
+    return g.K == t.bk && g.N % t.bn == 0 && g.N / t.bn <= G && g.dt == g.cdt && g.epi == MST_EPI_BIAS &&
+           (g.scale_cols % t.bn == 0 || g.scale_cols >= g.N) && g.M >= min_m && g.M < (1ll << 31) - t.bm && g.lda * 2 * t.bm < (1ll << 31) &&
+           g.ldc * 2 * t.bm < (1ll << 31) && g.ldc % 4 == 0;
+}
+
 // Cpart[z] = A[:, z Kc : (z + 1) Kc] . W[:, z Kc : (z + 1) Kc]^T for z < splits (fp32 partial products, split_stride elements apart; the caller
 // sums them: mst_colsum over a [splits, M * N] view).  The shape of d weight = dY^T . X: a small [N_out, N_in] output reduced over
 // thousands of token rows, which one workgroup per output tile would walk on a handful of CUs.
-int launch_gemm16_splitk(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, float* Cpart, int64_t ldc, int64_t M, int N, int K,
-                         int splits, int64_t split_stride, hipStream_t s) {
-    MST_CHECK_ARG(A && W && Cpart && M > 0 && splits > 0 && splits <= 65535, "gemm16_splitk: bad arguments");
-    MST_CHECK_ARG(K % splits == 0 && (K / splits) % BK == 0, "gemm16_splitk: K=%d must split into %d multiples of %d", K, splits, BK);
-    MST_CHECK_ARG(N > 0 && N % BN == 0, "gemm16_splitk: N=%d must be a multiple of %d", N, BN);
-    MST_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)Cpart & 15) == 0,
+int launch_gemm16_splitk(const gemm_args& g, int splits, int64_t split_stride) {
+    MST_CHECK_ARG(g.A && g.W && g.C && g.M > 0 && splits > 0 && splits <= 65535, "gemm16_splitk: bad arguments");
+    MST_CHECK_ARG(g.K % splits == 0 && (g.K / splits) % BK == 0, "gemm16_splitk: K=%d must split into %d multiples of %d", g.K, splits, BK);
+    MST_CHECK_ARG(g.N > 0 && g.N % BN == 0, "gemm16_splitk: N=%d must be a multiple of %d", g.N, BN);
+    MST_CHECK_ARG(g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 4 == 0 && ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.W & 15) == 0 && ((uintptr_t)g.C & 15) == 0,
                   "gemm16_splitk: lda/ldw must be multiples of 8, ldc of 4, bases 16-byte aligned");
-    MST_CHECK_ARG(split_stride >= M * ldc && split_stride % 4 == 0, "gemm16_splitk: split_stride");
-    if (dt == MST_BF16) return launch_split<bf16_t>(A, lda, W, ldw, Cpart, ldc, M, N, K / splits, splits, split_stride, s);
-    if (dt == MST_F16) return launch_split<f16_t>(A, lda, W, ldw, Cpart, ldc, M, N, K / splits, splits, split_stride, s);
-    mst_set_error("gemm16_splitk: bad operand dtype %d", dt);
+    MST_CHECK_ARG(split_stride >= g.M * g.ldc && split_stride % 4 == 0, "gemm16_splitk: split_stride");
+    if (g.dt == MST_BF16) return launch_split<bf16_t>(g, splits, split_stride);
+    if (g.dt == MST_F16) return launch_split<f16_t>(g, splits, split_stride);
+    mst_set_error("gemm16_splitk: bad operand dtype %d", g.dt);
     return MST_EINVAL;
 }
 
-int launch_gemm16(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias,
-                  void* C, int cdt, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                  float col_scale, int scale_cols, hipStream_t s) {
-    MST_CHECK_ARG(K > 0 && K % BK == 0, "gemm16: K=%d must be a multiple of %d", K, BK);
-    MST_CHECK_ARG(N > 0 && N % BN == 0, "gemm16: N=%d must be a multiple of %d", N, BN);
-    MST_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0, "gemm16: lda/ldw must be multiples of 8, ldc of 4");
-    MST_CHECK_ARG(M < (1ll << 31) - BM, "gemm16: M too large");
-    MST_CHECK_ARG(cdt == MST_F32 || cdt == dt, "gemm16: C dtype must be f32 or the operand dtype");
-    MST_CHECK_ARG(epi != MST_EPI_RESIDUAL || cdt == MST_F32, "gemm16: residual epilogue needs f32 C");
-    MST_CHECK_ARG(epi != MST_EPI_RESIDUAL_RELU, "gemm16: the residual + ReLU epilogue exists for f32 operands only");
-    if (M <= 0) return MST_OK;
-    // measured on MI355X (tools/bench_gemm.py): the read-modify-write epilogue of the residual GEMMs is
-    // HBM-bound and overlaps better with two small workgroups per CU; the others favour the big tile
-    // the weights-in-registers kernel moves 16-byte pieces on every operand (LDS-DMA of A, vector loads of W, vector stores of C): a
-    // caller of the C ABI with an odd row pitch or a sliced pointer falls back to the tiled kernels
-    const bool al16 = lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0;
-    if (al16 && gemm16_wreg_applicable(M, N, K, dt, cdt, epi, scale_cols, lda, ldc))
-        return launch_gemm16_wreg(A, dt, lda, W, ldw, bias, C, ldc, M, N, col_scale, scale_cols, s);
-    if (gemm16_mid_applicable(M, N, K, dt, cdt, epi))
-        return launch_gemm16_mid(A, dt, lda, W, ldw, bias, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    if (epi != MST_EPI_RESIDUAL && gemm16_big_applicable(M, N, K))
-        return launch_gemm16_big(A, dt, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    if (dt == MST_BF16) return dispatch<bf16_t>(A, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    if (dt == MST_F16) return dispatch<f16_t>(A, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    mst_set_error("gemm16: bad operand dtype %d", dt);
-    return MST_EINVAL;
+int launch_gemm16(const gemm_args& g) {
+    MST_CHECK_ARG(g.K > 0 && g.K % BK == 0, "gemm16: K=%d must be a multiple of %d", g.K, BK);
+    MST_CHECK_ARG(g.N > 0 && g.N % BN == 0, "gemm16: N=%d must be a multiple of %d", g.N, BN);
+    MST_CHECK_ARG(g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 4 == 0, "gemm16: lda/ldw must be multiples of 8, ldc of 4");
+    MST_CHECK_ARG(g.M < (1ll << 31) - BM, "gemm16: M too large");
+    MST_CHECK_ARG(g.cdt == MST_F32 || g.cdt == g.dt, "gemm16: C dtype must be f32 or the operand dtype");
+    MST_CHECK_ARG(g.epi != MST_EPI_RESIDUAL || g.cdt == MST_F32, "gemm16: residual epilogue needs f32 C");
+    MST_CHECK_ARG(g.epi != MST_EPI_RESIDUAL_RELU, "gemm16: the residual + ReLU epilogue exists for f32 operands only");
+    if (g.M <= 0) return MST_OK;
+    switch (gemm16_route(g)) {
+        case GEMM16_WREG: return launch_gemm16_wreg(g);
+        case GEMM16_MID: return launch_gemm16_mid(g);
+        case GEMM16_BIG: return launch_gemm16_big(g);
+        case GEMM16_TILE128: return gemm_dispatch("gemm16", g, tile_launcher{false});
+        case GEMM16_TILE64: return gemm_dispatch("gemm16", g, tile_launcher{true});
+    }
+    return MST_EINVAL;   // not reached: every route returns above
 }

@@ -1,5 +1,6 @@
-// Large-tile persistent variant of the 16-bit MFMA GEMM (same contract as k_gemm16.hip), for the
-// encoder's streaming shapes (M = slices x tokens ~ 10^5, N in {1152, 384, 1536}, K in {384, 1536}).
+// Large-tile persistent variant of the 16-bit MFMA GEMM (contract of k_gemm16.hip without the residual
+// epilogue, which stays on the 128 x 128 kernel: gemm16_route), for the encoder's streaming shapes
+// (M = slices x tokens ~ 10^5, N in {1152, 384, 1536}, K in {384, 1536}).
 //
 // Why: a CU's global->LDS fill rate (~55-90 GB/s per CU on MI355X, microarch guide "ring-gemm")
 // bounds a 128x128 tile at ~64 FLOP/B to well under half the MFMA rate; a 256 x 384 tile needs
@@ -24,7 +25,7 @@
 
 namespace {
 
-constexpr int BM = 256, BN = 384, BK = 32, NSTAGE = 4;
+constexpr int BM = GEMM16_BIG_TILE.bm, BN = GEMM16_BIG_TILE.bn, BK = GEMM16_BIG_TILE.bk, NSTAGE = 4;   // 256 x 384 x 32
 constexpr int A_BYTES = BM * BK * 2;              // 16 KiB
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;   // 40 KiB
 constexpr int LDS_BYTES = NSTAGE * STAGE_BYTES;   // 160 KiB
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
                                                          const T* __restrict__ W, int64_t ldw,
                                                          const float* __restrict__ bias, OutT* C,
                                                          int64_t ldc, int M, int N, int K,
-                                                         const float* __restrict__ gamma, float col_scale,
+                                                         float col_scale,
                                                          int scale_cols, int tiles_n, int ntiles) {
     typedef typename V8<T>::type vec8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -143,7 +144,8 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
             if (1 < nk) stage(1, 1);
         }
 
-        // ---- epilogue, coalesced through LDS.  In registers a lane owns C[mb+16j][nb+16i .. +3]: a direct
+        // ---- epilogue, coalesced through LDS (the same text as k_gemm16_mid.hip's: sharing it through a __forceinline__ template
+        // re-allocates and re-schedules both kernels, profiles/gemm_host_layer_device_asm_parent_vs_new.md).  In registers a lane owns C[mb+16j][nb+16i .. +3]: a direct
         // store touches 16 rows x 32-64 B per instruction (measured: 2 TB/s, 2x the whole K-loop).  Instead
         // each wave transposes one 16-row x 96-column slab at a time through its private staging area and
         // moves it to / from global memory as 16-byte lane accesses along whole row segments.
@@ -181,16 +183,6 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
                             *reinterpret_cast<o4*>(stg + wr_off + i * 32) = pk;
                         }
                     }
-                    float4 xv[NCH];
-                    if constexpr (EPI == MST_EPI_RESIDUAL) {   // all read-modify-write loads of the slab first
-#pragma unroll
-                        for (int c = 0; c < NCH; ++c) {
-                            const int q = c * 64 + lane;
-                            const int row = q / CPR, ch = q - row * CPR;
-                            const int m = m_w + j * 16 + row;
-                            if (FULL || m < M) xv[c] = *reinterpret_cast<const float4*>(C + (int64_t)m * ldc + n_w + ch * 4);
-                        }
-                    }
 #pragma unroll
                     for (int c = 0; c < NCH; ++c) {
                         const int q = c * 64 + lane;
@@ -199,18 +191,7 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
                         const u32x4 t = *reinterpret_cast<const u32x4*>(stg + row * ROWB + ch * 16);
                         if (!FULL && m >= M) continue;
                         OutT* cp = C + (int64_t)m * ldc + n_w + ch * (16 / OB);
-                        if constexpr (EPI == MST_EPI_RESIDUAL) {
-                            float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-                            if (gamma) gv = *reinterpret_cast<const float4*>(gamma + n_w + ch * 4);
-                            float4 o;
-                            o.x = xv[c].x + gv.x * __uint_as_float(t[0]);
-                            o.y = xv[c].y + gv.y * __uint_as_float(t[1]);
-                            o.z = xv[c].z + gv.z * __uint_as_float(t[2]);
-                            o.w = xv[c].w + gv.w * __uint_as_float(t[3]);
-                            *reinterpret_cast<float4*>(cp) = o;
-                        } else {
-                            *reinterpret_cast<u32x4*>(cp) = t;
-                        }
+                        *reinterpret_cast<u32x4*>(cp) = t;
                     }
                     __builtin_amdgcn_sched_barrier(0);   // keep each slab's loads/temps from being hoisted over the others
                 }
@@ -228,54 +209,26 @@ __global__ __launch_bounds__(512) void gemm16_big_kernel(const T* __restrict__ A
     }
 }
 
-template <typename T, int EPI, typename OutT>
-int launch_t(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
-             int64_t M, int N, int K, const float* gamma, float cs, int sc, hipStream_t s) {
-    static mst_lds_once lds_once;
-    auto kern = gemm16_big_kernel<T, EPI, OutT>;
-    mst_allow_lds((const void*)kern, LDS_BYTES, &lds_once);
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = N / BN;
-    const int ntiles = tiles_m * tiles_n;
-    const int cus = mst_persistent_grid();
-    int nblk = ntiles < cus ? ((ntiles + 7) / 8) * 8 : cus;
-    kern<<<dim3(nblk), dim3(512), LDS_BYTES, s>>>((const T*)A, lda, (const T*)W, ldw, bias, (OutT*)C, ldc, (int)M, N, K,
-                                                   gamma, cs, sc, tiles_n, ntiles);
-    return mst_check_launch("gemm16_big");
-}
-
-template <typename T>
-int dispatch(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int cdt, int64_t ldc,
-             int64_t M, int N, int K, int epi, const float* gamma, float cs, int sc, hipStream_t s) {
-    const bool f32out = (cdt == MST_F32);
-    switch (epi) {
-        case MST_EPI_BIAS:
-            return f32out ? launch_t<T, MST_EPI_BIAS, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s)
-                          : launch_t<T, MST_EPI_BIAS, T>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-        case MST_EPI_BIAS_GELU:
-            return f32out ? launch_t<T, MST_EPI_BIAS_GELU, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s)
-                          : launch_t<T, MST_EPI_BIAS_GELU, T>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-        case MST_EPI_BIAS_RELU:
-            return f32out ? launch_t<T, MST_EPI_BIAS_RELU, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s)
-                          : launch_t<T, MST_EPI_BIAS_RELU, T>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
-        case MST_EPI_RESIDUAL:
-            return launch_t<T, MST_EPI_RESIDUAL, float>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, cs, sc, s);
+// bias, GELU and ReLU epilogues into fp32 or the operand type
+struct big_launcher {
+    template <typename T, int EPI, typename OutT> static constexpr bool has() {
+        return (std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value) && EPI <= MST_EPI_BIAS_RELU &&
+               (std::is_same<OutT, float>::value || std::is_same<OutT, T>::value);
     }
-    mst_set_error("gemm16_big: bad epilogue %d", epi);
-    return MST_EINVAL;
-}
+    template <typename T, int EPI, typename OutT> int launch(const gemm_args& g) const {
+        static mst_lds_once lds_once;
+        auto kern = gemm16_big_kernel<T, EPI, OutT>;
+        mst_allow_lds((const void*)kern, LDS_BYTES, &lds_once);
+        const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = g.N / BN;
+        const int ntiles = tiles_m * tiles_n;
+        const int cus = mst_persistent_grid();
+        int nblk = ntiles < cus ? ((ntiles + 7) / 8) * 8 : cus;
+        kern<<<dim3(nblk), dim3(512), LDS_BYTES, g.s>>>((const T*)g.A, g.lda, (const T*)g.W, g.ldw, g.bias, (OutT*)g.C, g.ldc, (int)g.M, g.N,
+                                                         g.K, g.col_scale, g.scale_cols, tiles_n, ntiles);
+        return mst_check_launch("gemm16_big");
+    }
+};
 
 }  // namespace
 
-// true when the big-tile kernel applies and fills the chip (else the 128x128 kernel is used)
-bool gemm16_big_applicable(int64_t M, int N, int K) {
-    return (N % BN == 0) && (K % BK == 0) && ((M + BM - 1) / BM) * (int64_t)(N / BN) >= 192;
-}
-
-int launch_gemm16_big(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
-                      int cdt, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma, float col_scale,
-                      int scale_cols, hipStream_t s) {
-    if (dt == MST_BF16) return dispatch<bf16_t>(A, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    if (dt == MST_F16) return dispatch<f16_t>(A, lda, W, ldw, bias, C, cdt, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    mst_set_error("gemm16_big: bad operand dtype %d", dt);
-    return MST_EINVAL;
-}
+int launch_gemm16_big(const gemm_args& g) { return gemm_dispatch("gemm16_big", g, big_launcher{}); }

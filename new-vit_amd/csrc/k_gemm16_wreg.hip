@@ -31,7 +31,7 @@
 
 namespace {
 
-constexpr int KD = 384, BN = 384, CH = 32;
+constexpr int KD = GEMM16_WREG_TILE.bk, BN = GEMM16_WREG_TILE.bn, CH = GEMM16_WREG_TILE.bm;   // K = 384, 384-column tiles, 32-row chunks
 constexpr int ROWB = KD * 2;                       // 768-byte LDS rows
 constexpr int SLOT = CH * ROWB;                    // 24 KiB per chunk
 constexpr int WREG_NSLOT = 4;
@@ -245,37 +245,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 template <typename T, bool BLK>
-int launch_t(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc, int64_t M, int N,
-             float cs, int sc, hipStream_t s) {
+int launch_t(const gemm_args& g) {
     static mst_lds_once lds_once;
     auto kern = gemm16_wreg_kernel<T, BLK>;
     mst_allow_lds((const void*)kern, LDS_BYTES, &lds_once);
-    const int nchunks = (int)((M + CH - 1) / CH);
-    kern<<<dim3(mst_persistent_grid()), dim3(512), LDS_BYTES, s>>>((const T*)A, lda, (const T*)W, ldw, bias, (T*)C, ldc, (int)M, N, cs,
-                                                                  sc, nchunks);
+    const int nchunks = (int)((g.M + CH - 1) / CH);
+    kern<<<dim3(mst_persistent_grid()), dim3(512), LDS_BYTES, g.s>>>((const T*)g.A, g.lda, (const T*)g.W, g.ldw, g.bias, (T*)g.C, g.ldc, (int)g.M,
+                                                                      g.N, g.col_scale, g.scale_cols, nchunks);
     return mst_check_launch("gemm16_wreg");
 }
 
 }  // namespace
 
-// K = 384 exactly (the register-resident weight slice), 384-column tiles, plain bias epilogue into the operand type, the scaled
-// column range aligned to the tiles, at least 8,192 rows (profiles/r02v_qkv_wreg.txt, r03v)
-bool gemm16_wreg_applicable(int64_t M, int N, int K, int dt, int cdt, int epi, int scale_cols, int64_t lda, int64_t ldc) {
-    const int G = mst_persistent_grid() >> 3;
-    const char* e = getenv("MST_GEMM_WREG_MIN_M");    // tests lower the threshold to reach the few-chunks-per-CU paths
-    const int64_t min_m = e ? atoll(e) : 8192;        // measured crossover against the tiled kernels: faster from ~10 k rows (0.047 vs 0.080 ms at 43,840)
-    return K == KD && N % BN == 0 && N / BN <= G && dt == cdt && epi == MST_EPI_BIAS && (scale_cols % BN == 0 || scale_cols >= N) &&
-           M >= min_m && M < (1ll << 31) - CH && lda * 2 * CH < (1ll << 31) && ldc * 2 * CH < (1ll << 31) && ldc % 4 == 0;
-}
-
-int launch_gemm16_wreg(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
-                       int64_t M, int N, float col_scale, int scale_cols, hipStream_t s, int a_blocked) {
+// for the shapes gemm16_wreg_applicable (k_gemm16.hip) admits
+int launch_gemm16_wreg(const gemm_args& g, int a_blocked) {
     if (a_blocked) {
-        if (dt == MST_BF16) return launch_t<bf16_t, true>(A, lda, W, ldw, bias, C, ldc, M, N, col_scale, scale_cols, s);
-        if (dt == MST_F16) return launch_t<f16_t, true>(A, lda, W, ldw, bias, C, ldc, M, N, col_scale, scale_cols, s);
+        if (g.dt == MST_BF16) return launch_t<bf16_t, true>(g);
+        if (g.dt == MST_F16) return launch_t<f16_t, true>(g);
     }
-    if (dt == MST_BF16) return launch_t<bf16_t, false>(A, lda, W, ldw, bias, C, ldc, M, N, col_scale, scale_cols, s);
-    if (dt == MST_F16) return launch_t<f16_t, false>(A, lda, W, ldw, bias, C, ldc, M, N, col_scale, scale_cols, s);
-    mst_set_error("gemm16_wreg: bad operand dtype %d", dt);
+    if (g.dt == MST_BF16) return launch_t<bf16_t, false>(g);
+    if (g.dt == MST_F16) return launch_t<f16_t, false>(g);
+    mst_set_error("gemm16_wreg: bad operand dtype %d", g.dt);
     return MST_EINVAL;
 }

@@ -162,24 +162,35 @@ __global__ __launch_bounds__(256) void gemm32_kernel(const float* __restrict__ A
         }
 }
 
-template <int EPI>
-int launch_t(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C,
-             int64_t ldc, int64_t M, int N, int K, const float* gamma, float cs, int sc, hipStream_t s) {
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (N + BN - 1) / BN;
-    const int nwg = tiles_m * tiles_n;
-    gemm32_kernel<EPI><<<dim3(nwg), dim3(256), 0, s>>>(A, lda, W, ldw, bias, C, ldc, (int)M, N, K, gamma, cs, sc,
-                                                        tiles_n, nwg);
-    return mst_check_launch("gemm32");
-}
+// every epilogue, fp32 throughout
+struct tile_launcher {
+    template <typename T, int EPI, typename OutT> static constexpr bool has() { return std::is_same<T, float>::value && std::is_same<OutT, float>::value; }
+    template <typename T, int EPI, typename OutT> int launch(const gemm_args& g) const {
+        const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (g.N + BN - 1) / BN;
+        const int nwg = tiles_m * tiles_n;
+        gemm32_kernel<EPI><<<dim3(nwg), dim3(256), 0, g.s>>>((const float*)g.A, g.lda, (const float*)g.W, g.ldw, g.bias, (float*)g.C, g.ldc, (int)g.M,
+                                                              g.N, g.K, g.gamma, g.col_scale, g.scale_cols, tiles_n, nwg);
+        return mst_check_launch("gemm32");
+    }
+};
 
-template <int EPI>
-int launch_conv_t(const float* x, const ConvGeom& cg, int n, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, int N,
-                  int K, const float* gamma, hipStream_t s) {
-    const int64_t M = (int64_t)n * cg.Ho * cg.Wo;
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (N + BN - 1) / BN;
-    const int nwg = tiles_m * tiles_n;
-    gemm32_kernel<EPI, true><<<dim3(nwg), dim3(256), 0, s>>>(x, 0, W, ldw, bias, C, ldc, (int)M, N, K, gamma, 1.f, 0, tiles_n, nwg, cg);
-    return mst_check_launch("conv_gemm32");
+// the implicit-GEMM convolution: g.A is the NHWC activation, g.M its output pixels; no GELU
+struct conv_launcher {
+    ConvGeom cg;
+    template <typename T, int EPI, typename OutT> static constexpr bool has() { return tile_launcher::has<T, EPI, OutT>() && EPI != MST_EPI_BIAS_GELU; }
+    template <typename T, int EPI, typename OutT> int launch(const gemm_args& g) const {
+        const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (g.N + BN - 1) / BN;
+        const int nwg = tiles_m * tiles_n;
+        gemm32_kernel<EPI, true><<<dim3(nwg), dim3(256), 0, g.s>>>((const float*)g.A, 0, (const float*)g.W, g.ldw, g.bias, (float*)g.C, g.ldc,
+                                                                    (int)g.M, g.N, g.K, g.gamma, 1.f, 0, tiles_n, nwg, cg);
+        return mst_check_launch("conv_gemm32");
+    }
+};
+int launch_conv(const ConvGeom& cg, const float* x, int n, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, int N, int K,
+                int epi, const float* gamma, hipStream_t s) {
+    gemm_args g{x, MST_F32, 0, W, ldw, bias, C, MST_F32, ldc, (int64_t)n * cg.Ho * cg.Wo, N, K};
+    g.epi = epi, g.gamma = gamma, g.s = s;
+    return gemm_dispatch("conv_gemm", g, conv_launcher{cg});
 }
 
 }  // namespace
@@ -193,14 +204,9 @@ int launch_conv_gemm32(const float* x, int n, int H, int W_, int Cin, int kh, in
     MST_CHECK_ARG(Kpad >= kh * kw * Cin && Kpad % BK == 0 && ldw % 4 == 0 && ldw >= Kpad, "conv_gemm: Kpad=%d / ldw", Kpad);
     ConvGeom cg{H, W_, Cin, kh, kw, stride, pad, (H + 2 * pad - kh) / stride + 1, (W_ + 2 * pad - kw) / stride + 1, 0};
     MST_CHECK_ARG(cg.Ho > 0 && cg.Wo > 0 && (int64_t)n * cg.Ho * cg.Wo < (1ll << 31) - BM, "conv_gemm: output %d x %d x %d", n, cg.Ho, cg.Wo);
-    switch (epi) {
-        case MST_EPI_BIAS: return launch_conv_t<MST_EPI_BIAS>(x, cg, n, Wg, ldw, bias, out, ldc, Cout, Kpad, gamma, s);
-        case MST_EPI_BIAS_RELU: return launch_conv_t<MST_EPI_BIAS_RELU>(x, cg, n, Wg, ldw, bias, out, ldc, Cout, Kpad, gamma, s);
-        case MST_EPI_RESIDUAL: return launch_conv_t<MST_EPI_RESIDUAL>(x, cg, n, Wg, ldw, bias, out, ldc, Cout, Kpad, gamma, s);
-        case MST_EPI_RESIDUAL_RELU: return launch_conv_t<MST_EPI_RESIDUAL_RELU>(x, cg, n, Wg, ldw, bias, out, ldc, Cout, Kpad, gamma, s);
-    }
-    mst_set_error("conv_gemm: epilogue %d unsupported (bias, bias + ReLU, residual, residual + ReLU)", epi);
-    return MST_EINVAL;
+    MST_CHECK_ARG(epi == MST_EPI_BIAS || epi == MST_EPI_BIAS_RELU || epi == MST_EPI_RESIDUAL || epi == MST_EPI_RESIDUAL_RELU,
+                  "conv_gemm: epilogue %d unsupported (bias, bias + ReLU, residual, residual + ReLU)", epi);
+    return launch_conv(cg, x, n, Wg, ldw, bias, out, ldc, Cout, Kpad, epi, gamma, s);
 }
 
 // d input of a convolution as a convolution: dx[img][y][x][c] = sum_{ky',kx',co} dz[img][(y - pt + ky') / s][(x - pt + kx') / s][co] * Wt[c][(ky',kx',co)]
@@ -216,26 +222,15 @@ int launch_conv_dgrad32(const float* dz, int n, int Ho, int Wo, int Cout, int kh
     MST_CHECK_ARG((int64_t)n * H * W_ < (1ll << 31) - BM, "conv_dgrad: %d x %d x %d", n, H, W_);
     ConvGeom cg{Ho, Wo, Cout, kh, kw, 1, kh - 1 - pad, H, W_, stride - 1};
     const int K = kh * kw * Cout;
-    return launch_conv_t<MST_EPI_BIAS>(dz, cg, n, Wt, K, nullptr, dx, Cin, Cin, K, nullptr, s);
+    return launch_conv(cg, dz, n, Wt, K, nullptr, dx, Cin, Cin, K, MST_EPI_BIAS, nullptr, s);
 }
 
-int launch_gemm32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
-                  float* C, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                  float col_scale, int scale_cols, hipStream_t s) {
-    MST_CHECK_ARG(K > 0 && K % BK == 0, "gemm32: K=%d must be a multiple of %d", K, BK);
-    MST_CHECK_ARG(N > 0, "gemm32: N=%d", N);
-    MST_CHECK_ARG(lda % 4 == 0 && ldw % 4 == 0, "gemm32: lda/ldw must be multiples of 4");
-    MST_CHECK_ARG(M < (1ll << 31) - BM, "gemm32: M too large");
-    if (M <= 0) return MST_OK;
-    if (gemm32_small_applicable(M, N, K))   // across-slice stage: a few hundred rows (k_gemm32s.hip)
-        return launch_gemm32_small(A, lda, W, ldw, bias, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, s);
-    switch (epi) {
-        case MST_EPI_BIAS: return launch_t<MST_EPI_BIAS>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_BIAS_GELU: return launch_t<MST_EPI_BIAS_GELU>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_BIAS_RELU: return launch_t<MST_EPI_BIAS_RELU>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_RESIDUAL: return launch_t<MST_EPI_RESIDUAL>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_RESIDUAL_RELU: return launch_t<MST_EPI_RESIDUAL_RELU>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-    }
-    mst_set_error("gemm32: bad epilogue %d", epi);
-    return MST_EINVAL;
+int launch_gemm32(const gemm_args& g) {
+    MST_CHECK_ARG(g.K > 0 && g.K % BK == 0, "gemm32: K=%d must be a multiple of %d", g.K, BK);
+    MST_CHECK_ARG(g.N > 0, "gemm32: N=%d", g.N);
+    MST_CHECK_ARG(g.lda % 4 == 0 && g.ldw % 4 == 0, "gemm32: lda/ldw must be multiples of 4");
+    MST_CHECK_ARG(g.M < (1ll << 31) - BM, "gemm32: M too large");
+    if (g.M <= 0) return MST_OK;
+    if (gemm32_small_applicable(g.M, g.N, g.K)) return launch_gemm32_small(g);   // across-slice stage: a few hundred rows (k_gemm32s.hip)
+    return gemm_dispatch("gemm32", g, tile_launcher{});
 }

@@ -73,27 +73,18 @@ __global__ __launch_bounds__(64) void gemm32s_kernel(const float* __restrict__ A
     }
 }
 
-template <int EPI>
-int launch_t(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, int64_t M,
-             int N, int K, const float* gamma, float cs, int sc, hipStream_t s) {
-    gemm32s_kernel<EPI><<<dim3((N + 31) / 32, (unsigned)((M + 31) / 32)), dim3(64), 0, s>>>(A, lda, W, ldw, bias, C, ldc, (int)M, N,
-                                                                                          K, gamma, cs, sc);
-    return mst_check_launch("gemm32s");
-}
+// every epilogue, fp32 throughout
+struct small_launcher {
+    template <typename T, int EPI, typename OutT> static constexpr bool has() { return std::is_same<T, float>::value && std::is_same<OutT, float>::value; }
+    template <typename T, int EPI, typename OutT> int launch(const gemm_args& g) const {
+        gemm32s_kernel<EPI><<<dim3((g.N + 31) / 32, (unsigned)((g.M + 31) / 32)), dim3(64), 0, g.s>>>(
+            (const float*)g.A, g.lda, (const float*)g.W, g.ldw, g.bias, (float*)g.C, g.ldc, (int)g.M, g.N, g.K, g.gamma, g.col_scale, g.scale_cols);
+        return mst_check_launch("gemm32s");
+    }
+};
 
 }  // namespace
 
 bool gemm32_small_applicable(int64_t M, int N, int K) { return M <= 1024 && K % 16 == 0 && (int64_t)((M + 31) / 32) * ((N + 31) / 32) <= 65535 * 8; }
 
-int launch_gemm32_small(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc,
-                        int64_t M, int N, int K, int epi, const float* gamma, float col_scale, int scale_cols, hipStream_t s) {
-    switch (epi) {
-        case MST_EPI_BIAS: return launch_t<MST_EPI_BIAS>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_BIAS_GELU: return launch_t<MST_EPI_BIAS_GELU>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_BIAS_RELU: return launch_t<MST_EPI_BIAS_RELU>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_RESIDUAL: return launch_t<MST_EPI_RESIDUAL>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-        case MST_EPI_RESIDUAL_RELU: return launch_t<MST_EPI_RESIDUAL_RELU>(A, lda, W, ldw, bias, C, ldc, M, N, K, gamma, col_scale, scale_cols, s);
-    }
-    mst_set_error("gemm32s: bad epilogue %d", epi);
-    return MST_EINVAL;
-}
+int launch_gemm32_small(const gemm_args& g) { return gemm_dispatch("gemm32s", g, small_launcher{}); }

@@ -260,36 +260,25 @@ __global__ __launch_bounds__(256) void gemm8_kernel(const uint8_t* __restrict__ 
     }
 }
 
-template <int EPI, typename OutT>
-int launch_t(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* a_amax, float w_scale,
-             void* C, int64_t ldc, int64_t M, int N, int K, const float* gamma, float cs, int sc, float* out_amax,
-             const float* c_amax, hipStream_t s) {
-    static mst_lds_once lds_once[2];
-    static const bool mx = !(getenv("MST_FP8_MX") && atoi(getenv("MST_FP8_MX")) == 0);
-    auto kern = mx ? gemm8_kernel<EPI, OutT, true> : gemm8_kernel<EPI, OutT, false>;
-    mst_allow_lds((const void*)kern, 4 * TILE_BYTES, &lds_once[mx]);
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = N / BN;
-    const int nwg = tiles_m * tiles_n;
-    kern<<<dim3(nwg), dim3(256), 4 * TILE_BYTES, s>>>((const uint8_t*)A, lda, (const uint8_t*)W, ldw, bias, a_amax, w_scale,
-                                                       (OutT*)C, ldc, (int)M, N, K, gamma, cs, sc, tiles_n, nwg, out_amax, c_amax);
-    return mst_check_launch("gemm8");
-}
-
-template <typename OutT>
-int dispatch(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* a_amax, float w_scale,
-             void* C, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma, float cs, int sc, float* out_amax,
-             const float* c_amax, hipStream_t s) {
-    switch (epi) {
-        case MST_EPI_BIAS:
-            return launch_t<MST_EPI_BIAS, OutT>(A, lda, W, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, gamma, cs, sc, out_amax, c_amax, s);
-        case MST_EPI_BIAS_GELU:
-            return launch_t<MST_EPI_BIAS_GELU, OutT>(A, lda, W, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, gamma, cs, sc, out_amax, c_amax, s);
-        case MST_EPI_BIAS_RELU:
-            return launch_t<MST_EPI_BIAS_RELU, OutT>(A, lda, W, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, gamma, cs, sc, out_amax, c_amax, s);
+// e4m3 operands; bias, GELU and ReLU epilogues into e4m3, fp32, bf16 or fp16, the residual one into fp32
+struct fp8_launcher {
+    template <typename T, int EPI, typename OutT> static constexpr bool has() {
+        return std::is_same<T, uint8_t>::value && (EPI == MST_EPI_RESIDUAL ? std::is_same<OutT, float>::value : EPI <= MST_EPI_BIAS_RELU);
     }
-    mst_set_error("gemm8: bad epilogue %d", epi);
-    return MST_EINVAL;
-}
+    template <typename T, int EPI, typename OutT> int launch(const gemm_args& g) const {
+        static mst_lds_once lds_once[2];
+        static const bool mx = !(getenv("MST_FP8_MX") && atoi(getenv("MST_FP8_MX")) == 0);
+        auto kern = mx ? gemm8_kernel<EPI, OutT, true> : gemm8_kernel<EPI, OutT, false>;
+        mst_allow_lds((const void*)kern, 4 * TILE_BYTES, &lds_once[mx]);
+        const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = g.N / BN;
+        const int nwg = tiles_m * tiles_n;
+        constexpr bool res = EPI == MST_EPI_RESIDUAL;   // reads neither scale
+        kern<<<dim3(nwg), dim3(256), 4 * TILE_BYTES, g.s>>>((const uint8_t*)g.A, g.lda, (const uint8_t*)g.W, g.ldw, g.bias, g.a_amax, g.w_scale,
+                                                             (OutT*)g.C, g.ldc, (int)g.M, g.N, g.K, g.gamma, g.col_scale, g.scale_cols, tiles_n, nwg,
+                                                             res ? nullptr : g.out_amax, res ? nullptr : g.c_amax);
+        return mst_check_launch("gemm8");
+    }
+};
 
 }  // namespace
 
@@ -330,25 +319,17 @@ int launch_quant8_static(const void* x, int dt, int64_t n, const float* amax, vo
     return quant8_impl(x, dt, n, nullptr, amax, out8, s);
 }
 
-int launch_gemm8(const void* A8, int64_t lda, const void* W8, int64_t ldw, const float* bias, const float* a_amax,
-                 float w_scale, void* C, int cdt, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                 float col_scale, int scale_cols, float* out_amax, const float* c_amax, hipStream_t s) {
-    MST_CHECK_ARG(A8 && W8 && C && a_amax, "gemm8: null pointer");
-    MST_CHECK_ARG(cdt != MST_F8E4M3 || (c_amax && epi != MST_EPI_RESIDUAL && !out_amax),
+int launch_gemm8(const gemm_args& g) {
+    MST_CHECK_ARG(g.A && g.W && g.C && g.a_amax, "gemm8: null pointer");
+    MST_CHECK_ARG(g.cdt != MST_F8E4M3 || (g.c_amax && g.epi != MST_EPI_RESIDUAL && !g.out_amax),
                   "gemm8: an e4m3 C needs c_amax and a non-residual epilogue");
-    MST_CHECK_ARG(!out_amax || (cdt != MST_F32 && epi != MST_EPI_RESIDUAL), "gemm8: out_amax needs a 16-bit, non-residual C");
-    MST_CHECK_ARG(K > 0 && K % BKB == 0, "gemm8: K=%d must be a multiple of %d", K, BKB);
-    MST_CHECK_ARG(N > 0 && N % BN == 0, "gemm8: N=%d must be a multiple of %d", N, BN);
-    MST_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0, "gemm8: lda/ldw must be multiples of 16, ldc of 4");
-    MST_CHECK_ARG(M < (1ll << 31) - BM, "gemm8: M too large");
-    MST_CHECK_ARG(cdt == MST_F32 || cdt == MST_BF16 || cdt == MST_F16 || cdt == MST_F8E4M3, "gemm8: bad C dtype %d", cdt);
-    MST_CHECK_ARG(epi != MST_EPI_RESIDUAL || cdt == MST_F32, "gemm8: residual epilogue needs f32 C");
-    if (M <= 0) return MST_OK;
-    if (epi == MST_EPI_RESIDUAL)
-        return launch_t<MST_EPI_RESIDUAL, float>(A8, lda, W8, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, gamma, col_scale,
-                                                 scale_cols, nullptr, nullptr, s);
-    if (cdt == MST_F8E4M3) return dispatch<uint8_t>(A8, lda, W8, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, out_amax, c_amax, s);
-    if (cdt == MST_F32) return dispatch<float>(A8, lda, W8, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, out_amax, c_amax, s);
-    if (cdt == MST_BF16) return dispatch<bf16_t>(A8, lda, W8, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, out_amax, c_amax, s);
-    return dispatch<f16_t>(A8, lda, W8, ldw, bias, a_amax, w_scale, C, ldc, M, N, K, epi, gamma, col_scale, scale_cols, out_amax, c_amax, s);
+    MST_CHECK_ARG(!g.out_amax || (g.cdt != MST_F32 && g.epi != MST_EPI_RESIDUAL), "gemm8: out_amax needs a 16-bit, non-residual C");
+    MST_CHECK_ARG(g.K > 0 && g.K % BKB == 0, "gemm8: K=%d must be a multiple of %d", g.K, BKB);
+    MST_CHECK_ARG(g.N > 0 && g.N % BN == 0, "gemm8: N=%d must be a multiple of %d", g.N, BN);
+    MST_CHECK_ARG(g.lda % 16 == 0 && g.ldw % 16 == 0 && g.ldc % 4 == 0, "gemm8: lda/ldw must be multiples of 16, ldc of 4");
+    MST_CHECK_ARG(g.M < (1ll << 31) - BM, "gemm8: M too large");
+    MST_CHECK_ARG(g.cdt == MST_F32 || g.cdt == MST_BF16 || g.cdt == MST_F16 || g.cdt == MST_F8E4M3, "gemm8: bad C dtype %d", g.cdt);
+    MST_CHECK_ARG(g.epi != MST_EPI_RESIDUAL || g.cdt == MST_F32, "gemm8: residual epilogue needs f32 C");
+    if (g.M <= 0) return MST_OK;
+    return gemm_dispatch("gemm8", g, fp8_launcher{});
 }

@@ -90,6 +90,16 @@ struct ProfScope {
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline size_t dt_size(int dt) { return dt == MST_F32 ? 4 : 2; }
 
+// mst_gemm on a record: the null check the encoder's call sites rely on, then the exact-fp32 or the 16-bit kernels
+static int gemm(const gemm_args& g) {
+    MST_CHECK_ARG(g.A && g.W && g.C, "gemm: null pointer");
+    if (g.dt == MST_F32) {
+        MST_CHECK_ARG(g.cdt == MST_F32, "gemm: f32 operands need f32 C");
+        return launch_gemm32(g);
+    }
+    return launch_gemm16(g);
+}
+
 extern "C" {
 
 int mst_version(void) { return 300; }
@@ -104,14 +114,7 @@ int mst_layernorm(const float* x, int64_t x_stride, const float* gamma, const fl
 int mst_gemm(const void* A, int ab_dtype, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
              int c_dtype, int64_t ldc, int64_t M, int N, int K, int epilogue, const float* gamma,
              float col_scale, int scale_cols, mst_stream_t stream) {
-    MST_CHECK_ARG(A && W && C, "gemm: null pointer");
-    if (ab_dtype == MST_F32) {
-        MST_CHECK_ARG(c_dtype == MST_F32, "gemm: f32 operands need f32 C");
-        return launch_gemm32((const float*)A, lda, (const float*)W, ldw, bias, (float*)C, ldc, M, N, K, epilogue,
-                             gamma, col_scale, scale_cols, (hipStream_t)stream);
-    }
-    return launch_gemm16(A, ab_dtype, lda, W, ldw, bias, C, c_dtype, ldc, M, N, K, epilogue, gamma, col_scale,
-                         scale_cols, (hipStream_t)stream);
+    return gemm({A, ab_dtype, lda, W, ldw, bias, C, c_dtype, ldc, M, N, K, epilogue, gamma, col_scale, scale_cols, (hipStream_t)stream});
 }
 
 int mst_quantize_fp8(const void* x, int dtype, int64_t n, float* amax, void* out8, mst_stream_t stream) {
@@ -122,8 +125,8 @@ int mst_quantize_fp8(const void* x, int dtype, int64_t n, float* amax, void* out
 int mst_gemm_fp8(const void* A8, int64_t lda, const void* W8, int64_t ldw, const float* bias, const float* a_amax,
                  float w_scale, void* C, int c_dtype, int64_t ldc, int64_t M, int N, int K, int epilogue,
                  const float* gamma, float col_scale, int scale_cols, const float* c_amax, mst_stream_t stream) {
-    return launch_gemm8(A8, lda, W8, ldw, bias, a_amax, w_scale, C, c_dtype, ldc, M, N, K, epilogue, gamma, col_scale,
-                        scale_cols, nullptr, c_dtype == MST_F8E4M3 ? c_amax : nullptr, (hipStream_t)stream);
+    return launch_gemm8({A8, MST_F8E4M3, lda, W8, ldw, bias, C, c_dtype, ldc, M, N, K, epilogue, gamma, col_scale, scale_cols, (hipStream_t)stream,
+                         a_amax, w_scale, nullptr, c_dtype == MST_F8E4M3 ? c_amax : nullptr});
 }
 
 int mst_layernorm_fp8(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* out8,
@@ -219,7 +222,9 @@ int mst_cvt16(const float* x, int64_t ldx, int64_t rows, int cols, float scale, 
 }
 int mst_gemm16_splitk(const void* A, int ab_dtype, int64_t lda, const void* W, int64_t ldw, float* Cpart, int64_t ldc, int64_t M, int N, int K,
                       int splits, int64_t split_stride, mst_stream_t stream) {
-    return launch_gemm16_splitk(A, ab_dtype, lda, W, ldw, Cpart, ldc, M, N, K, splits, split_stride, (hipStream_t)stream);
+    gemm_args g{A, ab_dtype, lda, W, ldw, nullptr, Cpart, MST_F32, ldc, M, N, K};
+    g.s = (hipStream_t)stream;
+    return launch_gemm16_splitk(g, splits, split_stride);
 }
 int mst_softmax_rows(float* S, const uint8_t* mask, int64_t rows, int L, int rows_per_batch, mst_stream_t stream) {
     MST_CHECK_ARG(S && rows > 0 && L > 0 && rows_per_batch > 0, "softmax_rows: bad arguments");
@@ -611,13 +616,37 @@ struct vit_call {
     int64_t Mc;
     bool blocked;
 
+    // C[rows, n] = epi(A[rows, k] . W[n, k]^T + bias): a linear layer of the compute type on dense rows
+    gemm_args linear(int64_t rows, const void* A, const void* W, const float* bias, void* C, int cdt, int n, int k, int epi = MST_EPI_BIAS) const {
+        gemm_args g{A, dt, k, W, k, bias, C, cdt, n, rows, n, k};
+        g.epi = epi, g.s = s;
+        return g;
+    }
+    // x[rows of pitch ldx] += gamma * (A[rows, k] . W[E, k]^T + bias) on the fp32 residual stream
+    gemm_args residual(int64_t rows, const void* A, const void* W, const float* bias, const float* gamma, int k, int64_t ldx) const {
+        gemm_args g = linear(rows, A, W, bias, x, MST_F32, E, k, MST_EPI_RESIDUAL);
+        g.ldc = ldx, g.gamma = gamma;
+        return g;
+    }
+    // big = A . W^T + bias for this chunk, the q columns scaled for the attention kernels
+    gemm_args qkv_linear(const void* A, const void* W, const float* bias) const {
+        gemm_args g = linear(Mc, A, W, bias, big, dt, 3 * E, E);
+        g.col_scale = qscale, g.scale_cols = E;
+        return g;
+    }
+    // the same layer on e4m3 operands (A and W already quantised) under their per-tensor scales
+    static gemm_args fp8(gemm_args g, const float* a_amax, float w_scale) {
+        g.dt = MST_F8E4M3, g.a_amax = a_amax, g.w_scale = w_scale;
+        return g;
+    }
+
     // big = qkv(norm1 x)                                       block.py:90-91,112
     int qkv(const vit_plan& p, int l) const {
         const mst_vit_layer* L = &w->layers[l];
         if (p.tail == TAIL_FP8_STATIC) {
             const float* am = w->fp8_amax + l * 4;
             RUNK(MST_K_LAYERNORM, launch_layernorm_f8(x, E, L->ln1_w, L->ln1_b, a8, E, Mc, E, 1e-6f, am + 0, s));
-            RUNK(MST_K_GEMM_QKV, launch_gemm8(a8, E, L->qkv_w8, E, L->qkv_b, am + 0, L->w8_scale[0], big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, nullptr, nullptr, s));
+            RUNK(MST_K_GEMM_QKV, launch_gemm8(fp8(qkv_linear(a8, L->qkv_w8, L->qkv_b), am + 0, L->w8_scale[0])));
         } else if (p.tail == TAIL_FP8_DYNAMIC) {
             // every linear layer: quantise its input with a fresh per-tensor scale (this chunk's max|x|), e4m3 GEMM.  The
             // [M,E] inputs are scanned (53 us; a running maximum kept by the one-wave-per-row LayerNorm kernel cost 125 us:
@@ -626,14 +655,14 @@ struct vit_call {
             float* am = amax + l * 4;
             RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln1_w, L->ln1_b, xn, dt, E, Mc, E, 1e-6f, s));
             RUN(launch_quant8(xn, dt, Mc * E, am + 0, a8, 1, s));
-            RUNK(MST_K_GEMM_QKV, launch_gemm8(a8, E, L->qkv_w8, E, L->qkv_b, am + 0, L->w8_scale[0], big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, nullptr, nullptr, s));
+            RUNK(MST_K_GEMM_QKV, launch_gemm8(fp8(qkv_linear(a8, L->qkv_w8, L->qkv_b), am + 0, L->w8_scale[0])));
         } else if (p.fused_ln && blocked && l > 0) {
-            RUNK(MST_K_GEMM_QKV, launch_gemm16_wreg(xn, dt, E, L->qkv_wf, E, L->qkv_bf, big, 3 * E, Mc, 3 * E, qscale, E, s, 1));
+            RUNK(MST_K_GEMM_QKV, launch_gemm16_wreg(qkv_linear(xn, L->qkv_wf, L->qkv_bf), 1));
         } else if (p.fused_ln) {
-            RUNK(MST_K_GEMM_QKV, mst_gemm(xn, dt, E, L->qkv_wf, E, L->qkv_bf, big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, s));
+            RUNK(MST_K_GEMM_QKV, gemm(qkv_linear(xn, L->qkv_wf, L->qkv_bf)));
         } else {
             RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln1_w, L->ln1_b, xn, dt, E, Mc, E, 1e-6f, s));
-            RUNK(MST_K_GEMM_QKV, mst_gemm(xn, dt, E, L->qkv_w, E, L->qkv_b, big, dt, 3 * E, Mc, 3 * E, E, MST_EPI_BIAS, nullptr, qscale, E, s));
+            RUNK(MST_K_GEMM_QKV, gemm(qkv_linear(xn, L->qkv_w, L->qkv_b)));
         }
         return MST_OK;
     }
@@ -645,10 +674,10 @@ struct vit_call {
         char* const a_cls = (char*)xn;
         char* const n_cls = (char*)xn + (size_t)c * E * (dt == MST_F32 ? 4 : 2);
         RUNK(MST_K_ATTENTION, launch_cls_attn(big, dt, c, N, heads, pr, a_cls, log2q, s));
-        RUNK(MST_K_GEMM_PROJ, mst_gemm(a_cls, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, (int64_t)N * E, c, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
+        RUNK(MST_K_GEMM_PROJ, gemm(residual(c, a_cls, L->proj_w, L->proj_b, L->ls1, E, (int64_t)N * E)));
         RUNK(MST_K_LAYERNORM, launch_layernorm(x, (int64_t)N * E, L->ln2_w, L->ln2_b, n_cls, dt, E, c, E, 1e-6f, s));
-        RUNK(MST_K_GEMM_FC1, mst_gemm(n_cls, dt, E, L->fc1_w, E, L->fc1_b, big, dt, 4 * E, c, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, s));
-        RUNK(MST_K_GEMM_FC2, mst_gemm(big, dt, 4 * E, L->fc2_w, 4 * E, L->fc2_b, x, MST_F32, (int64_t)N * E, c, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, s));
+        RUNK(MST_K_GEMM_FC1, gemm(linear(c, n_cls, L->fc1_w, L->fc1_b, big, dt, 4 * E, E, MST_EPI_BIAS_GELU)));
+        RUNK(MST_K_GEMM_FC2, gemm(residual(c, big, L->fc2_w, L->fc2_b, L->ls2, 4 * E, (int64_t)N * E)));
         return MST_OK;
     }
     // x += ls1(proj(attn)); x += ls2(fc2(gelu(fc1(norm2 x))))   block.py:91,93-94,113; the fused forms also write xn = normalise(x) for the next block
@@ -659,21 +688,25 @@ struct vit_call {
             case TAIL_FP8_STATIC: {   // the e4m3 hidden activation lives in `big` (bytes); fc1 reads a8 and writes big, fc2 reads big
                 const float* am = w->fp8_amax + l * 4;
                 RUN(launch_quant8_static(xn, dt, Mc * E, am + 1, a8, s));
-                RUNK(MST_K_GEMM_PROJ, launch_gemm8(a8, E, L->proj_w8, E, L->proj_b, am + 1, L->w8_scale[1], x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, nullptr, nullptr, s));
+                RUNK(MST_K_GEMM_PROJ, launch_gemm8(fp8(residual(Mc, a8, L->proj_w8, L->proj_b, L->ls1, E, E), am + 1, L->w8_scale[1])));
                 RUNK(MST_K_LAYERNORM, launch_layernorm_f8(x, E, L->ln2_w, L->ln2_b, a8, E, Mc, E, 1e-6f, am + 2, s));
-                RUNK(MST_K_GEMM_FC1, launch_gemm8(a8, E, L->fc1_w8, E, L->fc1_b, am + 2, L->w8_scale[2], big, MST_F8E4M3, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, nullptr, am + 3, s));
-                RUNK(MST_K_GEMM_FC2, launch_gemm8(big, 4 * E, L->fc2_w8, 4 * E, L->fc2_b, am + 3, L->w8_scale[3], x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, nullptr, nullptr, s));
+                gemm_args fc1 = fp8(linear(Mc, a8, L->fc1_w8, L->fc1_b, big, MST_F8E4M3, 4 * E, E, MST_EPI_BIAS_GELU), am + 2, L->w8_scale[2]);
+                fc1.c_amax = am + 3;
+                RUNK(MST_K_GEMM_FC1, launch_gemm8(fc1));
+                RUNK(MST_K_GEMM_FC2, launch_gemm8(fp8(residual(Mc, big, L->fc2_w8, L->fc2_b, L->ls2, 4 * E, E), am + 3, L->w8_scale[3])));
                 return MST_OK;
             }
             case TAIL_FP8_DYNAMIC: {
                 float* am = amax + l * 4;
                 RUN(launch_quant8(xn, dt, Mc * E, am + 1, a8, 1, s));
-                RUNK(MST_K_GEMM_PROJ, launch_gemm8(a8, E, L->proj_w8, E, L->proj_b, am + 1, L->w8_scale[1], x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, nullptr, nullptr, s));
+                RUNK(MST_K_GEMM_PROJ, launch_gemm8(fp8(residual(Mc, a8, L->proj_w8, L->proj_b, L->ls1, E, E), am + 1, L->w8_scale[1])));
                 RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
                 RUN(launch_quant8(xn, dt, Mc * E, am + 2, a8, 1, s));
-                RUNK(MST_K_GEMM_FC1, launch_gemm8(a8, E, L->fc1_w8, E, L->fc1_b, am + 2, L->w8_scale[2], big, dt, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, am + 3, nullptr, s));
+                gemm_args fc1 = fp8(linear(Mc, a8, L->fc1_w8, L->fc1_b, big, dt, 4 * E, E, MST_EPI_BIAS_GELU), am + 2, L->w8_scale[2]);
+                fc1.out_amax = am + 3;   // the hidden activation's maximum, for the quantiser below
+                RUNK(MST_K_GEMM_FC1, launch_gemm8(fc1));
                 RUN(launch_quant8(big, dt, Mc * 4 * E, am + 3, a8, 0, s));
-                RUNK(MST_K_GEMM_FC2, launch_gemm8(a8, 4 * E, L->fc2_w8, 4 * E, L->fc2_b, am + 3, L->w8_scale[3], x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, nullptr, nullptr, s));
+                RUNK(MST_K_GEMM_FC2, launch_gemm8(fp8(residual(Mc, a8, L->fc2_w8, L->fc2_b, L->ls2, 4 * E, E), am + 3, L->w8_scale[3])));
                 return MST_OK;
             }
             case TAIL_BLOCK_SINGLE:   // one launch, x read and written once; rows stay in the registers of the wave that owns them
@@ -684,14 +717,14 @@ struct vit_call {
                 RUNK(MST_K_BLOCK_FUSED, launch_block16(x, xn, xn_out, dt, L->proj_pack, L->proj_bf, L->mlp_pack, L->fc1_bf, L->fc2_bf, blk, Mc, E, 1e-6f, s));
                 return MST_OK;
             case TAIL_MLP_FUSED:
-                RUNK(MST_K_GEMM_PROJ, mst_gemm(xn, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
+                RUNK(MST_K_GEMM_PROJ, gemm(residual(Mc, xn, L->proj_w, L->proj_b, L->ls1, E, E)));
                 RUNK(MST_K_MLP_FUSED, launch_mlp16(x, xn_out, dt, L->mlp_pack, L->fc1_bf, L->fc2_bf, Mc, E, 1e-6f, s));
                 return MST_OK;
             case TAIL_UNFUSED:
-                RUNK(MST_K_GEMM_PROJ, mst_gemm(xn, dt, E, L->proj_w, E, L->proj_b, x, MST_F32, E, Mc, E, E, MST_EPI_RESIDUAL, L->ls1, 1.f, 0, s));
+                RUNK(MST_K_GEMM_PROJ, gemm(residual(Mc, xn, L->proj_w, L->proj_b, L->ls1, E, E)));
                 RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
-                RUNK(MST_K_GEMM_FC1, mst_gemm(xn, dt, E, L->fc1_w, E, L->fc1_b, big, dt, 4 * E, Mc, 4 * E, E, MST_EPI_BIAS_GELU, nullptr, 1.f, 0, s));
-                RUNK(MST_K_GEMM_FC2, mst_gemm(big, dt, 4 * E, L->fc2_w, 4 * E, L->fc2_b, x, MST_F32, E, Mc, E, 4 * E, MST_EPI_RESIDUAL, L->ls2, 1.f, 0, s));
+                RUNK(MST_K_GEMM_FC1, gemm(linear(Mc, xn, L->fc1_w, L->fc1_b, big, dt, 4 * E, E, MST_EPI_BIAS_GELU)));
+                RUNK(MST_K_GEMM_FC2, gemm(residual(Mc, big, L->fc2_w, L->fc2_b, L->ls2, 4 * E, E)));
                 return MST_OK;
         }
         return MST_EINVAL;   // not reached: every vit_tail returns above
@@ -748,7 +781,7 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
         // output to the last block's input, the 16-bit rows (attention output, normalised rows) blocked from block 0's attention on.
         // Needs the QKV kernel that reads blocked rows (weights-in-registers form) and every block on the fused path.
         const bool prune = plan.may_prune && c <= 65535;
-        k.blocked = plan.tail == TAIL_BLOCK_SINGLE && !prune && gemm16_wreg_applicable(Mc, 3 * E, E, dt, dt, MST_EPI_BIAS, E, E, 3 * E);
+        k.blocked = plan.tail == TAIL_BLOCK_SINGLE && !prune && gemm16_wreg_applicable(k.qkv_linear(nullptr, nullptr, nullptr));
         // tokens: in the fused pipeline one kernel writes the residual stream AND block 0's plain-normalised rows (k_patch_rows.hip)
         if (plan.fused_ln)
             RUNK(MST_K_PATCH_EMBED, launch_patch_rows16(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, k.x, k.xn, s));
@@ -815,11 +848,16 @@ int mst_slice_fusion(const mst_fusion_weights* w, const float* emb, int B, int D
     float* qkv = (float*)p; p += align_up((size_t)B * L * 3 * e * 4, 256);
     float* feat = (float*)p;
 
+    // C[rows, n] = epi(A[rows, k] . W[n, k]^T + bias) in exact fp32 on dense rows (the residual epilogues add onto C)
+    auto linear32 = [s](const float* A, const float* W, const float* bias, float* C, int64_t rows, int n, int k, int epi) {
+        gemm_args g{A, MST_F32, k, W, k, bias, C, MST_F32, n, rows, n, k};
+        g.epi = epi, g.s = s;
+        return launch_gemm32(g);
+    };
     const float* src = emb;
     if (w->bottleneck_w) {  // dino.py:134-135
         MST_CHECK_ARG(w->emb_in % 16 == 0, "slice_fusion: emb_in=%d must be a multiple of 16", w->emb_in);
-        RUN(launch_gemm32(emb, w->emb_in, w->bottleneck_w, w->emb_in, w->bottleneck_b, eb, e, (int64_t)B * D, e,
-                          w->emb_in, MST_EPI_BIAS, nullptr, 1.f, 0, s));
+        RUN(linear32(emb, w->bottleneck_w, w->bottleneck_b, eb, (int64_t)B * D, e, w->emb_in, MST_EPI_BIAS));
         src = eb;
     } else {
         MST_CHECK_ARG(w->emb_in == e, "slice_fusion: emb_in=%d != emb=%d without a bottleneck", w->emb_in, e);
@@ -837,7 +875,7 @@ int mst_slice_fusion(const mst_fusion_weights* w, const float* emb, int B, int D
         RUN(launch_slice_tokens(src, w->cls_token, w->slice_pos_emb, B, D, e, xs, s));  // dino.py:140-145
         // x = x + out_proj(attn(in_proj(norm1 x)))                 transformer_blocks.py:567,576-582
         RUN(launch_layernorm(xs, e, w->ln1_w, w->ln1_b, y, MST_F32, e, ML, e, 1e-5f, s));
-        RUN(launch_gemm32(y, e, w->in_proj_w, e, w->in_proj_b, qkv, 3 * e, ML, 3 * e, e, MST_EPI_BIAS, nullptr, 1.f, 0, s));
+        RUN(linear32(y, w->in_proj_w, w->in_proj_b, qkv, ML, 3 * e, e, MST_EPI_BIAS));
         if (w->liere_rot) {
             // the reference's LieRE path views [B, 33, heads, hd] and then [B*heads, L, hd] of a permuted tensor:
             // both views fail (RuntimeError) unless D == 32 and B == 1 (rotary_embedding_torch.py:349;
@@ -849,11 +887,11 @@ int mst_slice_fusion(const mst_fusion_weights* w, const float* emb, int B, int D
                           "size and stride for batch %d > 1 (transformer_blocks.py:263)", B);
         }
         RUN(launch_slice_attn(qkv, B, L, w->num_heads, hd, key_padding_mask, w->rope_freqs, w->liere_rot, ao, slice_probs, s));
-        RUN(launch_gemm32(ao, e, w->out_proj_w, e, w->out_proj_b, xs, e, ML, e, e, MST_EPI_RESIDUAL, nullptr, 1.f, 0, s));
+        RUN(linear32(ao, w->out_proj_w, w->out_proj_b, xs, ML, e, e, MST_EPI_RESIDUAL));
         // x = x + linear2(relu(linear1(norm2 x)))                  transformer_blocks.py:568,585-587
         RUN(launch_layernorm(xs, e, w->ln2_w, w->ln2_b, y, MST_F32, e, ML, e, 1e-5f, s));
-        RUN(launch_gemm32(y, e, w->lin1_w, e, w->lin1_b, y2, e, ML, e, e, MST_EPI_BIAS_RELU, nullptr, 1.f, 0, s));
-        RUN(launch_gemm32(y2, e, w->lin2_w, e, w->lin2_b, xs, e, ML, e, e, MST_EPI_RESIDUAL, nullptr, 1.f, 0, s));
+        RUN(linear32(y, w->lin1_w, w->lin1_b, y2, ML, e, e, MST_EPI_BIAS_RELU));
+        RUN(linear32(y2, w->lin2_w, w->lin2_b, xs, ML, e, e, MST_EPI_RESIDUAL));
         // final LayerNorm, row 0 of every volume                   dino.py:95,153
         RUN(launch_layernorm(xs, (int64_t)L * e, w->norm_w, w->norm_b, feat, MST_F32, e, B, e, 1e-5f, s));
     } else if (w->fusion_type == MST_FUSION_LINEAR) {  // dino.py:154-155: 'b d e -> b (d e)'
@@ -871,7 +909,7 @@ int mst_slice_fusion(const mst_fusion_weights* w, const float* emb, int B, int D
         MST_CHECK_ARG(F % 16 == 0, "slice_fusion: feature width %d must be a multiple of 16", F);
         MST_CHECK_ARG(w->head_in <= 0 || F == w->head_in, "slice_fusion: mat1 and mat2 shapes cannot be multiplied (%dx%d and %dx%d)",
                       B, F, w->head_in, w->out_ch);
-        RUN(launch_gemm32(feat, F, w->head_w, F, w->head_b, logits, w->out_ch, B, w->out_ch, F, MST_EPI_BIAS, nullptr, 1.f, 0, s));
+        RUN(linear32(feat, w->head_w, w->head_b, logits, B, w->out_ch, F, MST_EPI_BIAS));
     }
     return MST_OK;
 }

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
+
 #include "../../include/mst_hip.h"
 
 typedef __bf16 bf16_t;
@@ -151,31 +154,95 @@ void mst_allow_lds(const void* kernel, int bytes, mst_lds_once* slot);
 // rounded down to a multiple of 8 (the persistent kernels deal tile ids to the 8 XCDs): the size of a persistent grid.
 int mst_persistent_grid(void);
 
+// ---- linear-layer GEMMs: C[M,N] = epi(A[M,K] . W[N,K]^T + bias) ---------------------------------------------------------------
+// What every launch_gemm* takes (the contract of mst_gemm / mst_gemm_fp8 in include/mst_hip.h).  Fill the operands and the shape; the
+// rest defaults to a plain bias epilogue on the null stream.
+struct gemm_args {
+    const void* A; int dt; int64_t lda;
+    const void* W; int64_t ldw;
+    const float* bias;
+    void* C; int cdt; int64_t ldc;
+    int64_t M; int N, K;
+    int epi = MST_EPI_BIAS;
+    const float* gamma = nullptr;          // residual epilogues: per-column LayerScale (null = 1)
+    float col_scale = 1.f; int scale_cols = 0;   // columns [0, scale_cols) are multiplied by col_scale
+    hipStream_t s = nullptr;
+    // e4m3 operands (launch_gemm8) only
+    const float* a_amax = nullptr; float w_scale = 1.f;   // per-tensor scales: max|A| behind the quantiser, max|W| / 448
+    float* out_amax = nullptr;             // (nullable, 16-bit C, non-residual epilogues) *out_amax = max(*out_amax, max |C as stored|)
+    const float* c_amax = nullptr;         // (cdt == MST_F8E4M3 only) calibrated scale of the e4m3 output
+};
+
+// The runtime (dt, cdt, epi) of a GEMM as the (T, EPI, OutT) of a kernel template: f.template launch<T, EPI, OutT>(g) for the
+// combinations f.template has<T, EPI, OutT>() names -- each file states there which kernels it instantiates; nothing else is compiled.
+// Every launcher has the plain bias epilogue for each operand type it takes, which is how an unknown operand type is told from an
+// unknown epilogue.
+template <typename X> struct gemm_type { typedef X type; };
+constexpr int GEMM_NO_KERNEL = -1;
+template <typename Fn> int gemm_with_type(int dt, Fn fn) {
+    switch (dt) {
+        case MST_F32: return fn(gemm_type<float>{});
+        case MST_F16: return fn(gemm_type<f16_t>{});
+        case MST_BF16: return fn(gemm_type<bf16_t>{});
+        case MST_F8E4M3: return fn(gemm_type<uint8_t>{});
+    }
+    return GEMM_NO_KERNEL;
+}
+template <typename Fn> int gemm_with_epi(int epi, Fn fn) {
+    switch (epi) {
+        case MST_EPI_BIAS: return fn(std::integral_constant<int, MST_EPI_BIAS>{});
+        case MST_EPI_BIAS_GELU: return fn(std::integral_constant<int, MST_EPI_BIAS_GELU>{});
+        case MST_EPI_BIAS_RELU: return fn(std::integral_constant<int, MST_EPI_BIAS_RELU>{});
+        case MST_EPI_RESIDUAL: return fn(std::integral_constant<int, MST_EPI_RESIDUAL>{});
+        case MST_EPI_RESIDUAL_RELU: return fn(std::integral_constant<int, MST_EPI_RESIDUAL_RELU>{});
+    }
+    return GEMM_NO_KERNEL;
+}
+template <typename F> int gemm_dispatch(const char* kernel, const gemm_args& g, const F& f) {
+    bool operand_ok = false;
+    const int rc = gemm_with_type(g.dt, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        operand_ok = F::template has<T, MST_EPI_BIAS, T>() || F::template has<T, MST_EPI_BIAS, float>();
+        return gemm_with_type(g.cdt, [&](auto o) {
+            typedef typename decltype(o)::type OutT;
+            return gemm_with_epi(g.epi, [&](auto e) {
+                constexpr int EPI = decltype(e)::value;
+                if constexpr (F::template has<T, EPI, OutT>()) return f.template launch<T, EPI, OutT>(g);
+                else return GEMM_NO_KERNEL;
+            });
+        });
+    });
+    if (rc != GEMM_NO_KERNEL) return rc;
+    if (operand_ok) mst_set_error("%s: bad epilogue %d", kernel, g.epi);
+    else mst_set_error("%s: bad operand dtype %d", kernel, g.dt);
+    return MST_EINVAL;
+}
+
+// Tile geometry (rows, columns, k per step) the 16-bit router shares with the kernels it chooses between (k_gemm16.hip: gemm16_route)
+struct gemm_tile { int bm, bn, bk; };
+constexpr gemm_tile GEMM16_WREG_TILE{32, 384, 384};   // k_gemm16_wreg.hip: 32-row chunks against a register-resident K = 384 weight slice
+constexpr gemm_tile GEMM16_MID_TILE{128, 384, 32};    // k_gemm16_mid.hip
+constexpr gemm_tile GEMM16_BIG_TILE{256, 384, 32};    // k_gemm16_big.hip
+
+int launch_gemm16(const gemm_args& g);                // k_gemm16.hip: argument checks, then the kernel gemm16_route names
+int launch_gemm16_big(const gemm_args& g);
+int launch_gemm16_mid(const gemm_args& g);
+// the shape rule of the weights-in-registers kernel (operand pointers are not looked at): mst_vit_encode keeps the blocked layout only where it holds
+bool gemm16_wreg_applicable(const gemm_args& g);
+// a_blocked: A in the 16-bit blocked layout of include/mst_hip.h (whole 32-row groups allocated; lda ignored)
+int launch_gemm16_wreg(const gemm_args& g, int a_blocked = 0);
+// fp32 partial products of `splits` K ranges, split_stride elements apart (g: A, W, C = the partials, ldc, M, N, K; no bias, no epilogue)
+int launch_gemm16_splitk(const gemm_args& g, int splits, int64_t split_stride);
+int launch_gemm32(const gemm_args& g);
+bool gemm32_small_applicable(int64_t M, int N, int K);
+int launch_gemm32_small(const gemm_args& g);
+int launch_gemm8(const gemm_args& g);
+
 // kernel launchers shared between translation units (all asynchronous on `s`)
 int launch_layernorm(const float* x, int64_t xs, const float* g, const float* b, void* out, int odt,
                      int64_t os, int64_t rows, int cols, float eps, hipStream_t s);
-int launch_gemm16(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias,
-                  void* C, int cdt, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                  float col_scale, int scale_cols, hipStream_t s);
 int launch_patch_rows16(const void* vol, int idt, int n, int H, int W, const void* wp, int dt, const float* bias, const float* prefix,
                         int n_prefix, const float* pos_patch, float* x, void* xn, hipStream_t s);
-bool gemm16_big_applicable(int64_t M, int N, int K);
-int launch_gemm16_big(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias,
-                      void* C, int cdt, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                      float col_scale, int scale_cols, hipStream_t s);
-bool gemm16_wreg_applicable(int64_t M, int N, int K, int dt, int cdt, int epi, int scale_cols, int64_t lda, int64_t ldc);
-// a_blocked: A in the 16-bit blocked layout of include/mst_hip.h (whole 32-row groups allocated; lda ignored)
-int launch_gemm16_wreg(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
-                       int64_t M, int N, float col_scale, int scale_cols, hipStream_t s, int a_blocked = 0);
-bool gemm16_mid_applicable(int64_t M, int N, int K, int dt, int cdt, int epi);
-int launch_gemm16_mid(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
-                      int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma, float col_scale, int scale_cols,
-                      hipStream_t s);
-int launch_gemm32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
-                  float* C, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                  float col_scale, int scale_cols, hipStream_t s);
-int launch_gemm16_splitk(const void* A, int dt, int64_t lda, const void* W, int64_t ldw, float* Cpart, int64_t ldc, int64_t M, int N, int K,
-                         int splits, int64_t split_stride, hipStream_t s);
 int launch_cvt16(const float* x, int64_t ldx, int64_t rows, int cols, float scale, void* out, int dt, int64_t ldo, int transpose,
                  int64_t rows_pad, hipStream_t s);
 int launch_conv_dgrad32(const float* dz, int n, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, const float* Wt, int H, int W,
@@ -209,18 +276,10 @@ int launch_conv_gemm16(const void* x, int dt, int n, int H, int W, int Cin, int 
                        void* out, int cdt, int Cout, int epi, hipStream_t s);
 int launch_conv_gemm32(const float* x, int n, int H, int W, int Cin, int kh, int kw, int stride, int pad, const float* Wg, int64_t ldw,
                        const float* bias, float* out, int64_t ldc, int Cout, int Kpad, int epi, const float* gamma, hipStream_t s);
-bool gemm32_small_applicable(int64_t M, int N, int K);
-int launch_gemm32_small(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc,
-                        int64_t M, int N, int K, int epi, const float* gamma, float col_scale, int scale_cols, hipStream_t s);
 // scan: 1 = *amax = max(*amax, max|x|) first (one extra pass over x); 0 = *amax already covers x (its producer kept it)
 int launch_quant8(const void* x, int dt, int64_t n, float* amax, void* out8, int scan, hipStream_t s);
 // quantise under a calibrated scale the caller owns (read-only)
 int launch_quant8_static(const void* x, int dt, int64_t n, const float* amax, void* out8, hipStream_t s);
-// out_amax (nullable, 16-bit C, non-residual epilogues): *out_amax = max(*out_amax, max |C as stored|)
-// c_amax (cdt == MST_F8E4M3 only): calibrated scale of the e4m3 output
-int launch_gemm8(const void* A8, int64_t lda, const void* W8, int64_t ldw, const float* bias, const float* a_amax,
-                 float w_scale, void* C, int cdt, int64_t ldc, int64_t M, int N, int K, int epi, const float* gamma,
-                 float col_scale, int scale_cols, float* out_amax, const float* c_amax, hipStream_t s);
 int launch_layernorm_f8(const float* x, int64_t xs, const float* g, const float* b, void* out8, int64_t os, int64_t rows,
                         int cols, float eps, const float* amax, hipStream_t s);
 int launch_amax_merge(float* out, const float* in, int n, hipStream_t s);

@@ -136,6 +136,52 @@ def test_gemm16_big_exact_integers(hip, dt):
     assert torch.equal(got.cpu(), a @ w.t())
 
 
+MID_SHAPE = (65536 + 77, 384, 64)    # 513 tiles of 128 x 384 (the mid kernel starts at 512), ragged last M tile; K = 64 keeps the
+                                     # weights-in-registers kernel out; 257 tiles of 256 x 384 would satisfy the big kernel too
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+def test_gemm16_mid_tile_path(hip, dt):
+    """The 128 x 384 kernel (16-bit output of the operand type, bias and ReLU epilogues) with the weights-in-registers kernel
+    declining: the plain epilogue with q-scaled columns, and ReLU."""
+    tdt = DT[dt]
+    M, N, K = MID_SHAPE
+    a = rnd((M, K), 24).to(tdt)
+    w = (rnd((N, K), 25) / math.sqrt(K)).to(tdt)
+    bias = rnd((N,), 26) * 0.1
+    ac, wc, bc = a.cuda(), w.cuda(), bias.cuda()
+    got = hip.gemm(ac, wc, bc, epilogue=0, out_dtype=tdt, col_scale=0.125, scale_cols=128)
+    assert scaled_err(got, _gemm_ref(a, w, bias, 0, col_scale=0.125, scale_cols=128)) < OUT_TOL[tdt]
+    got = hip.gemm(ac, wc, bc, epilogue=2, out_dtype=tdt)
+    assert scaled_err(got, _gemm_ref(a, w, bias, 2)) < OUT_TOL[tdt]
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("f32out", [False, True])
+def test_gemm16_mid_exact_integers(hip, dt, f32out):
+    """Entries 1 and 2 in A against |w| <= 18: every result is an integer of at most 54, exact in bf16 and fp16.  The 16-bit
+    output runs the 128 x 384 kernel; the fp32 output of the same operands leaves it (the persistent 256 x 384 kernel) and is exact too."""
+    tdt = DT[dt]
+    M, N, K = MID_SHAPE
+    a = torch.zeros(M, K)
+    a[torch.arange(M), torch.arange(M) % K] = 1.0
+    a[torch.arange(M), (torch.arange(M) * 7 + 3) % K] += 2.0
+    w = (torch.arange(N)[:, None] % 13 - 6) * 1.0 + (torch.arange(K)[None, :] % 7) * 2.0
+    odt = torch.float32 if f32out else tdt
+    got = hip.gemm(a.to(tdt).cuda(), w.to(tdt).cuda(), None, out_dtype=odt)
+    assert got.dtype == odt
+    assert torch.equal(got.cpu(), (a @ w.t()).to(odt))
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("M", [9605, 257])
+def test_gemm16_tile_width(hip, dt, M):
+    """Both widths of the 128 x 128 kernel at K = 64: 9605 rows are 76 x 3 = 228 workgroups (128 wide from 224 on) and 38 tiles of
+    256 x 384 (too few for the persistent kernel); 257 rows take the 128 x 64 form.  Every epilogue, the residual one with and without
+    gamma, both output types, at the bars of test_gemm16_epilogues."""
+    test_gemm16_epilogues(hip, dt, M, 384, 64)
+
+
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
 def test_gemm16_exact_integers_asymmetric(hip, dt):
     """A = [I | 0] against an asymmetric integer W: catches any row/col or k-order swap exactly."""
