@@ -198,6 +198,17 @@ int mst_conv_wgrad16(const void* dz, const void* x, int dtype, int n, int H, int
                      int nsplit, int64_t rows_per_split, mst_stream_t stream);
 int mst_conv_dgrad(const void* dz, int dtype, int n, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, const void* Wt, int H, int W,
                    int Cin, float* dx, mst_stream_t stream);
+/* mst_conv_dgrad_stem: d input of a THIN-input convolution (Cin 1, 2 or 3, where mst_conv_dgrad needs Cin % 4 == 0): the stem of the ResNet
+ * models -- torchvision's conv1, 7 x 7, stride 2, padding 3, 64 output channels, on the grey slice that reference resnet.py:176 repeats into
+ * three channels (folded: one channel, the three kernels summed) or on three real channels (plain ResNet).  The last link of the gradient
+ * with respect to the input volume.  dz [n,Ho,Wo,Cout] and Wg [Cout, kh*kw*Cin] -- the FORWARD's GEMM weight in (ky, kx, c) order, dense
+ * rows -- of `dtype` (f32 / bf16 / f16; 16-bit operands are widened and multiplied on the exact fp32 MFMA); dx fp32 [n,H,W,Cin], every
+ * element written exactly once.  Per tile of input pixels the product dz . Wg of the output positions that reach it stays in LDS and each
+ * pixel gathers its taps in ascending (ky, kx) order: no atomics, no workspace, and the summation order is fixed by the shape arguments,
+ * so the determinism contract below holds without an _ordered twin.  Cin in {1,2,3}, kh = kw <= 7, stride 1 or 2, 0 <= pad < kh, Cout 16,
+ * 32 or 64; anything else is MST_EINVAL. */
+int mst_conv_dgrad_stem(const void* dz, int dtype, int n, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, const void* Wg, int H,
+                        int W, int Cin, float* dx, mst_stream_t stream);
 int mst_maxpool_nhwc(const float* x, int n, int H, int W, int C, float* y, mst_stream_t stream);
 int mst_avgpool_nhwc(const float* x, int n, int HW, int C, float* y, mst_stream_t stream);
 /* Training step of the backbone (BASELINE configs[3]; what torch.autograd + nn.BatchNorm2d(train) do for the reference):

@@ -321,6 +321,11 @@ int mst_conv_dgrad(const void* dz, int dtype, int n, int Ho, int Wo, int Cout, i
         return launch_conv_dgrad32((const float*)dz, n, Ho, Wo, Cout, kh, kw, stride, pad, (const float*)Wt, H, W, Cin, dx, (hipStream_t)stream);
     return launch_conv_dgrad16(dz, dtype, n, Ho, Wo, Cout, kh, kw, stride, pad, Wt, H, W, Cin, dx, (hipStream_t)stream);
 }
+// the stem's data gradient (reference resnet.py:176 + torchvision's conv1): the last link of the gradient with respect to the input volume
+int mst_conv_dgrad_stem(const void* dz, int dtype, int n, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, const void* Wg, int H,
+                        int W, int Cin, float* dx, mst_stream_t stream) {
+    return launch_conv_dgrad_stem(dz, dtype, n, Ho, Wo, Cout, kh, kw, stride, pad, Wg, H, W, Cin, dx, (hipStream_t)stream);
+}
 int mst_conv_wgrad(const float* dz, const float* x, int n, int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, float* part,
                    int nsplit, int64_t rows_per_split, mst_stream_t stream) {
     return launch_conv_wgrad32(dz, x, n, H, W, Cin, kh, kw, stride, pad, Cout, part, nsplit, rows_per_split, (hipStream_t)stream);

@@ -249,6 +249,8 @@ int launch_conv_dgrad32(const float* dz, int n, int Ho, int Wo, int Cout, int kh
                         int Cin, float* dx, hipStream_t s);
 int launch_conv_dgrad16(const void* dz, int dt, int n, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, const void* Wt, int H, int W,
                         int Cin, float* dx, hipStream_t s);
+int launch_conv_dgrad_stem(const void* dz, int dt, int n, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, const void* Wg, int H, int W,
+                           int Cin, float* dx, hipStream_t s);   // k_conv_stem_dgrad.hip
 int launch_conv_wgrad32(const float* dz, const float* x, int n, int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, float* part,
                         int nsplit, int64_t rows_per_split, hipStream_t s);
 int launch_conv_wgrad16(const void* dz, const void* x, int dt, int n, int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, float* part,

@@ -114,6 +114,7 @@ SIGNATURES = {
     "mst_conv_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp]),
     "mst_conv_wgrad16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp]),
     "mst_conv_dgrad": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "mst_conv_dgrad_stem": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     "mst_maxpool_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_avgpool_nhwc": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mst_batchnorm_train": (_i, [_vp, _i64, _i, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -945,6 +946,37 @@ def conv_dgrad(dz: torch.Tensor, wt: torch.Tensor, k: int, stride: int, pad: int
     dx = torch.empty((n, H, W, Cin), dtype=torch.float32, device=dz.device)
     _check(load().mst_conv_dgrad(ptr(dz), dt_of(dz), n, Ho, Wo, Cout, k, k, stride, pad, ptr(wt), H, W, Cin, ptr(dx), stream_of(dz)), "mst_conv_dgrad")
     return dx
+
+
+def conv_dgrad_stem(dz: torch.Tensor, wg: torch.Tensor, k: int, stride: int, pad: int, H: int, W: int, Cin: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mst_conv_dgrad_stem: gradient of a thin-input convolution's input (Cin 1, 2 or 3: the ResNet stem) from dz [n,Ho,Wo,Cout] (fp32 /
+    bf16 / fp16) and the forward's GEMM weight wg [Cout, k*k*Cin] in (ky, kx, c) order, of dz's type -> dx [n,H,W,Cin] fp32.  Every element
+    of `out` is written; no atomics, no workspace."""
+    if not isinstance(dz, torch.Tensor) or not isinstance(wg, torch.Tensor):
+        raise TypeError("conv_dgrad_stem: dz and wg must be tensors")
+    if dz.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise TypeError(f"conv_dgrad_stem: dz is {dz.dtype} (fp32, bf16 or fp16)")
+    if wg.dtype != dz.dtype:
+        raise TypeError(f"conv_dgrad_stem: dz is {dz.dtype}, wg is {wg.dtype}")
+    if dz.dim() != 4:
+        raise ValueError(f"conv_dgrad_stem: dz must be [n, Ho, Wo, Cout], got {tuple(dz.shape)}")
+    n, Ho, Wo, Cout = dz.shape
+    if tuple(wg.shape) != (Cout, k * k * Cin) or wg.device != dz.device:
+        raise ValueError(f"conv_dgrad_stem: weight {tuple(wg.shape)} on {wg.device} does not match [Cout, k*k*Cin] = [{Cout}, {k * k * Cin}] on {dz.device}")
+    if not dz.is_cuda:
+        raise ValueError(f"conv_dgrad_stem: tensors must live on a HIP device (got {dz.device}); the MST kernels have no CPU path")
+    if not dz.is_contiguous() or not wg.is_contiguous():
+        raise ValueError("conv_dgrad_stem: dz and wg must be contiguous")
+    if (Ho, Wo) != ((H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1):
+        raise ValueError(f"conv_dgrad_stem: dz {Ho} x {Wo} is not the output of a {H} x {W} input (k {k}, stride {stride}, padding {pad})")
+    if out is None:
+        out = torch.empty((n, H, W, Cin), dtype=torch.float32, device=dz.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, H, W, Cin) or out.device != dz.device:
+        raise ValueError(f"conv_dgrad_stem: out must be contiguous fp32 [{n}, {H}, {W}, {Cin}] on dz's device")
+    _check(load().mst_conv_dgrad_stem(ptr(dz), dt_of(dz), n, Ho, Wo, Cout, k, k, stride, pad, ptr(wg), H, W, Cin, ptr(out), stream_of(dz)),
+           "mst_conv_dgrad_stem")
+    return out
 
 
 def conv_wgrad(dz: torch.Tensor, x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor:

@@ -20,12 +20,16 @@ fixture of the reference's own ``TransformerEncoderLayer`` (tests/golden/resnet_
 
   training   with gradients enabled in train mode the output carries one autograd node (mst/train_resnet.py): BatchNorm with batch
              statistics, convolution / pooling / slice-transformer backward in HIP kernels (BASELINE configs[3]'s step).
+  d source   ``source.grad`` / ``torch.autograd.grad(logits, source)``: the training node returns the gradient of the images too (the stem's
+             data gradient: ``mst_conv_dgrad_stem``); a FROZEN model whose floating source requires grad routes to the training node in
+             ``.train()`` (batch statistics, as torch would; pruned to the d x chain) and to the eval node in ``.eval()`` (folded BatchNorm,
+             fp32 whatever ``compute_dtype`` is: mst/train_resnet.py::_ResNetEvalFunction); ``save_attn=True`` stays on the inference path.
   Grad-CAM++ ``save_attn=True`` (resnet.py:62-118): the map of the LAST ReLU output -- the one ``get_attention_maps`` returns --
              by ``mst_gradcampp``; the maps of the earlier ReLUs, which the reference computes and never exposes, are not produced.
 
 Bottleneck ResNets (model 50 / 101 / 152: 2048-wide slice embeddings, 16 heads of 128) run through the same kernels (round 3).
-Not built (raise): the MONAI branches (3-D, and ``pretrained=False`` in the reference), a
-backward pass through eval-mode BatchNorm (gradients with ``model.eval()``).  ``pretrained=True`` needs torchvision's weights (network / hub cache); when torchvision is absent the tree
+Not built (raise): the MONAI branches (3-D, and ``pretrained=False`` in the reference), parameter
+gradients through eval-mode BatchNorm (trainable parameters with ``model.eval()``).  ``pretrained=True`` needs torchvision's weights (network / hub cache); when torchvision is absent the tree
 is initialised like torchvision's and a warning says so -- a checkpoint's ``state_dict`` replaces it anyway.
 """
 from __future__ import annotations
@@ -192,14 +196,15 @@ class ResNet(BasicClassifier):
             warnings.warn("ResNet(pretrained=False): the reference builds a MONAI resnet here; this build keeps the torchvision "
                           "parameter layout with torchvision's initialisation")
         self._prep = None
+        self._prep32 = None
         self._epoch = 0
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
     def _invalidate(self):
-        self._prep = None
+        self._prep = self._prep32 = None
 
     def _apply(self, fn, *args, **kwargs):
-        self._prep = None
+        self._prep = self._prep32 = None
         return super()._apply(fn, *args, **kwargs)
 
     # ---- backbone -------------------------------------------------------------------------------------------------------
@@ -212,11 +217,16 @@ class ResNet(BasicClassifier):
             v += t._version + (t.data_ptr() & 0xFFFF)
         return v
 
-    def _prepare(self, sum_in: bool):
-        cdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[self.compute_dtype_name]
-        key = (sum_in, str(self.device), self._state_version(), self.compute_dtype_name)
-        if self._prep is not None and self._prep["key"] == key:
-            return self._prep
+    def _prepare(self, sum_in: bool, fp32: bool = False):
+        """The BatchNorm-folded weights in compute_dtype (cached in ``_prep``).  fp32: in fp32 whatever compute_dtype is -- what the
+        eval-mode gradient node runs on; the same cache when compute_dtype is fp32, ``_prep32`` beside it otherwise."""
+        slot = "_prep32" if fp32 and self.compute_dtype_name != "fp32" else "_prep"
+        name = "fp32" if fp32 else self.compute_dtype_name
+        cdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[name]
+        key = (sum_in, str(self.device), self._state_version(), name)
+        cached = getattr(self, slot, None)
+        if cached is not None and cached["key"] == key:
+            return cached
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError(f"ResNet runs on an MI355X only: parameters are on {dev}; call .to('cuda'). There is no CPU fallback.")
@@ -233,7 +243,7 @@ class ResNet(BasicClassifier):
                 prep["blocks"].append(e)
         if not isinstance(m.fc, nn.Identity):
             prep["fc"] = (m.fc.weight.detach().to(dev, torch.float32).contiguous(), m.fc.bias.detach().to(dev, torch.float32).contiguous())
-        self._prep = prep
+        setattr(self, slot, prep)
         return prep
 
     def _features(self, x_nhwc: torch.Tensor, sum_in: bool, keep_last: bool = False) -> torch.Tensor:
@@ -303,6 +313,15 @@ class ResNet(BasicClassifier):
                                       "training step or run the forward under torch.no_grad()")
         return True
 
+    def _source_grad_route(self, x: torch.Tensor, save_attn: bool) -> Optional[str]:
+        """No parameter requires grad (``_wants_grad`` was False): does the SOURCE ask for a gradient?  'train' (.train(): the training
+        node with batch statistics, as torch would, pruned to the d x chain), 'eval' (.eval(): the frozen-model node on the folded
+        BatchNorm, mst/train_resnet.py::_ResNetEvalFunction) or None: the inference path -- also for ``save_attn=True``, whose Grad-CAM++
+        maps come from the inference forward."""
+        if save_attn or not torch.is_grad_enabled() or not (x.is_floating_point() and x.requires_grad):
+            return None
+        return "train" if self.training else "eval"
+
     def _gradcam(self, out: torch.Tensor, fc_weight: Optional[torch.Tensor]):
         """resnet.py:66-70 + 93-118 for the last ReLU: attention_maps[-1] = [N, 1, h, w]."""
         h, w = self._last_hw
@@ -324,6 +343,10 @@ class ResNet(BasicClassifier):
                                           "torch.no_grad()")
             from .. import train_resnet
             return train_resnet.forward_with_grad(self, x, False)
+        route = self._source_grad_route(x, save_attn)
+        if route is not None:                            # a frozen model, a source that requires grad: d logits / d source
+            from .. import train_resnet
+            return (train_resnet.forward_with_grad if route == "train" else train_resnet.forward_eval_with_grad)(self, x, False)
         feat = self._features(x, False, keep_last=save_attn)
         p = self._prep
         out = hip.gemm(feat, p["fc"][0], p["fc"][1], epilogue=hip.EPI_BIAS) if "fc" in p else feat
@@ -382,7 +405,7 @@ class ResNetSliceTrans(ResNet):
         self._fw = None
 
     def _invalidate(self):
-        self._prep = None
+        self._prep = self._prep32 = None
         self._fw = None
 
     def _apply(self, fn, *args, **kwargs):
@@ -449,6 +472,11 @@ class ResNetSliceTrans(ResNet):
                                           "under torch.no_grad()")
             from .. import train_resnet
             return train_resnet.forward_with_grad(self, x, True, B, D, src_key_padding_mask)
+        route = self._source_grad_route(x, save_attn)
+        if route is not None:                            # a frozen model, a source that requires grad: d logits / d source
+            from .. import train_resnet
+            fwd = train_resnet.forward_with_grad if route == "train" else train_resnet.forward_eval_with_grad
+            return fwd(self, x, True, B, D, src_key_padding_mask)
         emb = self._features(x, True, keep_last=save_attn)
         if save_attn:
             self._gradcam(emb, None)                     # super().forward(x, save_attn=True) with fc = Identity (resnet.py:181)

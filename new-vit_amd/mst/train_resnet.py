@@ -8,7 +8,8 @@ forward runs the model op by op through the C ABI and whose backward produces ev
                                                      Wg = weight in (ky, kx, c) order)
      backward      dWg = dz^T . im2col(x) as an implicit GEMM too (mst_conv_wgrad: pixel-split partial products reduced by mst_colsum),
                    dx = the stride-1 convolution of the stride-dilated dz with the flipped, transposed weight (mst_conv_dgrad); the
-                   stem and MST_CONV_IM2COL=1 keep the explicit forms (mst_im2col_nhwc + mst_gemm_ex, mst_col2im_nhwc)
+                   stem's dW and MST_CONV_IM2COL=1 keep the explicit forms (mst_im2col_nhwc + mst_gemm_ex, mst_col2im_nhwc); the stem's
+                   dx -- only when the source asks for a gradient -- is mst_conv_dgrad_stem (per-tile dz . Wg in LDS, gathered: no atomics)
      16-bit        a 16-bit train_precision: the three products on 16-bit MFMA operands with fp32 accumulation (mst_conv_gemm16,
                    mst_conv_dgrad, mst_conv_wgrad16)
   BatchNorm2d      batch statistics + running-stat update (mst_batchnorm_train), residual add and ReLU in the same pass
@@ -21,6 +22,12 @@ BatchNorm in train mode normalises over ALL (B D) images of the step, so the ste
 resident (fp32 NHWC; about 60 MB per 224^2 image for resnet34 -- sized for 288 GB of HBM; the mixed mode keeps a 16-bit image of every
 convolution input beside it).  Checked against torch.autograd of oracle/resnet_oracle.py on every parameter (tests/test_resnet_gpu.py).
 
+Gradient with respect to the input volume: the node returns d x_nhwc when its source requires grad (`backbone_bwd(need_source=True)`),
+and torch carries it through the model's own float() / permute / reshape to the source's shape, dtype and device.  The backward is pruned
+to what is asked for (`_Grads(needed=...)` from needs_input_grad): a frozen model's source-only backward forms no weight gradient.  A frozen
+model in eval mode has its own node on the BatchNorm-folded weights (`_ResNetEvalFunction`, fp32, chunked like the inference forward).
+Checked against float64 torch.autograd through the oracle (tests/test_resnet_input_grad_gpu.py).
+
 The mode (train_precision, train_storage and the autocast rule) is described, validated and resolved in mst/train_mode.py;
 `forward_train` resolves it once and the saved state and every unit's record carry it to the backward.
 
@@ -32,7 +39,7 @@ loss, gradients, running statistics -- is bit-reproducible.  Flag off: the atomi
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Set
 
 import torch
 import torch.nn as nn
@@ -126,7 +133,10 @@ def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool 
     G.put(bn.bias, db)
     implicit = st16 or os.environ.get("MST_CONV_IM2COL", "0") != "1"    # the explicit im2col / col2im forms are fp32 storage's
     col = None
-    if rec["col16"] is not None:                                         # the stem's 16-bit product: d weight over its 16-bit im2col "pixels"
+    dwg = None
+    if not G.need(conv.weight):                                          # pruned (a frozen model's source-only backward): the d x chain alone
+        pass
+    elif rec["col16"] is not None:                                       # the stem's 16-bit product: d weight over its 16-bit im2col "pixels"
         dwg = hip.conv_wgrad(dz16, rec["col16"], 1, 1, 0)
         if not st16:                                                     # fp32 storage hands on a [Cout, kpad] matrix like its other forms
             kpad, dwg64 = wg.shape[1], dwg
@@ -146,17 +156,25 @@ def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool 
         hip.gemm_ex(dz, col, part, Cout, kpad, ch, sa=(1, Cout), sb=(kpad, 1), sc=(kpad, 1), nb=(s1, s2), ba=(hw * Cout, ch * Cout),
                     bb=(hw * kpad, ch * kpad), bc=(s2 * Cout * kpad, Cout * kpad))
         dwg = hip.colsum(part, torch.zeros(Cout * kpad, dtype=torch.float32, device=dev)).view(Cout, kpad)
-    dw = dwg[:, :k * k * Cin].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
-    if rec["sum_in"]:
-        dw = dw.expand(Cout, conv.weight.shape[1], k, k)                  # w_eff = sum over the identical input channels
-    G.put(conv.weight, dw.contiguous())
+    if dwg is not None:
+        dw = dwg[:, :k * k * Cin].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
+        if rec["sum_in"]:
+            dw = dw.expand(Cout, conv.weight.shape[1], k, k)              # w_eff = sum over the identical input channels
+        G.put(conv.weight, dw.contiguous())
     if not need_dx:
         return None
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    g = dz if mp is None else dz16
+    if Cin < 4 and implicit:
+        # the stem (one input channel after the gray fold, or three): mst_conv_dgrad_stem multiplies dz by the FORWARD's GEMM weight (the
+        # identical channels' kernels summed, then rounded to the operand type) per tile and gathers the taps from LDS -- no [rows, Kpad]
+        # gradient matrix, no atomics; in fp32, mixed precision and 16-bit storage alike
+        del col
+        wstem = (wg if wg is not None else _gemm_weight(conv, rec["sum_in"]))[:, :k * k * Cin].to(g.dtype).contiguous()
+        return hip.conv_dgrad_stem(g.view(n, Ho, Wo, Cout), wstem, k, stride, pad, H, W, Cin)
     if st16 or (implicit and Cout % 16 == 0 and Cin % 4 == 0 and stride in (1, 2)):
         # d input as a convolution of dz with the flipped, transposed weight (mst_conv_dgrad): no gradient matrix, no atomics
         del col
-        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        g = dz if mp is None else dz16
         return hip.conv_dgrad(g.view(n, Ho, Wo, Cout), hip.conv_dgrad_weight(conv.weight, g.dtype), k, stride, pad, H, W)
     kpad = wg.shape[1]
     if col is None:
@@ -198,7 +216,9 @@ def backbone_fwd(m, x_nhwc: torch.Tensor, sum_in: bool, mp: Optional[torch.dtype
     return hip.avgpool_nhwc(y), sv
 
 
-def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor):
+def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor, need_source: bool = False) -> Optional[torch.Tensor]:
+    """Parameter gradients into G (those it needs).  need_source: the stem unit hands back the gradient of the input images [n,H,W,C]
+    (mst_conv_dgrad_stem); parameter gradients are computed exactly as without it."""
     y = sv["last"]
     n, H, W, Cc = y.shape
     dy = hip.avgpool_bwd_nhwc(dfeat.contiguous(), H * W).view(n * H * W, Cc)
@@ -215,7 +235,7 @@ def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor):
         hip.axpby_cols(d1.view(1, -1), dx.view(1, -1))
         dy = dx.view(-1, dx.shape[-1])
     dstem = hip.maxpool_bwd_nhwc(sv["pool_in"], dy.view(sv["units"][0][0]["x"].shape))
-    _conv_bn_bwd(G, sv["stem"], dstem.view(-1, dstem.shape[-1]), False, False)
+    return _conv_bn_bwd(G, sv["stem"], dstem.view(-1, dstem.shape[-1]), need_source, False)
 
 
 # ---- whole models ------------------------------------------------------------------------------------------------------
@@ -236,8 +256,10 @@ def forward_train(model, x_nhwc: torch.Tensor, sum_in: bool, B: Optional[int], D
     return hip.gemm(fused, model.linear.weight.detach(), model.linear.bias.detach()), sv
 
 
-def backward_train(model, sv, dout: torch.Tensor):
-    G = _Grads()
+def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = None, need_source: bool = False):
+    """-> ({id(param): grad}, d x_nhwc or None).  needed: ids of the parameters whose gradient is asked for (None: all); the products
+    behind the others are skipped, so a frozen model's source-only backward is the d x chain alone."""
+    G = _Grads(needed=needed)
     if "fusion" in sv:
         from .models.resnet import SLICE_HEADS
         dfused = G.lin_bwd(dout, sv["fused"], model.linear)
@@ -245,11 +267,14 @@ def backward_train(model, sv, dout: torch.Tensor):
     else:
         fc = model.model.fc
         dfeat = dout if isinstance(fc, nn.Identity) else G.lin_bwd(dout, sv["feat"], fc)
-    backbone_bwd(G, sv, dfeat)
-    return G.by_param
+    dx = backbone_bwd(G, sv, dfeat, need_source)
+    return G.by_param, dx
 
 
 class _ResNetFunction(torch.autograd.Function):
+    """One autograd node for the training-mode model: inputs are the parameters and the NHWC fp32 images x_nhwc.  Its gradient goes back
+    through the model's own float() / permute / reshape to the source's shape, dtype and device (torch.autograd)."""
+
     @staticmethod
     def forward(ctx, model, x_nhwc, sum_in, B, D, mask, *params):
         with torch.no_grad():
@@ -259,13 +284,159 @@ class _ResNetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        needed = {id(p) for p, need in zip(ctx.params, ctx.needs_input_grad[6:]) if need}
+        need_source = bool(ctx.needs_input_grad[1])
         with torch.no_grad():
-            grads = backward_train(ctx.model, ctx.saved, dout.contiguous().float())
+            grads, dx = backward_train(ctx.model, ctx.saved, dout.contiguous().float(), needed, need_source)
         ctx.saved = None
-        return (None, None, None, None, None, None, *route_grads(grads, ctx.params, ctx.needs_input_grad[6:]))
+        return (None, dx, None, None, None, None, *route_grads(grads, ctx.params, ctx.needs_input_grad[6:]))
 
 
 def forward_with_grad(model, x_nhwc, sum_in: bool, B=None, D=None, mask=None):
     model._invalidate()                                  # a training step follows: the BatchNorm-folded inference weights are stale after it
     params = fp32_device_params(model)
     return _ResNetFunction.apply(model, x_nhwc, sum_in, B, D, mask, *params)
+
+
+# ---- eval mode: the gradient of a frozen model's output with respect to its input volume --------------------------------------------------
+def _folded_dgrad_weight(prep, key, w: torch.Tensor, k: int, Cin: int) -> torch.Tensor:
+    """The folded GEMM weight [Cout, (ky, kx, c)] re-laid as mst_conv_dgrad's operand [Cin, (ky', kx', co)] (both kernel axes flipped, what
+    hip.conv_dgrad_weight builds from a [Cout, Cin, k, k] weight); cached in the prepared weights beside it."""
+    cache = prep.setdefault("dgrad", {})
+    if key not in cache:
+        Cout = w.shape[0]
+        cache[key] = w[:, :k * k * Cin].reshape(Cout, k, k, Cin).flip(1, 2).permute(3, 1, 2, 0).reshape(Cin, k * k * Cout).contiguous()
+    return cache[key]
+
+
+def _eval_backbone_fwd(model, x_nhwc: torch.Tensor, sum_in: bool):
+    """ResNet._features in fp32 on the folded weights, keeping every ReLU output (its mask) per chunk of `chunk_images` images.  The
+    inference forward forms relu(identity + .) in place on the unit's dead input, which would destroy the previous unit's mask: here the
+    sum is formed on a copy, by the same kernels on the same operands -- the features are those of the inference forward bit for bit."""
+    from .models.resnet import _conv
+    p = model._prepare(sum_in, fp32=True)
+    feats, chunks = [], []
+    for i0 in range(0, x_nhwc.shape[0], model.chunk_images):
+        x = x_nhwc[i0:i0 + model.chunk_images].contiguous()
+        n, H, W, Cin = x.shape
+        w, b, kpad = p["stem"]
+        Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+        y0 = hip.gemm(hip.im2col_nhwc(x, 7, 7, 2, 3, kpad), w, b, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, 64)
+        y = hip.maxpool_nhwc(y0)
+        units = []
+        for bi, e in enumerate(p["blocks"]):
+            n, H1, W1, C1 = y.shape
+            s = e["stride"]
+            H2, W2 = (H1 + 2 - 3) // s + 1, (W1 + 2 - 3) // s + 1
+            w1, b1, k1 = e["c1"]
+            w2, b2, k2 = e["c2"]
+            h0 = None
+            if "c3" in e:
+                h0 = _conv(x=y, w=w1, b=b1, k=1, stride=1, pad=0, kpad=k1, epilogue=hip.EPI_BIAS_RELU).view(n, H1, W1, w1.shape[0])
+                h1 = _conv(x=h0, w=w2, b=b2, k=3, stride=s, pad=1, kpad=k2, epilogue=hip.EPI_BIAS_RELU).view(n, H2, W2, w2.shape[0])
+                wl, bl, kl = e["c3"]
+            else:
+                h1 = _conv(x=y, w=w1, b=b1, k=3, stride=s, pad=1, kpad=k1, epilogue=hip.EPI_BIAS_RELU).view(n, H2, W2, w1.shape[0])
+                wl, bl, kl = e["c2"]
+            if "ds" in e:
+                wd, bd, kd = e["ds"]
+                idt = _conv(x=y, w=wd, b=bd, k=1, stride=s, pad=0, kpad=kd, epilogue=hip.EPI_BIAS)
+            else:
+                idt = y.reshape(n * H1 * W1, C1).clone()         # y carries the previous unit's ReLU mask: the sum goes into a copy
+            kl_ = 1 if "c3" in e else 3
+            _conv(x=h1, w=wl, b=bl, k=kl_, stride=1, pad=kl_ // 2, kpad=kl, epilogue=hip.EPI_RESIDUAL_RELU, out=idt)  # relu(identity + .)
+            yo = idt.view(n, H2, W2, wl.shape[0])
+            units.append({"bi": bi, "e": e, "in": (n, H1, W1, C1), "h0": h0, "h1": h1, "y": yo})
+            y = yo
+        feats.append(hip.avgpool_nhwc(y))
+        chunks.append({"x": (n, H, W, Cin), "y0": y0, "units": units})
+    return (torch.cat(feats, dim=0) if len(feats) > 1 else feats[0]), {"prep": p, "chunks": chunks}
+
+
+def _eval_backbone_bwd(sv, dfeat: torch.Tensor) -> torch.Tensor:
+    """d features [n, C] -> d x_nhwc: per unit mst_act_bwd on the saved ReLU output, then mst_conv_dgrad with the folded weight; the
+    shortcut sums; mst_maxpool_bwd_nhwc; the stem through mst_conv_dgrad_stem.  No parameter gradient is formed."""
+    p = sv["prep"]
+    outs = []
+    i0 = 0
+    for ch in sv["chunks"]:
+        n, H, W, Cin = ch["x"]
+        last = ch["units"][-1]["y"]
+        hw = last.shape[1] * last.shape[2]
+        dy = hip.avgpool_bwd_nhwc(dfeat[i0:i0 + n].contiguous(), hw).view(n * hw, last.shape[3])
+        i0 += n
+        for u in reversed(ch["units"]):
+            e, bi = u["e"], u["bi"]
+            _, H1, W1, C1 = u["in"]
+            _, H2, W2, C2 = u["y"].shape
+            s = e["stride"]
+            hip.act_bwd(u["y"], dy, 1)
+            dy4 = dy.view(n, H2, W2, C2)
+            if u["h0"] is not None:                          # bottleneck: 1x1 <- 3x3 (stride) <- 1x1
+                wm = u["h1"].shape[3]
+                d = hip.conv_dgrad(dy4, _folded_dgrad_weight(p, (bi, "c3"), e["c3"][0], 1, wm), 1, 1, 0, H2, W2)
+                hip.act_bwd(u["h1"], d, 1)
+                d = hip.conv_dgrad(d, _folded_dgrad_weight(p, (bi, "c2"), e["c2"][0], 3, wm), 3, s, 1, H1, W1)
+                hip.act_bwd(u["h0"], d, 1)
+                d1 = hip.conv_dgrad(d, _folded_dgrad_weight(p, (bi, "c1"), e["c1"][0], 1, C1), 1, 1, 0, H1, W1)
+            else:                                            # basic: 3x3 <- 3x3 (stride)
+                d = hip.conv_dgrad(dy4, _folded_dgrad_weight(p, (bi, "c2"), e["c2"][0], 3, C2), 3, 1, 1, H2, W2)
+                hip.act_bwd(u["h1"], d, 1)
+                d1 = hip.conv_dgrad(d, _folded_dgrad_weight(p, (bi, "c1"), e["c1"][0], 3, C1), 3, s, 1, H1, W1)
+            if "ds" in e:
+                dsx = hip.conv_dgrad(dy4, _folded_dgrad_weight(p, (bi, "ds"), e["ds"][0], 1, C1), 1, s, 0, H1, W1)
+                hip.axpby_cols(dsx.view(1, -1), d1.view(1, -1))
+            else:
+                hip.axpby_cols(dy.view(1, -1), d1.view(1, -1))
+            dy = d1.view(n * H1 * W1, C1)
+        y0 = ch["y0"]
+        dstem = hip.maxpool_bwd_nhwc(y0, dy.view(ch["units"][0]["in"]))
+        hip.act_bwd(y0, dstem, 1)
+        outs.append(hip.conv_dgrad_stem(dstem, p["stem"][0][:, :49 * Cin].contiguous(), 7, 2, 3, H, W, Cin))
+    return torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
+
+
+class _ResNetEvalFunction(torch.autograd.Function):
+    """One autograd node for a FROZEN model in eval mode: the only differentiable input is x_nhwc.  The forward is the inference forward
+    (eval-mode BatchNorm folded into the convolutions, `chunk_images` images at a time) in fp32 WHATEVER the model's compute_dtype is --
+    the gradient path has no 16-bit operands -- with every ReLU output kept; the logits equal the fp32 torch.no_grad() forward bit for
+    bit.  ResNetSliceTrans: the logits come from the inference slice fusion (mst_slice_fusion); the op-by-op fusion of the training step
+    runs beside it on the same features to keep what its backward needs.  The backward is the d x chain alone: no parameter gradient."""
+
+    @staticmethod
+    def forward(ctx, model, x_nhwc, sum_in, B, D, mask):
+        with torch.no_grad():
+            feat, sv = _eval_backbone_fwd(model, x_nhwc, sum_in)
+            if B is None:
+                fc = model.model.fc
+                out = feat if isinstance(fc, nn.Identity) else hip.gemm(feat, sv["prep"]["fc"][0], sv["prep"]["fc"][1], epilogue=hip.EPI_BIAS)
+            else:
+                from .models.resnet import SLICE_HEADS
+                out = model.fuse(feat, B, D, mask, False)
+                sv["fused"], sv["fusion"] = fusion_fwd(model, feat, B, D, model.emb_ch, SLICE_HEADS, mask)
+            sv["feat"] = feat
+        ctx.model, ctx.saved, ctx.BD = model, sv, (B, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        model, sv = ctx.model, ctx.saved
+        B, D = ctx.BD
+        with torch.no_grad():
+            G = _Grads(needed=set())                         # nothing but d x
+            dout = dout.contiguous().float()
+            if B is None:
+                fc = model.model.fc
+                dfeat = dout if isinstance(fc, nn.Identity) else G.lin_bwd(dout, sv["feat"], fc)
+            else:
+                from .models.resnet import SLICE_HEADS
+                dfused = G.lin_bwd(dout, sv["fused"], model.linear)
+                dfeat = fusion_bwd(G, model, sv["fusion"], dfused, B, D, model.emb_ch, SLICE_HEADS)
+            dx = _eval_backbone_bwd(sv, dfeat)
+        ctx.saved = None
+        return (None, dx, None, None, None, None)
+
+
+def forward_eval_with_grad(model, x_nhwc, sum_in: bool, B=None, D=None, mask=None):
+    fp32_device_params(model)
+    return _ResNetEvalFunction.apply(model, x_nhwc, sum_in, B, D, mask)

@@ -3,7 +3,8 @@
 HIP kernels + AdamW) of both model families, and the ViT-B forward on the unfused path.  One JSON line per case.
 --deterministic: torch.use_deterministic_algorithms(True) for every case (the fixed-order reductions; DESIGN.md "Determinism");
 --no-fill on top: torch.utils.deterministic.fill_uninitialized_memory = False, to tell torch's NaN fill from the kernels' cost.
---input-grad: the source-gradient timings (input_grad_cases).
+--input-grad: the source-gradient timings (input_grad_cases, then resnet_input_grad_cases: --c3 adds the 1 x 128 x 512^2 shape, --out FILE
+keeps the ResNet lines, --resnet-only skips the DinoV2ClassifierSlice cases).
 --train-storage 16bit (beside --train-attention flash and a 16-bit precision): the encoder blocks' saved activations in 16 bits.  A comma
 list (fp32,16bit,fp32) times those modes one after the other in this process: the repeated mode gives the spread the other is read against.
 The same list drives the ResNet cases (train_storage of ResNetSliceTrans: --c3 for the configs[3] shape, --only-resnet for 2 x 32 x 224^2; add
@@ -179,6 +180,132 @@ def input_grad_cases():
                 "dtype": "fp32"}}), flush=True)
 
 
+def resnet_input_grad_cases(c3, out_path):
+    """--input-grad --resnet [--c3] [--out FILE]: gradients with respect to the source volume of ResNetSliceTrans(34), all in this process.
+    Per shape and training mode (fp32, fp16, fp16 with 16-bit storage) the step with and without the source gradient, the two arms
+    ALTERNATING (a-b-a-b, median of each) so that clock drift and allocator state hit both alike; a frozen eval-mode forward + backward
+    (mst/train_resnet.py::_ResNetEvalFunction); then the stem's data gradient alone (mst_conv_dgrad_stem, HIP events) at 128 x 512^2, Cin 1,
+    fp32: a `roofline` line against the algorithmic work (52.6 GFLOP, 2.1 GB of dz read, 134 MB written; fp32 MFMA peak 157 TF, HBM 8 TB/s)
+    and the explicit forms it replaces -- mst_gemm_ex into a [rows, 64] matrix + mst_col2im_nhwc (atomics), and + the gather under the
+    determinism flag.  `gate`: the new kernel is not slower than the gather form."""
+    from mst import hip
+    lines = []
+
+    def emit(d):
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+
+    def ev(fn, n=10):
+        for _ in range(2):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def median(v):
+        return sorted(v)[len(v) // 2]
+    shapes = [(2, 1, 32, 224, 224)] + ([(1, 1, 128, 512, 512)] if c3 else [])
+    for shape in shapes:
+        src = synth.synth_volume(shape, 3).cuda()
+        tgt = torch.arange(shape[0]).cuda() % 2
+        rounds = 3 if shape[2] >= 128 else 5
+        for prec, st in (("fp32", "fp32"), ("fp16", "fp32"), ("fp16", "16bit")):
+            m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34, train_precision=prec, train_storage=st)
+            m.load_state_dict(synth.synth_resnet_state_dict(0, 34, 2), strict=True)
+            m = m.cuda().train()
+
+            def step(with_src):
+                m.zero_grad(set_to_none=True)
+                x = src.clone().requires_grad_(with_src)
+                torch.nn.functional.cross_entropy(m(x), tgt).backward()
+            step(False), step(True)                      # warm-up of both arms
+            t = {False: [], True: []}
+            for _ in range(rounds):
+                for arm in (False, True):
+                    t[arm].append(once(lambda: step(arm)))
+            emit({"case": f"ResNetSliceTrans(resnet34) step, {prec} convolutions, {st} storage", "shape": list(shape), "arms": "alternating",
+                  "rounds": rounds, "step_params_ms": round(median(t[False]), 2), "step_params_and_source_ms": round(median(t[True]), 2),
+                  "all_params_ms": [round(v, 2) for v in t[False]], "all_params_and_source_ms": [round(v, 2) for v in t[True]]})
+            del m
+            torch.cuda.empty_cache()
+        m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34)
+        m.load_state_dict(synth.synth_resnet_state_dict(0, 34, 2), strict=True)
+        m = m.cuda().eval().requires_grad_(False)
+
+        def saliency():
+            x = src.clone().requires_grad_(True)
+            torch.autograd.grad(m(x)[:, 1].sum(), x)
+
+        def fwd():
+            with torch.no_grad():
+                m(src)
+        saliency(), fwd()
+        ts, tf = [], []
+        for _ in range(rounds):
+            ts.append(once(saliency))
+            tf.append(once(fwd))
+        emit({"case": "ResNetSliceTrans(resnet34) frozen eval, fp32", "shape": list(shape), "arms": "alternating", "rounds": rounds,
+              "frozen_source_only_fwd_bwd_ms": round(median(ts), 2), "no_grad_forward_ms": round(median(tf), 2)})
+        del m
+        torch.cuda.empty_cache()
+    # the stem kernel alone, 128 x 512^2, one input channel, fp32
+    n, H, W, Cout, K, kpad = 128, 512, 512, 64, 49, 64
+    Ho = Wo = 256
+    rows = n * Ho * Wo
+    g = torch.Generator(device="cuda").manual_seed(0)
+    dz = torch.randn(n, Ho, Wo, Cout, device="cuda", generator=g)
+    wg = torch.zeros(Cout, kpad, device="cuda")
+    wg[:, :K] = torch.randn(Cout, K, device="cuda", generator=g) * 0.1
+    wk = wg[:, :K].contiguous()
+    out = torch.empty(n, H, W, 1, device="cuda")
+    col = torch.empty(rows, kpad, device="cuda")
+    dx = torch.empty(n, H, W, 1, device="cuda")
+
+    def explicit():
+        hip.gemm_ex(dz.view(rows, Cout), wg, col, rows, kpad, Cout, sa=(Cout, 1), sb=(kpad, 1), sc=(kpad, 1))
+        dx.zero_()
+        hip.col2im_nhwc(col, dx, 7, 7, 2, 3)
+    new_ms, atomic_ms = [], []
+    for _ in range(3):                                   # arms alternating
+        new_ms.append(ev(lambda: hip.conv_dgrad_stem(dz, wk, 7, 2, 3, H, W, 1, out=out)))
+        atomic_ms.append(ev(explicit, 5))
+    torch.use_deterministic_algorithms(True)
+    gather_ms = []
+    try:
+        for _ in range(3):
+            gather_ms.append(ev(explicit, 5))
+    finally:
+        torch.use_deterministic_algorithms("--deterministic" in sys.argv)
+    ms = median(new_ms)
+    fl = 2.0 * rows * Cout * K
+    nbytes = 4.0 * (rows * Cout + n * H * W + Cout * K)
+    tf, tbs = fl / ms / 1e9, nbytes / ms / 1e9
+    emit({"case": f"mst_conv_dgrad_stem {n} x {H}x{W}, Cin=1, Cout={Cout}", "roofline": {
+        "kernel": "stem_dgrad_kernel", "bound": "mfma" if fl / 157e12 > nbytes / 8e12 else "hbm", "achieved": round(tf, 1), "peak": 157.0,
+        "unit": "TFLOP/s", "frac": round(tf / 157.0, 3), "achieved_GBps": round(tbs * 1e3, 1), "hbm_peak_TBps": 8.0, "frac_hbm": round(tbs / 8.0, 3),
+        "flops_per_launch": fl, "bytes_per_launch": nbytes, "avg_launch_ms": round(ms, 4), "dtype": "fp32"}})
+    emit({"case": "stem data gradient: mst_conv_dgrad_stem against mst_gemm_ex + mst_col2im_nhwc", "shape": [n, H, W, 1], "arms": "alternating",
+          "conv_dgrad_stem_ms": [round(v, 3) for v in new_ms], "gemm_ex_col2im_atomic_ms": [round(v, 3) for v in atomic_ms],
+          "gemm_ex_col2im_gather_ms": [round(v, 3) for v in gather_ms], "gate_not_slower_than_gather": bool(ms <= median(gather_ms)),
+          "faster_than_atomic": bool(ms <= median(atomic_ms))})
+    if out_path:
+        Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+        Path(out_path).write_text("\n".join(lines) + "\n")
+    if ms > median(gather_ms):
+        sys.exit("gate: mst_conv_dgrad_stem is slower than the explicit gather form")
+
+
 def train_case(name, model, shape, n=5):
     model = model.cuda().train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-5)
@@ -211,7 +338,10 @@ def main():
         if "--no-fill" in sys.argv:                      # attribution only: without torch's NaN fill of every torch.empty under the flag
             torch.utils.deterministic.fill_uninitialized_memory = False
     if "--input-grad" in sys.argv:
-        input_grad_cases()
+        if "--resnet-only" not in sys.argv:
+            input_grad_cases()
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+        resnet_input_grad_cases("--c3" in sys.argv, out)
         return
     if "--rooflines" in sys.argv:
         backward_rooflines()
