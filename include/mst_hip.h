@@ -40,8 +40,11 @@ enum mst_epilogue {
     MST_EPI_BIAS_GELU = 1, /* C = gelu_erf(A W^T + b)                     mlp.py:34-36            */
     MST_EPI_BIAS_RELU = 2, /* C = relu(A W^T + b)                         transformer_blocks.py:586 */
     MST_EPI_RESIDUAL = 3,  /* C(f32) += gamma * (A W^T + b)               block.py:90-94,112-113  */
-    MST_EPI_RESIDUAL_RELU = 4 /* C(f32) = relu(C + gamma * (A W^T + b))    resnet BasicBlock / Bottleneck exit; fp32 operands only */
+    MST_EPI_RESIDUAL_RELU = 4, /* C(f32) = relu(C + gamma * (A W^T + b))   resnet BasicBlock / Bottleneck exit; fp32 operands only */
+    MST_EPI_BIAS_SWIGLU = 5   /* C[M, N/2] = silu(A Wg^T + bg) o (A Wv^T + bv)   swiglu_ffn.py:54-72; W is the row-paired image, see mst_gemm */
 };
+
+enum mst_ffn_kind { MST_FFN_MLP = 0, MST_FFN_SWIGLU = 1 };   /* mst_vit_weights.ffn_kind */
 
 enum mst_fusion_type { MST_FUSION_TRANSFORMER = 0, MST_FUSION_LINEAR = 1, MST_FUSION_AVERAGE = 2 };
 
@@ -69,7 +72,18 @@ int mst_layernorm(const float* x, int64_t x_stride, const float* gamma, const fl
  * c_dtype: f32 or (16-bit A only) the A dtype; MST_EPI_RESIDUAL needs c_dtype f32 (C is read and
  * written, gamma = LayerScale vector or NULL: layer_scale.py:26-27).
  * Columns n < scale_cols are multiplied by col_scale after the bias (q * head_dim^-0.5 of
- * attention.py:60 folded into the QKV projection); pass scale_cols = 0 for none. */
+ * attention.py:60 folded into the QKV projection); pass scale_cols = 0 for none.
+ *
+ * MST_EPI_BIAS_SWIGLU (SwiGLUFFNFused, extern/dinov2/layers/swiglu_ffn.py:54-72: x1, x2 = w12(x).chunk(2); hidden = silu(x1) * x2):
+ * gate and value of an output element are combined in the accumulators, so the [M, 2H] pre-activation never reaches memory.  W [N, K]
+ * and bias [N] are the ROW-PAIRED image of w12 [2H, K] / its bias with pairing group G (what hip.pack_swiglu builds; H is first padded
+ * with zero rows to Hp, a multiple of 64, and N = 2 Hp):
+ *     image rows 2G g     .. 2G g + G - 1   = w12 rows       G g .. G g + G - 1    (gate)
+ *     image rows 2G g + G .. 2G g + 2G - 1  = w12 rows  Hp + G g .. Hp + G g + G - 1  (value)          for g < Hp / G
+ * G is part of this contract and depends on the operand type: G = 16 for 16-bit operands (N % 128 == 0, K % 64 == 0), G = 32 for f32
+ * operands (N % 128 == 0, K % 16 == 0).  C is [M, N / 2] with row stride ldc >= N / 2 (ldc % 4 == 0); A, W, C and bias 16-byte aligned;
+ * gamma NULL and scale_cols 0.  An N that is not a multiple of 128 (whole tiles of paired groups) returns MST_EINVAL.  The sigmoid runs in fp32:
+ * x / (1 + expf(-x)) for f32 C, one v_exp + one v_rcp for 16-bit C; a large negative gate gives -0, never NaN. */
 int mst_gemm(const void* A, int ab_dtype, int64_t lda, const void* W, int64_t ldw, const float* bias,
              void* C, int c_dtype, int64_t ldc, int64_t M, int N, int K, int epilogue,
              const float* gamma, float col_scale, int scale_cols, mst_stream_t stream);
@@ -347,6 +361,12 @@ int mst_layernorm_bwd(const float* x, int64_t x_stride, const float* gamma, cons
                       float eps, mst_stream_t stream);
 int mst_act_fwd(const float* h, float* y, int64_t n, int kind, mst_stream_t stream);
 int mst_act_bwd(const float* h, float* dy, int64_t n, int kind, mst_stream_t stream);
+/* SwiGLU of the training step (swiglu_ffn.py:54-72) in the reference layout x12 = [x1 | x2] (chunk(2, dim=-1)): x12 fp32 [rows, 2 hidden],
+ * mst_swiglu_fwd: h[r][c] = silu(x12[r][c]) * x12[r][hidden + c], h fp32 [rows, hidden];
+ * mst_swiglu_bwd: with s = sigmoid(x1): dx12[r][c] = dh x2 s (1 + x1 (1 - s)), dx12[r][hidden + c] = dh x1 s, dx12 fp32 [rows, 2 hidden]
+ * (every element written; must not alias x12).  No reduction: one entry point for both determinism modes.  Any positive rows, hidden. */
+int mst_swiglu_fwd(const float* x12, float* h, int64_t rows, int hidden, mst_stream_t stream);
+int mst_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows, int hidden, mst_stream_t stream);
 int mst_colsum(const float* a, int64_t a_stride, const float* b, int64_t b_stride, int64_t rows, int cols, float* out,
                mst_stream_t stream);
 int mst_axpby_cols(const float* x, int64_t x_stride, const float* g, float alpha, float beta, float* y, int64_t y_stride,
@@ -380,11 +400,16 @@ int mst_patch_embed_dgrad(const float* dx, int tokens_per_image, int first_patch
  *   (mst_colsum_ordered_workspace_bytes(rows, cols) bytes): its result has the bits of mst_colsum_ordered on the upcast b.
  * mst_transpose16: out[c][r] = x[r][c] for r < rows, 0 for rows <= r < rows_pad (x [rows, cols] T with row stride ldx, out [cols, rows_pad] T
  *   with row stride ldo >= rows_pad): the 16-bit-input counterpart of mst_cvt16(transpose = 1), the operand image of d weight = dY^T . X
- *   above 12,288 tokens (mst_gemm16_splitk). */
+ *   above 12,288 tokens (mst_gemm16_splitk).
+ * mst_swiglu_fwd16 / mst_swiglu_bwd16: mst_swiglu_fwd / mst_swiglu_bwd with x12 (and h) in T: h = T(fp32 formula on float(x12)), one rounding;
+ *   dh and dx12 stay fp32.  The results are those of the fp32 entry points on the upcast x12 bit for bit (h: rounded to T).  Any positive
+ *   rows and hidden (16-byte accesses when hidden % 8 == 0, one element per thread otherwise); bases 16-byte aligned. */
 int mst_residual_layernorm16(const float* x_in, const void* br, int dtype, const float* gamma, float* x_out, const float* ln_w,
                              const float* ln_b, void* y, int64_t rows, int cols, float eps, mst_stream_t stream);
 int mst_act_fwd16(const void* h, void* y, int dtype, int64_t n, int kind, mst_stream_t stream);
 int mst_act_bwd16(const void* h, int dtype, float* dy, int64_t n, int kind, mst_stream_t stream);
+int mst_swiglu_fwd16(const void* x12, void* h, int dtype, int64_t rows, int hidden, mst_stream_t stream);
+int mst_swiglu_bwd16(const void* x12, int dtype, const float* dh, float* dx12, int64_t rows, int hidden, mst_stream_t stream);
 int mst_colsum_b16(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
                    mst_stream_t stream);
 int mst_colsum_b16_ordered(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
@@ -535,6 +560,12 @@ typedef struct mst_vit_weights {
                                    * full maps when asked for), then attention, out-projection and MLP of the CLS rows alone.  The
                                    * reference discards the last block's patch-token outputs (vision_transformer.py:324-329 returns
                                    * x_norm_clstoken only), so the results are the same; ignored in fp8 mode. */
+    /* appended (additions only: the ABI version stays 300; a zero-initialised tail behaves as before) */
+    int ffn_kind;                 /* MST_FFN_MLP (0): fc1 [4E, E] + GELU + fc2 [E, 4E].  MST_FFN_SWIGLU (1): SwiGLUFFNFused
+                                   * (swiglu_ffn.py:54-72) -- every layer's fc1_w / fc1_b carry the row-paired w12 image [2 ffn_hidden, E] /
+                                   * [2 ffn_hidden] of MST_EPI_BIAS_SWIGLU for compute_dtype's pairing group, fc2_w / fc2_b carry
+                                   * w3 zero-padded to [E, ffn_hidden] / [E]; the fused-LayerNorm packs are not read; not with fp8_linear */
+    int ffn_hidden;               /* ffn_kind 1: Hp, the hidden width padded to a multiple of 64 (<= 4E) */
 } mst_vit_weights;
 
 /* DinoVisionTransformer.forward on n_slices gray slices (vision_transformer.py:254-270,324-329;

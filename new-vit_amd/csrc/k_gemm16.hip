@@ -124,6 +124,35 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const T* __restrict__ A, in
     // Interior tiles run branch-free (per-lane `m < M` branches make hipcc drain vmcnt(0) before every store).
     auto epilogue = [&](auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
+        if constexpr (EPI == MST_EPI_BIAS_SWIGLU) {
+            // W is the row-paired w12 image (include/mst_hip.h): image rows n0 + wn TN/2 + 32 p + [0, 16) are gates, + [16, 32) their values, so
+            // acc[2p][j] and acc[2p + 1][j] of this lane are gate and value of output columns (n0 + wn TN/2) / 2 + 16 p + 4 (lane >> 4) + [0, 4)
+#pragma unroll
+            for (int p = 0; p < NI / 2; ++p) {
+                const int n = (n0 + wn * (TN / 2)) / 2 + p * 16 + (lane >> 4) * 4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int m = m0 + wm * 64 + j * 16 + (lane & 15);
+                    if (!FULL && m >= M) continue;
+                    float v[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = swiglu_gate<sizeof(OutT) == 2>(acc[2 * p][j][r], acc[2 * p + 1][j][r]);
+                    OutT* cp = C + (int64_t)m * ldc + n;
+                    if constexpr (sizeof(OutT) == 4) {
+                        *reinterpret_cast<float4*>(cp) = make_float4(v[0], v[1], v[2], v[3]);
+                    } else {
+                        typedef __attribute__((ext_vector_type(4))) OutT o4;
+                        o4 pk;
+                        pk[0] = (OutT)v[0];
+                        pk[1] = (OutT)v[1];
+                        pk[2] = (OutT)v[2];
+                        pk[3] = (OutT)v[3];
+                        *reinterpret_cast<o4*>(cp) = pk;
+                    }
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int n = n0 + wn * (TN / 2) + i * 16 + (lane >> 4) * 4;
@@ -218,6 +247,16 @@ int launch_split(const gemm_args& g, int splits, int64_t split_stride) {
     return mst_check_launch("gemm16_splitk");
 }
 
+// MST_EPI_BIAS_SWIGLU: W / bias are the row-paired image with g.N rows, C is [M, N / 2].  Always the tiled kernel, in gemm16_route's two
+// widths (the wreg, mid and big kernels have no such epilogue); the runtime dispatcher of mst_common.h does not know the value, so no
+// other launcher is asked for it.
+template <typename T>
+int launch_swiglu(const gemm_args& g) {
+    const tile_launcher tl{(int64_t)((g.M + BM - 1) / BM) * (g.N / BN) < 224};
+    if (g.cdt == MST_F32) return tl.template launch<T, MST_EPI_BIAS_SWIGLU, float>(g);
+    return tl.template launch<T, MST_EPI_BIAS_SWIGLU, T>(g);
+}
+
 // Which kernel a 16-bit GEMM runs.  Every threshold is here, beside the measurement behind it (MI355X, tools/bench_gemm.py unless named).
 enum gemm16_kernel_id { GEMM16_WREG, GEMM16_MID, GEMM16_BIG, GEMM16_TILE128, GEMM16_TILE64 };
 
@@ -238,7 +277,8 @@ gemm16_kernel_id gemm16_route(const gemm_args& g) {
         return GEMM16_MID;
     // persistent 256 x 384 (k_gemm16_big.hip) once its tiles fill the chip: 153 FLOP per staged byte against 64.  Never the residual
     // epilogue: its read-modify-write is HBM-bound and overlaps better with two small workgroups per CU; the big kernel's form was removed.
-    if (g.epi != MST_EPI_RESIDUAL && divides(GEMM16_BIG_TILE, g) && tiles_of(GEMM16_BIG_TILE, g) >= 192) return GEMM16_BIG;
+    // (bias, GELU, ReLU only: the SwiGLU epilogue never reaches this router, launch_gemm16 sends it to the tiled kernel.)
+    if (g.epi <= MST_EPI_BIAS_RELU && divides(GEMM16_BIG_TILE, g) && tiles_of(GEMM16_BIG_TILE, g) >= 192) return GEMM16_BIG;
     // 128 x 128; below 224 workgroups that grid would leave CUs idle (a few thousand token rows against N = 384: 99 workgroups on 256
     // CUs), so 128 x 64 tiles, twice the workgroups
     return (int64_t)((g.M + BM - 1) / BM) * (g.N / BN) < 224 ? GEMM16_TILE64 : GEMM16_TILE128;
@@ -276,12 +316,20 @@ int launch_gemm16_splitk(const gemm_args& g, int splits, int64_t split_stride) {
 
 int launch_gemm16(const gemm_args& g) {
     MST_CHECK_ARG(g.K > 0 && g.K % BK == 0, "gemm16: K=%d must be a multiple of %d", g.K, BK);
-    MST_CHECK_ARG(g.N > 0 && g.N % BN == 0, "gemm16: N=%d must be a multiple of %d", g.N, BN);
+    MST_CHECK_ARG(g.N > 0 && g.N % BN == 0, g.epi == MST_EPI_BIAS_SWIGLU ? "gemm16: N=%d rows of the paired image must be a multiple of %d (16-bit pairing group 16)"
+                                                                          : "gemm16: N=%d must be a multiple of %d", g.N, BN);
     MST_CHECK_ARG(g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 4 == 0, "gemm16: lda/ldw must be multiples of 8, ldc of 4");
     MST_CHECK_ARG(g.M < (1ll << 31) - BM, "gemm16: M too large");
     MST_CHECK_ARG(g.cdt == MST_F32 || g.cdt == g.dt, "gemm16: C dtype must be f32 or the operand dtype");
     MST_CHECK_ARG(g.epi != MST_EPI_RESIDUAL || g.cdt == MST_F32, "gemm16: residual epilogue needs f32 C");
     MST_CHECK_ARG(g.epi != MST_EPI_RESIDUAL_RELU, "gemm16: the residual + ReLU epilogue exists for f32 operands only");
+    if (g.epi == MST_EPI_BIAS_SWIGLU) {   // (N % 128 above: whole pairs of 16-row pairing groups for both tile widths)
+        MST_CHECK_ARG(g.scale_cols == 0 && !g.gamma, "gemm16: no column scaling and no LayerScale on the SwiGLU epilogue");
+        MST_CHECK_ARG(g.ldc >= g.N / 2, "gemm16: ldc=%lld is less than the %d output columns of the SwiGLU epilogue", (long long)g.ldc, g.N / 2);
+        MST_CHECK_ARG(g.dt == MST_BF16 || g.dt == MST_F16, "gemm16: bad operand dtype %d", g.dt);
+        if (g.M <= 0) return MST_OK;
+        return g.dt == MST_BF16 ? launch_swiglu<bf16_t>(g) : launch_swiglu<f16_t>(g);
+    }
     if (g.M <= 0) return MST_OK;
     switch (gemm16_route(g)) {
         case GEMM16_WREG: return launch_gemm16_wreg(g);

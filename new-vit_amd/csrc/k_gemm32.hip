@@ -121,6 +121,31 @@ __global__ __launch_bounds__(256) void gemm32_kernel(const float* __restrict__ A
     // epilogue: D[row = n_local = (r&3)+8*(r>>2)+4*(lane>>5)][col = m_local = lane&31]
     const bool vec_ok = (ldc % 4 == 0);
     constexpr bool RES = (EPI == MST_EPI_RESIDUAL || EPI == MST_EPI_RESIDUAL_RELU);
+    if constexpr (EPI == MST_EPI_BIAS_SWIGLU) {
+        // W is the row-paired w12 image with pairing group 32 (include/mst_hip.h): acc[0][j] holds the gates (image rows n0 + wn 64 + [0, 32)),
+        // acc[1][j] their values; output columns (n0 + wn 64) / 2 + [0, 32), of which the lane owns 8 g + 4 (lane >> 5) + [0, 4).  N % 128 == 0.
+        const int nb = n0 + wn * 64;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int m = m0 + wm * 64 + j * 32 + (lane & 31);
+            if (m >= M) continue;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c = 8 * g + 4 * (lane >> 5);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float gt = acc[0][j][g * 4 + e], vl = acc[1][j][g * 4 + e];
+                    if (bias) { gt += bias[nb + c + e]; vl += bias[nb + 32 + c + e]; }
+                    v[e] = swiglu_gate<false>(gt, vl);
+                }
+                float* cp = C + (int64_t)m * ldc + nb / 2 + c;
+                if (vec_ok) *reinterpret_cast<float4*>(cp) = make_float4(v[0], v[1], v[2], v[3]);
+                else { cp[0] = v[0]; cp[1] = v[1]; cp[2] = v[2]; cp[3] = v[3]; }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -230,6 +255,13 @@ int launch_gemm32(const gemm_args& g) {
     MST_CHECK_ARG(g.N > 0, "gemm32: N=%d", g.N);
     MST_CHECK_ARG(g.lda % 4 == 0 && g.ldw % 4 == 0, "gemm32: lda/ldw must be multiples of 4");
     MST_CHECK_ARG(g.M < (1ll << 31) - BM, "gemm32: M too large");
+    if (g.epi == MST_EPI_BIAS_SWIGLU) {   // W / bias are the row-paired image with g.N rows, C is [M, N / 2]: the tiled kernel only
+        MST_CHECK_ARG(g.N % 128 == 0, "gemm32: N=%d rows of the paired image must be a multiple of 128 (fp32 pairing group 32, whole tiles)", g.N);
+        MST_CHECK_ARG(g.scale_cols == 0 && !g.gamma, "gemm32: no column scaling and no LayerScale on the SwiGLU epilogue");
+        MST_CHECK_ARG(g.ldc >= g.N / 2, "gemm32: ldc=%lld is less than the %d output columns of the SwiGLU epilogue", (long long)g.ldc, g.N / 2);
+        if (g.M <= 0) return MST_OK;
+        return tile_launcher{}.launch<float, MST_EPI_BIAS_SWIGLU, float>(g);
+    }
     if (g.M <= 0) return MST_OK;
     if (gemm32_small_applicable(g.M, g.N, g.K)) return launch_gemm32_small(g);   // across-slice stage: a few hundred rows (k_gemm32s.hip)
     return gemm_dispatch("gemm32", g, tile_launcher{});

@@ -181,6 +181,30 @@ __global__ void act_fwd_kernel(const float* __restrict__ h, float* __restrict__ 
     }
 }
 
+// SwiGLU (layers/swiglu_ffn.py:54-72) on rows x12 = [x1 | x2] of 2 H columns: h[r][c] = silu(x1[r][c]) x2[r][c], and with s = sigmoid(x1)
+// dx12[r] = [dh x2 s (1 + x1 (1 - s)) | dh x1 s].  One thread per element of h; no reduction, one form for both determinism modes.
+__global__ void swiglu_fwd_kernel(const float* __restrict__ x12, float* __restrict__ h, int64_t rows, int H) {
+    const int64_t n = rows * H;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / H;
+        const int c = (int)(i - r * H);
+        const float* x = x12 + r * 2 * H + c;
+        h[i] = swiglu_fwd_value(x[0], x[H]);
+    }
+}
+__global__ void swiglu_bwd_kernel(const float* __restrict__ x12, const float* __restrict__ dh, float* __restrict__ dx12, int64_t rows, int H) {
+    const int64_t n = rows * H;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / H;
+        const int c = (int)(i - r * H);
+        const int64_t o = r * 2 * H + c;
+        float d1, d2;
+        swiglu_bwd_values(x12[o], x12[o + H], dh[i], &d1, &d2);
+        dx12[o] = d1;
+        dx12[o + H] = d2;
+    }
+}
+
 // out[j] += sum_i a[i][j] * (b ? b[i][j] : 1).  A 256-thread block owns 64 columns x a chunk of rows: 16 threads x float4 across the
 // columns (VEC) or 64 threads x 1, the other 16 (4) thread rows stride down the chunk; the partial sums meet in LDS and ONE atomic per
 // column per block goes out (the round-2 kernel ran one thread per column down 256 rows: 34 workgroups for a [4112, 384] bias gradient).
@@ -350,6 +374,16 @@ int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const f
 int launch_act_bwd(const float* h, float* dy, int64_t n, int kind, hipStream_t s) {
     act_bwd_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(h, dy, n, kind);
     return mst_check_launch("act_bwd");
+}
+
+int launch_swiglu_fwd(const float* x12, float* h, int64_t rows, int H, hipStream_t s) {
+    swiglu_fwd_kernel<<<dim3(grid_for(rows * H)), dim3(256), 0, s>>>(x12, h, rows, H);
+    return mst_check_launch("swiglu_fwd");
+}
+
+int launch_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s) {
+    swiglu_bwd_kernel<<<dim3(grid_for(rows * H)), dim3(256), 0, s>>>(x12, dh, dx12, rows, H);
+    return mst_check_launch("swiglu_bwd");
 }
 
 int launch_act_fwd(const float* h, float* y, int64_t n, int kind, hipStream_t s) {

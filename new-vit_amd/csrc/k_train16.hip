@@ -136,6 +136,56 @@ __global__ __launch_bounds__(256) void act_bwd16_kernel(const T* __restrict__ h,
     if (gid < (n & 7)) dy[8 * n8 + gid] *= act_deriv((float)h[8 * n8 + gid], kind);
 }
 
+// SwiGLU on rows x12 = [x1 | x2] of 2 H elements of T (swiglu_fwd_kernel / swiglu_bwd_kernel of k_train.hip, the same fp32 expressions):
+// V = 8 columns per thread in 16-byte accesses when H % 8 == 0 (every half row is then 16-byte aligned), one column per thread otherwise.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void swiglu_fwd16_kernel(const T* __restrict__ x12, T* __restrict__ h, int64_t rows, int H) {
+    const int hv = H / V;
+    const int64_t n = rows * hv;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / hv;
+        const int c = (int)(i - r * hv) * V;
+        const T* x = x12 + r * 2 * H + c;
+        if constexpr (V == 8) {
+            float a[8], b[8];
+            load8(x, a);
+            load8(x + H, b);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) a[e] = f32_rounded(swiglu_fwd_value(a[e], b[e]));          // the bits of T(mst_swiglu_fwd)
+            store8(h + r * H + c, a);
+        } else {
+            h[r * H + c] = (T)f32_rounded(swiglu_fwd_value((float)x[0], (float)x[H]));
+        }
+    }
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void swiglu_bwd16_kernel(const T* __restrict__ x12, const float* __restrict__ dh, float* __restrict__ dx12,
+                                                           int64_t rows, int H) {
+    const int hv = H / V;
+    const int64_t n = rows * hv;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / hv;
+        const int c = (int)(i - r * hv) * V;
+        const int64_t o = r * 2 * H + c;
+        if constexpr (V == 8) {
+            float a[8], b[8], d[8], d1[8], d2[8];
+            load8(x12 + o, a);
+            load8(x12 + o + H, b);
+            load8(dh + r * H + c, d);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) swiglu_bwd_values(a[e], b[e], d[e], &d1[e], &d2[e]);
+            store8(dx12 + o, d1);
+            store8(dx12 + o + H, d2);
+        } else {
+            float d1, d2;
+            swiglu_bwd_values((float)x12[o], (float)x12[o + H], dh[r * H + c], &d1, &d2);
+            dx12[o] = d1;
+            dx12[o + H] = d2;
+        }
+    }
+}
+
 // colsum_kernel<VEC = true> of k_train.hip with a 16-bit factor: 16 threads x 4 columns across, 16 thread rows down the chunk, one atomic
 // per column per workgroup.
 template <typename T>
@@ -272,6 +322,38 @@ int launch_act_bwd16(const void* h, int dt, float* dy, int64_t n, int kind, hipS
     else if (dt == MST_F16) act_bwd16_kernel<f16_t><<<dim3(grid8(n)), dim3(256), 0, s>>>((const f16_t*)h, dy, n, kind);
     else { mst_set_error("act_bwd16: dtype %d (bf16 / f16)", dt); return MST_EINVAL; }
     return mst_check_launch("act_bwd16");
+}
+
+template <typename T>
+static int swiglu16_t(const void* x12, void* h, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s) {
+    const bool vec = H % 8 == 0;
+    const int64_t n = rows * (vec ? H / 8 : H);
+    const int64_t g = (n + 255) / 256;
+    const dim3 grid((unsigned)(g > 16384 ? 16384 : g)), block(256);
+    if (h) {
+        if (vec) swiglu_fwd16_kernel<T, 8><<<grid, block, 0, s>>>((const T*)x12, (T*)h, rows, H);
+        else swiglu_fwd16_kernel<T, 1><<<grid, block, 0, s>>>((const T*)x12, (T*)h, rows, H);
+        return mst_check_launch("swiglu_fwd16");
+    }
+    if (vec) swiglu_bwd16_kernel<T, 8><<<grid, block, 0, s>>>((const T*)x12, dh, dx12, rows, H);
+    else swiglu_bwd16_kernel<T, 1><<<grid, block, 0, s>>>((const T*)x12, dh, dx12, rows, H);
+    return mst_check_launch("swiglu_bwd16");
+}
+
+int launch_swiglu_fwd16(const void* x12, void* h, int dt, int64_t rows, int H, hipStream_t s) {
+    MST_CHECK_ARG(aligned(x12, 16) && aligned(h, 16), "swiglu_fwd16: bases must be 16-byte aligned");
+    if (dt == MST_BF16) return swiglu16_t<bf16_t>(x12, h, nullptr, nullptr, rows, H, s);
+    if (dt == MST_F16) return swiglu16_t<f16_t>(x12, h, nullptr, nullptr, rows, H, s);
+    mst_set_error("swiglu_fwd16: dtype %d (bf16 / f16)", dt);
+    return MST_EINVAL;
+}
+
+int launch_swiglu_bwd16(const void* x12, int dt, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s) {
+    MST_CHECK_ARG(aligned(x12, 16) && aligned(dh, 16) && aligned(dx12, 16), "swiglu_bwd16: bases must be 16-byte aligned");
+    if (dt == MST_BF16) return swiglu16_t<bf16_t>(x12, nullptr, dh, dx12, rows, H, s);
+    if (dt == MST_F16) return swiglu16_t<f16_t>(x12, nullptr, dh, dx12, rows, H, s);
+    mst_set_error("swiglu_bwd16: dtype %d (bf16 / f16)", dt);
+    return MST_EINVAL;
 }
 
 static int colsum_b16_args(const char* what, const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols) {

@@ -249,6 +249,14 @@ int mst_act_bwd(const float* h, float* dy, int64_t n, int kind, mst_stream_t str
     MST_CHECK_ARG(h && dy && n > 0 && (kind == 0 || kind == 1), "act_bwd: bad arguments");
     return launch_act_bwd(h, dy, n, kind, (hipStream_t)stream);
 }
+int mst_swiglu_fwd(const float* x12, float* h, int64_t rows, int hidden, mst_stream_t stream) {
+    MST_CHECK_ARG(x12 && h && rows > 0 && hidden > 0, "swiglu_fwd: bad arguments");
+    return launch_swiglu_fwd(x12, h, rows, hidden, (hipStream_t)stream);
+}
+int mst_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows, int hidden, mst_stream_t stream) {
+    MST_CHECK_ARG(x12 && dh && dx12 && rows > 0 && hidden > 0, "swiglu_bwd: bad arguments");
+    return launch_swiglu_bwd(x12, dh, dx12, rows, hidden, (hipStream_t)stream);
+}
 // ---- 16-bit storage mode of the training step (k_train16.hip)
 int mst_residual_layernorm16(const float* x_in, const void* br, int dtype, const float* gamma, float* x_out, const float* ln_w,
                              const float* ln_b, void* y, int64_t rows, int cols, float eps, mst_stream_t stream) {
@@ -262,6 +270,14 @@ int mst_act_fwd16(const void* h, void* y, int dtype, int64_t n, int kind, mst_st
 int mst_act_bwd16(const void* h, int dtype, float* dy, int64_t n, int kind, mst_stream_t stream) {
     MST_CHECK_ARG(h && dy && n > 0 && (kind == 0 || kind == 1), "act_bwd16: bad arguments");
     return launch_act_bwd16(h, dtype, dy, n, kind, (hipStream_t)stream);
+}
+int mst_swiglu_fwd16(const void* x12, void* h, int dtype, int64_t rows, int hidden, mst_stream_t stream) {
+    MST_CHECK_ARG(x12 && h && rows > 0 && hidden > 0, "swiglu_fwd16: bad arguments");
+    return launch_swiglu_fwd16(x12, h, dtype, rows, hidden, (hipStream_t)stream);
+}
+int mst_swiglu_bwd16(const void* x12, int dtype, const float* dh, float* dx12, int64_t rows, int hidden, mst_stream_t stream) {
+    MST_CHECK_ARG(x12 && dh && dx12 && rows > 0 && hidden > 0, "swiglu_bwd16: bad arguments");
+    return launch_swiglu_bwd16(x12, dtype, dh, dx12, rows, hidden, (hipStream_t)stream);
 }
 int mst_colsum_b16(const float* a, int64_t a_stride, const void* b, int b_dtype, int64_t b_stride, int64_t rows, int cols, float* out,
                    mst_stream_t stream) {
@@ -536,7 +552,7 @@ int mst_block_fused_s(float* x, const void* attn_out, void* xn_out, int dtype, c
 // workspace carve (chunk of C slices, Mc = C*N rows):
 //   x   fp32 [Mc, E]      residual stream
 //   xn  T    [Mc, E]      LayerNorm output; reused as the attention output
-//   big T    [Mc, 4E]     qkv [Mc, 3E] during attention, then the MLP hidden [Mc, 4E]
+//   big T    [Mc, 4E]     qkv [Mc, 3E] during attention, then the MLP hidden [Mc, 4E] (SwiGLU: [Mc, ffn_hidden], ffn_hidden <= 4E)
 //   fp8_linear only:  a8 u8 [Mc, 4E] (the quantised input of the current GEMM) | amax f32 [depth][4]
 static void vit_carve(const mst_vit_weights* w, int N, int chunk, size_t* off_xn, size_t* off_big, size_t* total,
                       size_t* off_a8 = nullptr, size_t* off_amax = nullptr, size_t* off_blk = nullptr) {
@@ -582,7 +598,8 @@ enum vit_tail {           // a block's work behind attention
     TAIL_BLOCK_ROLES,     // out-projection folded into that launch, producer/consumer form (k_block16.hip)
     TAIL_BLOCK_SINGLE,    // the same in the single-role form (k_block16s.hip)
     TAIL_FP8_DYNAMIC,     // e4m3 GEMMs, every input quantised with this chunk's max|x|
-    TAIL_FP8_STATIC       // e4m3 GEMMs with calibrated scales: producers write e4m3, nothing is scanned
+    TAIL_FP8_STATIC,      // e4m3 GEMMs with calibrated scales: producers write e4m3, nothing is scanned
+    TAIL_SWIGLU           // ffn_kind 1: out-projection, LayerNorm2, w12 with the SwiGLU epilogue, w3 (swiglu_ffn.py:54-72)
 };
 struct vit_plan {
     vit_tail tail;
@@ -593,6 +610,7 @@ struct vit_plan {
 static vit_plan vit_resolve(const mst_vit_weights* w, int64_t tokens) {
     if (w->fp8_linear) return {w->fp8_amax ? TAIL_FP8_STATIC : TAIL_FP8_DYNAMIC, false, false};
     const bool may_prune = w->prune_last_block && w->num_heads * 64 == w->embed_dim;
+    if (w->ffn_kind == MST_FFN_SWIGLU) return {TAIL_SWIGLU, false, may_prune};
     // fused-LayerNorm pipeline (16-bit, E = 384): norm1 folded into QKV, norm2 + MLP in one kernel.  The fused MLP is a
     // persistent kernel of 128-token tiles: below ~one tile per CU it leaves CUs idle (c1 shape, 4k tokens: 90 us per
     // launch on 33 CUs against ~45 us for LN + fc1 + fc2 as three well-filled launches), so small calls take the unfused path.
@@ -639,6 +657,12 @@ struct vit_call {
         g.col_scale = qscale, g.scale_cols = E;
         return g;
     }
+    // big[rows, Hp] = silu(A . Wg^T + bg) o (A . Wv^T + bv): fc1_w / fc1_b carry the row-paired w12 image of 2 Hp rows (MST_EPI_BIAS_SWIGLU)
+    gemm_args swiglu(int64_t rows, const void* A, const mst_vit_layer* L) const {
+        gemm_args g = linear(rows, A, L->fc1_w, L->fc1_b, big, dt, 2 * w->ffn_hidden, E, MST_EPI_BIAS_SWIGLU);
+        g.ldc = w->ffn_hidden;
+        return g;
+    }
     // the same layer on e4m3 operands (A and W already quantised) under their per-tensor scales
     static gemm_args fp8(gemm_args g, const float* a_amax, float w_scale) {
         g.dt = MST_F8E4M3, g.a_amax = a_amax, g.w_scale = w_scale;
@@ -681,6 +705,11 @@ struct vit_call {
         RUNK(MST_K_ATTENTION, launch_cls_attn(big, dt, c, N, heads, pr, a_cls, log2q, s));
         RUNK(MST_K_GEMM_PROJ, gemm(residual(c, a_cls, L->proj_w, L->proj_b, L->ls1, E, (int64_t)N * E)));
         RUNK(MST_K_LAYERNORM, launch_layernorm(x, (int64_t)N * E, L->ln2_w, L->ln2_b, n_cls, dt, E, c, E, 1e-6f, s));
+        if (w->ffn_kind == MST_FFN_SWIGLU) {
+            RUNK(MST_K_GEMM_FC1, gemm(swiglu(c, n_cls, L)));
+            RUNK(MST_K_GEMM_FC2, gemm(residual(c, big, L->fc2_w, L->fc2_b, L->ls2, w->ffn_hidden, (int64_t)N * E)));
+            return MST_OK;
+        }
         RUNK(MST_K_GEMM_FC1, gemm(linear(c, n_cls, L->fc1_w, L->fc1_b, big, dt, 4 * E, E, MST_EPI_BIAS_GELU)));
         RUNK(MST_K_GEMM_FC2, gemm(residual(c, big, L->fc2_w, L->fc2_b, L->ls2, 4 * E, (int64_t)N * E)));
         return MST_OK;
@@ -725,6 +754,12 @@ struct vit_call {
                 RUNK(MST_K_GEMM_PROJ, gemm(residual(Mc, xn, L->proj_w, L->proj_b, L->ls1, E, E)));
                 RUNK(MST_K_MLP_FUSED, launch_mlp16(x, xn_out, dt, L->mlp_pack, L->fc1_bf, L->fc2_bf, Mc, E, 1e-6f, s));
                 return MST_OK;
+            case TAIL_SWIGLU:
+                RUNK(MST_K_GEMM_PROJ, gemm(residual(Mc, xn, L->proj_w, L->proj_b, L->ls1, E, E)));
+                RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
+                RUNK(MST_K_GEMM_FC1, gemm(swiglu(Mc, xn, L)));
+                RUNK(MST_K_GEMM_FC2, gemm(residual(Mc, big, L->fc2_w, L->fc2_b, L->ls2, w->ffn_hidden, E)));
+                return MST_OK;
             case TAIL_UNFUSED:
                 RUNK(MST_K_GEMM_PROJ, gemm(residual(Mc, xn, L->proj_w, L->proj_b, L->ls1, E, E)));
                 RUNK(MST_K_LAYERNORM, launch_layernorm(x, E, L->ln2_w, L->ln2_b, xn, dt, E, Mc, E, 1e-6f, s));
@@ -751,6 +786,12 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
     MST_CHECK_ARG(dt == MST_F16 || dt == MST_BF16 || dt == MST_F32, "vit_encode: bad compute dtype %d", dt);
     MST_CHECK_ARG(n_slices > 0 && chunk_slices > 0, "vit_encode: n_slices=%d chunk=%d", n_slices, chunk_slices);
     MST_CHECK_ARG(n_layers_probs >= 0 && n_layers_probs <= w->depth, "vit_encode: n_layers_probs=%d", n_layers_probs);
+    MST_CHECK_ARG(w->ffn_kind == MST_FFN_MLP || w->ffn_kind == MST_FFN_SWIGLU, "vit_encode: ffn_kind=%d", w->ffn_kind);
+    if (w->ffn_kind == MST_FFN_SWIGLU) {
+        MST_CHECK_ARG(w->ffn_hidden > 0 && w->ffn_hidden % 64 == 0 && w->ffn_hidden <= 4 * E,
+                      "vit_encode: ffn_hidden=%d must be a multiple of 64, at most 4 * embed_dim (the padded width of hip.pack_swiglu)", w->ffn_hidden);
+        MST_CHECK_ARG(!w->fp8_linear, "vit_encode: fp8_linear has no SwiGLU form");
+    }
     const int R = w->num_registers, Np = w->grid_h * w->grid_w, N = 1 + R + Np;
     if (chunk_slices > n_slices) chunk_slices = n_slices;
     size_t off_xn, off_big, total, off_a8 = 0, off_amax = 0, off_blk = 0;

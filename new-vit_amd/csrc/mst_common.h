@@ -128,6 +128,28 @@ template <> __device__ __forceinline__ float gelu_sig<f16_t>(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+// silu(g) * v of the MST_EPI_BIAS_SWIGLU GEMM epilogue (k_gemm16.hip, k_gemm32.hip).  Exact form for fp32 output; for 16-bit output one
+// v_exp + one v_rcp (relative error ~2 ulp of fp32: far below one fp16 / bf16 ulp), as gelu_fast is for GELU.  A large negative gate:
+// exp -> inf, g / inf = g * 0 = -0, never NaN.
+template <bool FAST>
+__device__ __forceinline__ float swiglu_gate(float g, float v) {
+    if (FAST) return g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-g * 1.4426950408889634f)) * v;
+    return g / (1.0f + expf(-g)) * v;
+}
+
+// SwiGLU of the training step (layers/swiglu_ffn.py:54-72; x12 = [x1 | x2] as chunk(2, dim=-1) gives it): h = silu(x1) x2 and its
+// gradient, in fp32 with every product spelled out (no contraction left to the compiler), so that the fp32 kernels of k_train.hip and
+// the 16-bit-storage kernels of k_train16.hip return the same bits on the same values.  x1 -> -inf side: expf overflows to inf, s = 0,
+// h = (x1 / inf) * x2 = -0 * x2; nothing is NaN for finite inputs.
+__device__ __forceinline__ float swiglu_sigmoid(float x1) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x1))); }
+__device__ __forceinline__ float swiglu_fwd_value(float x1, float x2) { return __fmul_rn(__fdiv_rn(x1, __fadd_rn(1.0f, expf(-x1))), x2); }
+__device__ __forceinline__ void swiglu_bwd_values(float x1, float x2, float dh, float* d1, float* d2) {
+    const float s = swiglu_sigmoid(x1);
+    const float t = __fadd_rn(1.0f, __fmul_rn(x1, __fsub_rn(1.0f, s)));       // silu'(x1) = s (1 + x1 (1 - s))
+    *d1 = __fmul_rn(__fmul_rn(__fmul_rn(dh, x2), s), t);
+    *d2 = __fmul_rn(__fmul_rn(dh, x1), s);
+}
+
 // Bijective XCD-aware remap of a 1-D grid: blocks b and b+8 share an XCD (round-robin dispatch),
 // so give each XCD a contiguous run of tile ids (neighbouring tiles share operand panels in its L2).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -266,6 +288,8 @@ int launch_residual_layernorm16(const float* xin, const void* br, int dt, const 
                                 void* y, int64_t rows, int cols, float eps, hipStream_t s);
 int launch_act_fwd16(const void* h, void* y, int dt, int64_t n, int kind, hipStream_t s);
 int launch_act_bwd16(const void* h, int dt, float* dy, int64_t n, int kind, hipStream_t s);
+int launch_swiglu_fwd16(const void* x12, void* h, int dt, int64_t rows, int H, hipStream_t s);
+int launch_swiglu_bwd16(const void* x12, int dt, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s);
 int launch_colsum_b16(const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out, hipStream_t s);
 int launch_colsum_b16_ordered(const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out, void* ws,
                               size_t ws_bytes, hipStream_t s);
@@ -331,6 +355,8 @@ int launch_layernorm_bwd(const float* x, int64_t xs, const float* gamma, const f
                          float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, hipStream_t s);
 int launch_act_fwd(const float* h, float* y, int64_t n, int kind, hipStream_t s);
 int launch_act_bwd(const float* h, float* dy, int64_t n, int kind, hipStream_t s);
+int launch_swiglu_fwd(const float* x12, float* h, int64_t rows, int H, hipStream_t s);
+int launch_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s);
 int launch_colsum(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, hipStream_t s);
 int launch_axpby_cols(const float* x, int64_t xs, const float* g, float alpha, float beta, float* y, int64_t ys, int64_t rows,
                       int cols, hipStream_t s);

@@ -17,7 +17,8 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("MST_HIP_LIB", _HERE / "libmst_hip.so"))
 
 F32, F16, BF16, F8E4M3 = 0, 1, 2, 3
-EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_RESIDUAL, EPI_RESIDUAL_RELU = 0, 1, 2, 3, 4
+EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_RESIDUAL, EPI_RESIDUAL_RELU, EPI_BIAS_SWIGLU = 0, 1, 2, 3, 4, 5
+FFN_MLP, FFN_SWIGLU = 0, 1
 FUSION_TRANSFORMER, FUSION_LINEAR, FUSION_AVERAGE = 0, 1, 2
 
 _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
@@ -43,7 +44,8 @@ class VitWeights(C.Structure):
                 ("compute_dtype", _i), ("grid_h", _i), ("grid_w", _i),
                 ("patch_w", _vp), ("patch_b", _vp), ("prefix", _vp), ("pos_patch", _vp),
                 ("layers", C.POINTER(VitLayer)), ("norm_w", _vp), ("norm_b", _vp), ("fp8_linear", _i),
-                ("fp8_amax", _vp), ("fp8_amax_out", _vp), ("profiler", _vp), ("prune_last_block", _i)]
+                ("fp8_amax", _vp), ("fp8_amax_out", _vp), ("profiler", _vp), ("prune_last_block", _i),
+                ("ffn_kind", _i), ("ffn_hidden", _i)]
 
 
 class FusionWeights(C.Structure):
@@ -82,6 +84,8 @@ SIGNATURES = {
     "mst_layernorm_bwd": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _f, _vp]),
     "mst_act_fwd": (_i, [_vp, _vp, _i64, _i, _vp]),
     "mst_act_bwd": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "mst_swiglu_fwd": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "mst_swiglu_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "mst_colsum": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _vp, _vp]),
     "mst_axpby_cols": (_i, [_vp, _i64, _vp, _f, _f, _vp, _i64, _i64, _i, _vp]),
     "mst_im2col14": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
@@ -91,6 +95,8 @@ SIGNATURES = {
     "mst_residual_layernorm16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "mst_act_fwd16": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
     "mst_act_bwd16": (_i, [_vp, _i, _vp, _i64, _i, _vp]),
+    "mst_swiglu_fwd16": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
+    "mst_swiglu_bwd16": (_i, [_vp, _i, _vp, _vp, _i64, _i, _vp]),
     "mst_colsum_b16": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp]),
     "mst_colsum_b16_ordered": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
     "mst_transpose16": (_i, [_vp, _i, _i64, _i64, _i, _vp, _i64, _i64, _vp]),
@@ -253,9 +259,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epil
     _dev(w, "gemm")
     M, K = a.shape
     N = w.shape[0]
+    n_out = N // 2 if epilogue == EPI_BIAS_SWIGLU else N     # w is the row-paired w12 image (pack_swiglu): gate and value rows give one column
     if out is None:
-        out = torch.empty((M, N), dtype=out_dtype or a.dtype, device=a.device)
-    _check(load().mst_gemm(ptr(a), dt_of(a), K, ptr(w), K, ptr(bias), ptr(out), dt_of(out), N, M, N, K, epilogue,
+        out = torch.empty((M, n_out), dtype=out_dtype or a.dtype, device=a.device)
+    _check(load().mst_gemm(ptr(a), dt_of(a), K, ptr(w), K, ptr(bias), ptr(out), dt_of(out), n_out, M, N, K, epilogue,
                            ptr(gamma), col_scale, scale_cols, stream_of(a)), "mst_gemm")
     return out
 
@@ -588,6 +595,39 @@ def pack_mlp(fc1_w, fc1_b, fc2_w, fc2_b, ln_w, ln_b, ls2, dtype: torch.dtype):
     return wpack, b1p, b2f.contiguous()
 
 
+def swiglu_hidden(embed_dim: int) -> int:
+    """Hidden width of SwiGLUFFNFused(E, 4E) (swiglu_ffn.py:63-64): (int(4E * 2 / 3) + 7) // 8 * 8."""
+    return (int(4 * embed_dim * 2 / 3) + 7) // 8 * 8
+
+
+def swiglu_group(dtype: torch.dtype) -> int:
+    """Pairing group of the MST_EPI_BIAS_SWIGLU weight image per operand type (include/mst_hip.h, mst_gemm)."""
+    return 32 if dtype == torch.float32 else 16
+
+
+def pack_swiglu(w12, b12, w3, dtype: torch.dtype):
+    """Weight images of one SwiGLUFFNFused for MST_EPI_BIAS_SWIGLU (layout: include/mst_hip.h, mst_gemm).  w12 [2H, E], b12 [2H],
+    w3 [E, H] on any device (the model packs on the GPU, once per weight version).  H is padded with zero rows to Hp, a multiple of 64:
+    zero gate rows give zero hidden columns, which meet zero w3 columns.  Returns (w12p [2 Hp, E] dtype, gate and value rows interleaved
+    in groups of swiglu_group(dtype); b12p [2 Hp] fp32, paired the same way; w3p [E, Hp] dtype)."""
+    H2, E = w12.shape
+    H = H2 // 2
+    if H2 != 2 * H or tuple(b12.shape) != (H2,) or tuple(w3.shape) != (E, H):
+        raise ValueError(f"pack_swiglu: w12 {tuple(w12.shape)}, b12 {tuple(b12.shape)}, w3 {tuple(w3.shape)} are not [2H, E], [2H], [E, H]")
+    G = swiglu_group(dtype)
+    Hp = (H + 63) // 64 * 64
+    dev = w12.device
+    wg = torch.zeros((2, Hp, E), dtype=torch.float32, device=dev)
+    wg[:, :H] = w12.detach().float().view(2, H, E)
+    bg = torch.zeros((2, Hp), dtype=torch.float32, device=dev)
+    bg[:, :H] = b12.detach().float().view(2, H)
+    w12p = wg.view(2, Hp // G, G, E).permute(1, 0, 2, 3).reshape(2 * Hp, E).to(dtype).contiguous()
+    b12p = bg.view(2, Hp // G, G).permute(1, 0, 2).reshape(2 * Hp).contiguous()
+    w3p = torch.zeros((E, Hp), dtype=torch.float32, device=dev)
+    w3p[:, :H] = w3.detach().float()
+    return w12p, b12p, w3p.to(dtype).contiguous()
+
+
 def vit_workspace_bytes(w: VitWeights, H: int, W: int, chunk: int) -> int:
     return int(load().mst_vit_workspace_bytes(C.byref(w), H, W, chunk))
 
@@ -753,6 +793,35 @@ def act_fwd(h: torch.Tensor, kind: int) -> torch.Tensor:
 def act_bwd(h: torch.Tensor, dy: torch.Tensor, kind: int) -> torch.Tensor:
     _check(load().mst_act_bwd(ptr(h), ptr(dy), h.numel(), kind, stream_of(h)), "mst_act_bwd")
     return dy
+
+
+def swiglu_fwd(x12: torch.Tensor) -> torch.Tensor:
+    """mst_swiglu_fwd / mst_swiglu_fwd16 by x12's dtype: h = silu(x1) * x2 of x12 = [x1 | x2] ([rows, 2H] -> [rows, H], x12's dtype)."""
+    _dev(x12, "swiglu_fwd")
+    rows, H2 = x12.shape
+    if H2 % 2:
+        raise ValueError("swiglu_fwd: x12 must have an even number of columns")
+    h = torch.empty((rows, H2 // 2), dtype=x12.dtype, device=x12.device)
+    if x12.dtype == torch.float32:
+        _check(load().mst_swiglu_fwd(ptr(x12), ptr(h), rows, H2 // 2, stream_of(x12)), "mst_swiglu_fwd")
+    else:
+        _check(load().mst_swiglu_fwd16(ptr(x12), ptr(h), dt_of(x12), rows, H2 // 2, stream_of(x12)), "mst_swiglu_fwd16")
+    return h
+
+
+def swiglu_bwd(x12: torch.Tensor, dh: torch.Tensor) -> torch.Tensor:
+    """mst_swiglu_bwd / mst_swiglu_bwd16 by x12's dtype: the fp32 gradient [rows, 2H] of x12 from dh fp32 [rows, H]."""
+    _dev(x12, "swiglu_bwd")
+    _dev(dh, "swiglu_bwd")
+    rows, H2 = x12.shape
+    if dh.dtype != torch.float32 or tuple(dh.shape) != (rows, H2 // 2) or H2 % 2 or dh.device != x12.device:
+        raise ValueError("swiglu_bwd: dh must be fp32 [rows, H] on x12's device for x12 [rows, 2H]")
+    dx = torch.empty((rows, H2), dtype=torch.float32, device=x12.device)
+    if x12.dtype == torch.float32:
+        _check(load().mst_swiglu_bwd(ptr(x12), ptr(dh), ptr(dx), rows, H2 // 2, stream_of(x12)), "mst_swiglu_bwd")
+    else:
+        _check(load().mst_swiglu_bwd16(ptr(x12), dt_of(x12), ptr(dh), ptr(dx), rows, H2 // 2, stream_of(x12)), "mst_swiglu_bwd16")
+    return dx
 
 
 def _is16(t: torch.Tensor, what: str, name: str):

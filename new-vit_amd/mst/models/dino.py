@@ -18,6 +18,9 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
                   the model is not slice-sharded.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
                   dtype and device).  Such a call computes its logits on the TRAINING forward (fp32, or ``train_precision``'s linear
                   products), not on ``compute_dtype``.
+  ffn_layer       None (default) | 'mlp' | 'swiglufused' | 'swiglu' (the alias the reference accepts, vision_transformer.py:124): the blocks'
+                  feed-forward network.  None is what the reference builds: the plain GELU MLP, but SwiGLUFFNFused for the hub's
+                  dinov2_vitg14 (``pretrained=True, model_size='g'``).  State-dict keys follow: ``mlp.fc1/fc2`` or ``mlp.w12/w3``.
   chunk_slices    slices encoded per pass (activations of a pass sized for the Infinity Cache).
   full_attention_maps  keep the complete [n,h,N,N] softmax of every block on ``save_attn`` (needed
                   only by ``get_attention_cls``); default keeps the CLS rows ([n,h,1,N]) only.
@@ -44,6 +47,18 @@ _VIT_SIZES = {  # reference: extern/dinov2/vision_transformer.py:340-395
     "g": dict(embed_dim=1536, depth=40, num_heads=24),
 }
 SLICE_HEADS = 12  # reference dino.py:87
+_FFN_LAYERS = {"mlp": "mlp", "swiglufused": "swiglufused", "swiglu": "swiglufused"}   # vision_transformer.py:120-126
+
+
+def resolve_ffn_layer(ffn_layer, pretrained: bool, model_size: str) -> str:
+    """'mlp' or 'swiglufused'.  None: what the reference builds -- vit_giant2's default ffn_layer is 'mlp' (vision_transformer.py:63,382-396),
+    the hub's dinov2_vitg14 is configured with 'swiglufused'."""
+    if ffn_layer is None:
+        return "swiglufused" if (pretrained and model_size == "g") else "mlp"
+    try:
+        return _FFN_LAYERS[str(ffn_layer).lower()]
+    except KeyError:
+        raise ValueError(f"ffn_layer must be None or one of {sorted(_FFN_LAYERS)} (got {ffn_layer!r})") from None
 
 
 def slices2rgb(tensor):
@@ -105,13 +120,21 @@ class _Mlp(_Params):
         self.fc2 = _lin(E, 4 * E, std=0.02)
 
 
+class _SwiGLU(_Params):  # SwiGLUFFNFused(E, 4E): swiglu_ffn.py:54-72
+    def __init__(self, E):
+        super().__init__()
+        self.hidden = hip.swiglu_hidden(E)
+        self.w12 = _lin(2 * self.hidden, E, std=0.02)
+        self.w3 = _lin(E, self.hidden, std=0.02)
+
+
 class _Block(_Params):  # block.py:42-87
-    def __init__(self, E, layerscale: Optional[float]):
+    def __init__(self, E, layerscale: Optional[float], ffn_layer: str = "mlp"):
         super().__init__()
         self.norm1 = _ln(E)
         self.attn = _Attn(E)
         self.norm2 = _ln(E)
-        self.mlp = _Mlp(E)
+        self.mlp = _SwiGLU(E) if ffn_layer == "swiglufused" else _Mlp(E)
         if layerscale:
             self.ls1 = _Gamma(E, layerscale)
             self.ls2 = _Gamma(E, layerscale)
@@ -128,8 +151,9 @@ class _ViT(_Params):
     """Parameter tree of DinoVisionTransformer (vision_transformer.py:44-170)."""
 
     def __init__(self, embed_dim, depth, num_heads, img_size=224, num_register_tokens=0,
-                 layerscale: Optional[float] = None, chunked=True):
+                 layerscale: Optional[float] = None, chunked=True, ffn_layer: str = "mlp"):
         super().__init__()
+        self.ffn_layer = resolve_ffn_layer(ffn_layer, False, "")
         assert embed_dim % num_heads == 0, "embed_dim must be divisible by num_heads"
         self.embed_dim = self.num_features = embed_dim
         self.depth, self.num_heads = depth, num_heads
@@ -141,7 +165,7 @@ class _ViT(_Params):
         self.pos_embed = nn.Parameter(torch.zeros(1, g * g + 1, embed_dim))
         if num_register_tokens:
             self.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, embed_dim))
-        blocks = [_Block(embed_dim, layerscale) for _ in range(depth)]
+        blocks = [_Block(embed_dim, layerscale, self.ffn_layer) for _ in range(depth)]
         self.chunked = chunked
         self.blocks = nn.ModuleList([nn.ModuleList(blocks)]) if chunked else nn.ModuleList(blocks)
         self.norm = _ln(embed_dim)
@@ -198,6 +222,15 @@ class _SliceFusion(_Params):  # nn.TransformerEncoder(num_layers=1, norm=LayerNo
         self.norm = _ln(E)
 
 
+def _check_fp8_supported(embed_dim: int, ffn_layer: str):
+    """compute_dtype='fp8' covers the GELU MLP up to E = 1024 (mst_layernorm_fp8 stops there); fp8 is not a performance mode of this
+    build, so neither limit is lifted."""
+    if ffn_layer != "mlp":
+        raise NotImplementedError("compute_dtype='fp8' has no SwiGLU form (ffn_layer='swiglufused'): use bf16, fp16 or fp32")
+    if embed_dim > 1024:
+        raise NotImplementedError(f"compute_dtype='fp8' stops at embed_dim 1024 (mst_layernorm_fp8); embed_dim={embed_dim}: use bf16, fp16 or fp32")
+
+
 # ------------------------------------------------------------------------------------------------
 class DinoV2ClassifierSlice(BasicClassifier):
     def __init__(self, in_ch, out_ch, spatial_dims=2, pretrained=True, save_attn=False,
@@ -211,6 +244,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         # opt-in (default off: every block computes every token, as the reference does): the last block computes only what is read
         # behind it -- K/V of every token and the attention + MLP of the class tokens; results are the reference's
         prune_last_block = bool(int(kwargs.pop("prune_last_block", os.environ.get("MST_PRUNE_LAST_BLOCK", 0))))
+        ffn_layer = resolve_ffn_layer(kwargs.pop("ffn_layer", None), bool(pretrained), model_size)
         # hipGraph replay of the inference forward for small fixed shapes.  OPT-IN ("1"; "auto" = calls of at most MST_GRAPH_MAX_TOKENS
         # tokens): measured on the MI355X box the 16 x 224^2 forward takes 1.083 ms eager and 1.082 ms replayed -- the ~90 launches are
         # not the bound, the under-filled kernels are (profiles/r04d_small_shapes.txt).  Results are the eager ones bit for bit.
@@ -242,18 +276,20 @@ class DinoV2ClassifierSlice(BasicClassifier):
         self.rotary = rotary_positional_encoding
         self.model_size = model_size
 
+        self.ffn_layer = ffn_layer
         cfg = _VIT_SIZES[model_size]
-        if model_size == "g":
-            raise NotImplementedError("model_size='g' needs the SwiGLU FFN (out of scope: SURVEY.md section 2)")
+        if compute_dtype in hip.FP8_NAMES:
+            _check_fp8_supported(cfg["embed_dim"], ffn_layer)
         if pretrained:
             # reference dino.py:59-63: torch.hub fetch (needs network); hub models are img 518, LayerScale, unchunked
             name = f"dinov2_vit{model_size}14_reg" if use_registers else f"dinov2_vit{model_size}14"
             hub = torch.hub.load("facebookresearch/dinov2", name)
+            # (dinov2_vitg14: ffn_layer='swiglufused', init_values=1.0, img_size=518, block_chunks=0 -- the upstream hub's configuration)
             self.encoder = _ViT(**cfg, img_size=518, num_register_tokens=4 if use_registers else 0,
-                                layerscale=1.0, chunked=False)
+                                layerscale=1.0, chunked=False, ffn_layer=ffn_layer)
             self.encoder.load_state_dict(hub.state_dict(), strict=True)
         else:
-            self.encoder = _ViT(**cfg, img_size=224, num_register_tokens=0, layerscale=None, chunked=True)
+            self.encoder = _ViT(**cfg, img_size=224, num_register_tokens=0, layerscale=None, chunked=True, ffn_layer=ffn_layer)
         if cfg["embed_dim"] != cfg["num_heads"] * 64:
             raise NotImplementedError("the HIP attention kernels are built for head_dim 64")
         if freeze:
@@ -409,6 +445,9 @@ class DinoV2ClassifierSlice(BasicClassifier):
 
         enc = self.encoder
         E, R = enc.embed_dim, enc.num_register_tokens
+        swiglu = getattr(enc, "ffn_layer", "mlp") == "swiglufused"
+        if fp8:
+            _check_fp8_supported(E, "swiglufused" if swiglu else "mlp")
         with torch.no_grad():
             w = enc.patch_embed.proj.weight.detach().to(dev, torch.float32)          # [E,3,14,14]
             wp = torch.zeros(E, PATCH, 16, device=dev, dtype=torch.float32)
@@ -427,9 +466,19 @@ class DinoV2ClassifierSlice(BasicClassifier):
             L.proj_w, L.proj_b = hip.ptr(cmp(b.attn.proj.weight)), hip.ptr(f32(b.attn.proj.bias))
             L.ls1 = hip.ptr(f32(b.ls1.gamma)) if hasattr(b, "ls1") else None
             L.ln2_w, L.ln2_b = hip.ptr(f32(b.norm2.weight)), hip.ptr(f32(b.norm2.bias))
+            L.ls2 = hip.ptr(f32(b.ls2.gamma)) if hasattr(b, "ls2") else None
+            if swiglu:
+                # SwiGLUFFNFused: w12 as the row-paired image the MST_EPI_BIAS_SWIGLU epilogue reads, w3 zero-padded to its width
+                with torch.no_grad():
+                    w12p, b12p, w3p = hip.pack_swiglu(b.mlp.w12.weight.detach().to(dev), b.mlp.w12.bias.detach().to(dev),
+                                                      b.mlp.w3.weight.detach().to(dev), tdt)
+                keep.extend([w12p, b12p, w3p])
+                L.fc1_w, L.fc1_b = hip.ptr(w12p), hip.ptr(b12p)
+                L.fc2_w, L.fc2_b = hip.ptr(w3p), hip.ptr(f32(b.mlp.w3.bias))
+                ffn_hidden = w3p.shape[1]
+                continue
             L.fc1_w, L.fc1_b = hip.ptr(cmp(b.mlp.fc1.weight)), hip.ptr(f32(b.mlp.fc1.bias))
             L.fc2_w, L.fc2_b = hip.ptr(cmp(b.mlp.fc2.weight)), hip.ptr(f32(b.mlp.fc2.bias))
-            L.ls2 = hip.ptr(f32(b.ls2.gamma)) if hasattr(b, "ls2") else None
             if fp8:
                 # BASELINE configs[4]: the four block matrices as OCP e4m3 bytes + per-tensor scales (mst_gemm_fp8)
                 for j, (name, lin) in enumerate((("qkv_w8", b.attn.qkv), ("proj_w8", b.attn.proj),
@@ -466,6 +515,8 @@ class DinoV2ClassifierSlice(BasicClassifier):
         vit.embed_dim, vit.depth, vit.num_heads, vit.num_registers = E, enc.depth, enc.num_heads, R
         vit.compute_dtype = cdt
         vit.fp8_linear = 1 if fp8 else 0
+        if swiglu:
+            vit.ffn_kind, vit.ffn_hidden = hip.FFN_SWIGLU, ffn_hidden
         if fp8 and self._fp8_amax is not None:
             vit.fp8_amax = hip.ptr(self._fp8_amax)
         elif fp8 and self._fp8_collect:

@@ -24,6 +24,7 @@ import torch
 _VIT = {  # reference: vision_transformer.py:340-365
     "s": dict(embed_dim=384, depth=12, num_heads=6),
     "b": dict(embed_dim=768, depth=12, num_heads=12),
+    "g": dict(embed_dim=1536, depth=40, num_heads=24),   # vision_transformer.py:382-396
 }
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -71,15 +72,23 @@ def synth_state_dict(model_size: str = "s", seed: int = 0, *, img_size: int = 22
                      patch_size: int = 14, out_ch: int = 2, use_bottleneck: bool = False,
                      use_slice_pos_emb: bool = False, slice_fusion: str = "transformer",
                      rotary: str | None = None, layerscale: bool = False, chunked: bool = True,
-                     num_register_tokens: int = 0, enable_linear: bool = True) -> "OrderedDict[str, torch.Tensor]":
+                     num_register_tokens: int = 0, enable_linear: bool = True, ffn_layer: str = "mlp",
+                     depth: int | None = None) -> "OrderedDict[str, torch.Tensor]":
     """A full ``DinoV2ClassifierSlice.state_dict()`` with the reference's key layout.
 
     ``chunked=True`` gives the ``pretrained=False`` layout (``encoder.blocks.0.<i>.*``, reference
     vision_transformer.py:153-160); ``chunked=False, layerscale=True, img_size=518`` gives the hub
-    layout (``encoder.blocks.<i>.*`` with ``ls{1,2}.gamma``).
+    layout (``encoder.blocks.<i>.*`` with ``ls{1,2}.gamma``).  ``ffn_layer='swiglufused'`` (or its alias ``'swiglu'``) gives the blocks
+    SwiGLUFFNFused's ``mlp.w12`` / ``mlp.w3`` (layers/swiglu_ffn.py:54-72) instead of ``mlp.fc1`` / ``mlp.fc2``; ``depth`` overrides the
+    size's number of blocks (tests of the 1536-wide encoder use one block).  Every tensor is a function of its key alone, so the
+    defaults give the tensors they always gave.
     """
     cfg = _VIT[model_size]
-    E, depth = cfg["embed_dim"], cfg["depth"]
+    E, depth = cfg["embed_dim"], (cfg["depth"] if depth is None else int(depth))
+    if ffn_layer not in ("mlp", "swiglufused", "swiglu"):
+        raise ValueError(f"ffn_layer must be 'mlp', 'swiglufused' or 'swiglu' (got {ffn_layer!r})")
+    from .hip import swiglu_hidden                       # (ctypes binding: importing it loads no library)
+    hidden = swiglu_hidden(E)
     g = img_size // patch_size
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
 
@@ -108,8 +117,12 @@ def synth_state_dict(model_size: str = "s", seed: int = 0, *, img_size: int = 22
         if layerscale:
             sd[p + ".ls1.gamma"] = _t(p + ".ls1.gamma", (E,), seed, 0.2, 0.8)
         ln(p + ".norm2", E)
-        lin(p + ".mlp.fc1", 4 * E, E, gain=1.2)
-        lin(p + ".mlp.fc2", E, 4 * E, gain=0.7)
+        if ffn_layer == "mlp":
+            lin(p + ".mlp.fc1", 4 * E, E, gain=1.2)
+            lin(p + ".mlp.fc2", E, 4 * E, gain=0.7)
+        else:
+            lin(p + ".mlp.w12", 2 * hidden, E, gain=1.2)
+            lin(p + ".mlp.w3", E, hidden, gain=0.9)
         if layerscale:
             sd[p + ".ls2.gamma"] = _t(p + ".ls2.gamma", (E,), seed, 0.2, 0.8)
     ln("encoder.norm", E)

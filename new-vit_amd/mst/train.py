@@ -9,7 +9,8 @@ backward produces the gradient of every parameter with the kernels of csrc/k_tra
 
 The mode (train_precision, train_attention, train_storage and the autocast rule) is described, validated and resolved in
 mst/train_mode.py; `forward_train` resolves it once and the saved state carries it to the backward.
-RoPE slice transformers and register-token encoders (at their stored position grid) train; raise: the LieRE variant, ``save_attn``
+RoPE slice transformers, register-token encoders (at their stored position grid) and SwiGLU blocks (ffn_layer='swiglufused': x12 and h
+kept, mst_swiglu_bwd between the two lin_bwd calls) train; raise: the LieRE variant, ``save_attn``
 inside a training forward.
 
 Source gradient: ``source`` is an input of the node too.  When it requires grad the backward also returns d ``source`` (source's shape,
@@ -56,9 +57,14 @@ def _block_fwd_16(blk, nxt, xt: torch.Tensor, xn: torch.Tensor, mode: TrainMode,
     s["a"], s["lse"] = hip.attention_train_fwd(s["qkv16"], n, N, heads, out_dtype=mp)
     s["br1"] = hip.gemm(s["a"], _w16(blk.attn.proj, mp), blk.attn.proj.bias.detach())
     s["x1"], s["xn2"] = hip.residual_layernorm16(xt, s["br1"], g1, blk.norm2.weight.detach(), blk.norm2.bias.detach(), 1e-6)
-    s["hpre"] = hip.gemm(s["xn2"], _w16(blk.mlp.fc1, mp), blk.mlp.fc1.bias.detach())
-    s["hact"] = hip.act_fwd16(s["hpre"], 0)
-    s["br2"] = hip.gemm(s["hact"], _w16(blk.mlp.fc2, mp), blk.mlp.fc2.bias.detach())
+    if _is_swiglu(blk):                                   # SwiGLUFFNFused (swiglu_ffn.py:54-72): x12 and h where the MLP keeps hpre and hact
+        s["x12"] = hip.gemm(s["xn2"], _w16(blk.mlp.w12, mp), blk.mlp.w12.bias.detach())
+        s["h"] = hip.swiglu_fwd(s["x12"])
+        s["br2"] = hip.gemm(s["h"], _w16(blk.mlp.w3, mp), blk.mlp.w3.bias.detach())
+    else:
+        s["hpre"] = hip.gemm(s["xn2"], _w16(blk.mlp.fc1, mp), blk.mlp.fc1.bias.detach())
+        s["hact"] = hip.act_fwd16(s["hpre"], 0)
+        s["br2"] = hip.gemm(s["hact"], _w16(blk.mlp.fc2, mp), blk.mlp.fc2.bias.detach())
     x2, xn_next = hip.residual_layernorm16(s["x1"], s["br2"], g2, nxt.norm1.weight.detach() if nxt is not None else None,
                                            nxt.norm1.bias.detach() if nxt is not None else None, 1e-6)
     return s, x2, xn_next
@@ -84,12 +90,21 @@ def _block_fwd(blk, nxt, xt: torch.Tensor, xn: Optional[torch.Tensor], mode: Tra
     hip.axpby_cols(s["br1"], x1, g=blk.ls1.gamma.detach() if hasattr(blk, "ls1") else None)
     s["x1"] = x1
     s["xn2"] = hip.layernorm(x1, blk.norm2.weight.detach(), blk.norm2.bias.detach(), 1e-6)
-    s["hpre"] = _lin_fwd(s["xn2"], blk.mlp.fc1, mp, k16)
-    s["hact"] = hip.act_fwd(s["hpre"], 0)
-    s["br2"] = _lin_fwd(s["hact"], blk.mlp.fc2, mp, k16)
+    if _is_swiglu(blk):
+        s["x12"] = _lin_fwd(s["xn2"], blk.mlp.w12, mp, k16)
+        s["h"] = hip.swiglu_fwd(s["x12"])
+        s["br2"] = _lin_fwd(s["h"], blk.mlp.w3, mp, k16)
+    else:
+        s["hpre"] = _lin_fwd(s["xn2"], blk.mlp.fc1, mp, k16)
+        s["hact"] = hip.act_fwd(s["hpre"], 0)
+        s["br2"] = _lin_fwd(s["hact"], blk.mlp.fc2, mp, k16)
     x2 = x1.clone()
     hip.axpby_cols(s["br2"], x2, g=blk.ls2.gamma.detach() if hasattr(blk, "ls2") else None)
     return s, x2, None
+
+
+def _is_swiglu(blk) -> bool:
+    return hasattr(blk.mlp, "w12")
 
 
 def _lin_fwd(x: torch.Tensor, lin, mp: Optional[torch.dtype] = None, keep: Optional[dict] = None,
@@ -444,9 +459,14 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
             dbr = torch.empty_like(dx)
             hip.axpby_cols(dx, dbr, g=blk.ls2.gamma.detach(), beta=0.0)
         x16 = s.get("x16", {})
-        dh = G.lin_bwd(dbr, s["hact"], blk.mlp.fc2, X16=x16.get(id(blk.mlp.fc2)))
-        act_bwd(s["hpre"], dh, 0)
-        dxn2 = G.lin_bwd(dh, s["xn2"], blk.mlp.fc1, X16=x16.get(id(blk.mlp.fc1)))
+        if _is_swiglu(blk):                              # x2 = x1 + ls2 * w3(silu(x1') * x2'), [x1' | x2'] = w12(norm2 x1)
+            dh = G.lin_bwd(dbr, s["h"], blk.mlp.w3, X16=x16.get(id(blk.mlp.w3)))
+            dx12 = hip.swiglu_bwd(s["x12"], dh)
+            dxn2 = G.lin_bwd(dx12, s["xn2"], blk.mlp.w12, X16=x16.get(id(blk.mlp.w12)))
+        else:
+            dh = G.lin_bwd(dbr, s["hact"], blk.mlp.fc2, X16=x16.get(id(blk.mlp.fc2)))
+            act_bwd(s["hpre"], dh, 0)
+            dxn2 = G.lin_bwd(dh, s["xn2"], blk.mlp.fc1, X16=x16.get(id(blk.mlp.fc1)))
         dx1 = torch.empty_like(dx)
         G.ln_bwd(s["x1"], E, blk.norm2, dxn2, E, dx, E, dx1, E, M, E, 1e-6)
         # x1 = x0 + ls1 * proj(attn(qkv(norm1 x0)))

@@ -351,6 +351,100 @@ def case_hub_reg(synth, name, seed):
     print(name, {k: getattr(v, "shape", v) for k, v in out.items()})
 
 
+def _swiglu_encoder(embed_dim, depth, num_heads, device=None):
+    """The vendored DinoVisionTransformer as the hub configures dinov2_vitg14 (facebookresearch/dinov2 hub/backbones.py:
+    ffn_layer='swiglufused', init_values=1.0, img_size=518, block_chunks=0), at any width and depth."""
+    from functools import partial
+    vt = importlib.import_module("refmst.models.extern.dinov2.vision_transformer")
+    layers = importlib.import_module("refmst.models.extern.dinov2.layers")
+    kw = dict(patch_size=14, embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=4, ffn_layer="swiglufused", img_size=518,
+              init_values=1.0, block_chunks=0, block_fn=partial(layers.NestedTensorBlock, attn_class=layers.MemEffAttention))
+    if device is not None:                      # meta: drop_path_uniform avoids the constructor's linspace(...).item() (the rate is 0 either way)
+        with torch.device(device):
+            return vt.DinoVisionTransformer(drop_path_uniform=True, **kw)
+    return vt.DinoVisionTransformer(**kw).eval()
+
+
+def _load_encoder(enc, sd):
+    missing, unexpected = enc.load_state_dict({k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}, strict=False)
+    assert not unexpected and all("mask_token" in m for m in missing), (missing, unexpected)
+
+
+@torch.no_grad()
+def case_swiglu_ops(synth):
+    """SwiGLUFFNFused (layers/swiglu_ffn.py:54-72) alone: E = 384 (hidden 1024) and E = 128 (hidden 344, which the packed image pads to
+    384).  Weights and inputs are functions of the stored seed (tests rebuild them with synth.hash_normal); only the outputs are stored."""
+    layers = importlib.import_module("refmst.models.extern.dinov2.layers")
+    out = {"seed": np.array(31)}
+    for tag, E, rows, stream in (("384", 384, 130, 0), ("128", 128, 130, 10)):
+        ffn = layers.SwiGLUFFNFused(E, 4 * E).eval()
+        H = ffn.w3.in_features
+        ffn.w12.weight.copy_(torch.from_numpy(synth.hash_normal((2 * H, E), 31, stream + 1)) * (1.2 / E ** 0.5))
+        ffn.w12.bias.copy_(torch.from_numpy(synth.hash_normal((2 * H,), 31, stream + 2)) * 0.3)
+        ffn.w3.weight.copy_(torch.from_numpy(synth.hash_normal((E, H), 31, stream + 3)) * (0.9 / H ** 0.5))
+        ffn.w3.bias.copy_(torch.from_numpy(synth.hash_normal((E,), 31, stream + 4)) * 0.05)
+        x = torch.from_numpy(synth.hash_normal((rows, E), 31, stream + 5))
+        out[f"hidden_{tag}"] = np.array(H)
+        out[f"stream_{tag}"] = np.array(stream)
+        out[f"rows_{tag}"] = np.array(rows)
+        out[f"out_{tag}"] = np_(ffn(x))
+    np.savez_compressed(GOLD / "swiglu_ops.npz", **out)
+    print("swiglu_ops", {k: getattr(v, "shape", v) for k, v in out.items()})
+
+
+@torch.no_grad()
+def case_swiglu_s2(dino, synth, seed=32):
+    """E = 384, depth 2 SwiGLU encoder (hub configuration): embeddings of two slice stacks, and the same encoder inside the reference
+    DinoV2ClassifierSlice(pretrained=False) with save_attn."""
+    sd = synth.synth_state_dict("s", seed, img_size=518, layerscale=True, chunked=False, ffn_layer="swiglufused", depth=2)
+    enc = _swiglu_encoder(384, 2, 6)
+    _load_encoder(enc, sd)
+    out = {"seed": np.array(seed)}
+    for tag, shape in (("3x28x42", (3, 28, 42)), ("2x224x224", (2, 224, 224))):
+        x = synth.synth_volume((1, 1) + shape, seed + 100)[0, 0]
+        out[f"shape_{tag}"] = np.array(shape)
+        out[f"emb_{tag}"] = np_(enc(x[:, None].repeat(1, 3, 1, 1)))
+    model = dino.DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False)
+    model.encoder = enc
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    assert not unexpected and all(("auc_roc" in m or "acc." in m or "mask_token" in m) for m in missing), (missing, unexpected)
+    model.eval()
+    shape = (1, 1, 3, 56, 70)
+    src = synth.synth_volume(shape, seed + 101)
+    out["model_shape"] = np.array(shape)
+    out["logits"] = np_(model(src, save_attn=True))
+    out["vit_cls_rows"] = np.stack([np_(a[:, :, 0]) for a in model.attention_maps])      # [depth, n, h, N]
+    out["slice_map"] = np_(model.attention_maps_slice[-1])
+    out["plane_attention"] = np_(model.get_plane_attention())
+    out["slice_attention"] = np_(model.get_slice_attention())
+    model(src, save_attn=True)                       # the getters normalise in place (dino.py:197-202): a fresh forward for the product
+    out["attention_maps"] = np_(model.get_attention_maps())
+    np.savez_compressed(GOLD / "swiglu_s2.npz", **out)
+    print("swiglu_s2", {k: getattr(v, "shape", v) for k, v in out.items()})
+
+
+@torch.no_grad()
+def case_swiglu_g1(synth, seed=33):
+    """The same class at the 'g' width: embed_dim 1536, 24 heads, ONE block."""
+    sd = synth.synth_state_dict("g", seed, img_size=518, layerscale=True, chunked=False, ffn_layer="swiglufused", depth=1)
+    enc = _swiglu_encoder(1536, 1, 24)
+    _load_encoder(enc, sd)
+    shape = (2, 56, 70)
+    x = synth.synth_volume((1, 1) + shape, seed + 100)[0, 0]
+    out = {"seed": np.array(seed), "shape": np.array(shape), "emb": np_(enc(x[:, None].repeat(1, 3, 1, 1)))}
+    np.savez_compressed(GOLD / "swiglu_g1.npz", **out)
+    print("swiglu_g1", {k: getattr(v, "shape", v) for k, v in out.items()})
+
+
+def case_hub_vitg14_keys():
+    """Names and shapes of the state dict of the encoder the hub's dinov2_vitg14 is (vit_giant2: embed_dim 1536, depth 40, 24 heads),
+    built on the meta device: a list of names, no weights."""
+    enc = _swiglu_encoder(1536, 40, 24, device="meta")
+    keys = {k: list(v.shape) for k, v in enc.state_dict().items()}
+    (GOLD / "hub_vitg14_keys.json").write_text("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in keys.items()) + "\n}\n")   # one key per line
+    print("hub_vitg14_keys", len(keys), "entries")
+
+
 def case_resnet_fusion(dino, synth):
     """The across-slice half of ResNetSliceTrans (reference resnet.py:146-166,180-191) built from the reference's own
     TransformerEncoderLayer(d_model=512, nhead=16, dim_feedforward=512, norm_first) + final LayerNorm, cls_token, linear head,
@@ -433,6 +527,10 @@ def main():
         "rollout_1x3x84": lambda: case_rollout(dino, synth, "rollout_1x3x84", (1, 1, 3, 84, 84), 8),
         "slices2rgb": lambda: case_slices2rgb(dino, synth),
         "resnet_fusion": lambda: case_resnet_fusion(dino, synth),
+        "swiglu_ops": lambda: case_swiglu_ops(synth),
+        "swiglu_s2": lambda: case_swiglu_s2(dino, synth),
+        "swiglu_g1": lambda: case_swiglu_g1(synth),
+        "hub_vitg14_keys": lambda: case_hub_vitg14_keys(),
     }
     for name, fn in cases.items():
         if args.only and name not in args.only:
