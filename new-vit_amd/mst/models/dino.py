@@ -14,8 +14,8 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
                   per-tensor absmax scales (dynamic for activations), everything else as in bf16 mode.
   train_precision, train_attention, train_storage  the mode of the TRAINING step: see mst/train_mode.py.
   Gradients: under torch.enable_grad() the forward returns logits with one autograd node (mst/train.py) when a parameter requires grad,
-                  or when ``source`` is a floating tensor that requires grad (a frozen model: saliency, attribution), ``save_attn`` is off and
-                  the model is not slice-sharded.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
+                  or when ``source`` is a floating tensor that requires grad (a frozen model: saliency, attribution) and ``save_attn`` is off;
+                  slice-sharded or not.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
                   dtype and device).  Such a call computes its logits on the TRAINING forward (fp32, or ``train_precision``'s linear
                   products), not on ``compute_dtype``.
   ffn_layer       None (default) | 'mlp' | 'swiglufused' | 'swiglu' (the alias the reference accepts, vision_transformer.py:124): the blocks'
@@ -356,6 +356,8 @@ class DinoV2ClassifierSlice(BasicClassifier):
         ``get_plane_attention`` / ``get_attention_maps`` read, reference dino.py:190); ``attention_maps[:-1]`` then hold
         this rank's own slices only.  ``gather_all_layers=True`` gathers every block's rows (the unsharded list).
         ``get_attention_cls`` chains each rank's own full maps and gathers the result.
+        A gradient forward shards too (mst/train.py): the rank keeps the saved activations of its own slices only, the backward sums the
+        encoder's parameter gradients over the group and gathers d ``source``; every rank must be fed the same batch and the same loss.
         ``sharding``: a prepared transport (tests rehearse several ranks on one GPU with tools/rehearsal.py)."""
         self._sharding = sharding if sharding is not None else SliceSharding(group)
         self._gather_all_layers = bool(gather_all_layers)
@@ -653,12 +655,10 @@ class DinoV2ClassifierSlice(BasicClassifier):
             # training step (base_model.py:148-181): logits with ONE autograd node whose backward runs on the HIP kernels too
             if save_attn:
                 raise NotImplementedError("save_attn inside a training forward: run the attention read-outs under torch.no_grad()")
-            if self._sharding is not None and self._sharding.world_size > 1:
-                raise NotImplementedError("training under slice sharding: use data-parallel ranks (DDP) for the training step")
             from .. import train
             return train.forward_with_grad(self, source, src_key_padding_mask, bool(kwargs.get("without_linear", False)))
         if (torch.is_grad_enabled() and isinstance(source, torch.Tensor) and source.is_floating_point() and source.requires_grad
-                and not save_attn and not (self._sharding is not None and self._sharding.world_size > 1)):
+                and not save_attn):
             # gradient with respect to the input of a frozen model (saliency, attribution, adversarial checks): the same autograd node,
             # its backward runs the d x chain only and ends in the patch embedding's data gradient (mst_patch_embed_dgrad)
             from .. import train

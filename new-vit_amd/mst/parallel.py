@@ -6,7 +6,8 @@ Transformer mixes them, so rank r of G encodes slices [r*ceil(D/G), (r+1)*ceil(D
 volume and ONE all-gather of the slice embeddings ([B, D/G, E] fp32: 98 KB per volume at D=64)
 precedes the replicated fusion stage.  The message is latency-bound, so it is issued as a single
 ``all_gather_into_tensor`` (RCCL over xGMI with backend "nccl"; gloo on CPU tensors in the tests).
-Pure tensor plumbing: no arithmetic lives here.
+The training step (mst/train.py) adds one sum of the encoder's parameter gradients (``all_reduce_sum`` on one flat fp32 bucket) and, for a
+source gradient, one more ``all_gather_slices``.  Pure tensor plumbing: the only arithmetic here is the collectives' own.
 """
 from __future__ import annotations
 
@@ -31,6 +32,18 @@ class SliceSharding:
     def _all_gather(self, out: torch.Tensor, local: torch.Tensor):
         """One collective on tensors of the group's backend (device tensors over RCCL)."""
         dist.all_gather_into_tensor(out, local, group=self.group)    # rank-major concatenation on dim 0
+
+    def _all_reduce(self, flat: torch.Tensor):
+        """One in-place sum on a tensor of the group's backend (device tensors over RCCL)."""
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+
+    def all_reduce_sum(self, flat: torch.Tensor) -> torch.Tensor:
+        """Element-wise sum over the ranks, in place, of one flat contiguous tensor (the training step's bucket of encoder gradients:
+        mst/train.py).  Every rank ends with the same bits."""
+        if flat.dim() != 1 or not flat.is_contiguous():
+            raise ValueError("all_reduce_sum takes one flat contiguous tensor")
+        self._all_reduce(flat)
+        return flat
 
     def all_reduce_max(self, t: torch.Tensor) -> torch.Tensor:
         """Element-wise maximum over the ranks, in place (the fp8 scale table: every rank must quantise alike).  Built on the one

@@ -27,6 +27,17 @@ partials, LayerNorm d gamma / d beta, the bicubic pos-embed adjoint -- takes its
 slabs summed in ascending order, no floating-point atomics), and two steps on the same state and inputs give bit-identical logits, loss and
 gradients.  Flag off: the atomic kernels, as before.  The patch embedding's data gradient has no reduction across workgroups (every pixel is
 written once by one workgroup), so one entry point serves both modes.
+
+Slice sharding (mst/parallel.py; ``enable_slice_sharding`` over more than one rank): a rank encodes only its slices [d0, d1) of every volume
+(patch rows, blocks, the final LayerNorm's CLS rows), the slice embeddings are all-gathered and everything behind the encoder runs replicated
+on the full [B*D, E].  The backward runs the replicated part, takes this rank's rows of d emb through its own slices and sums the gradients of
+the ENCODER's parameters over the group as one flat fp32 bucket (only those asked for); bottleneck, slice_pos_emb, slice_fusion, cls_token and
+linear are complete and identical on every rank and do not travel.  With a source gradient the rank's [B*dl, H, W] part is all-gathered and
+every rank returns the whole d source.  Collectives, the same on every rank whatever its shard holds: forward -- the embeddings; backward -- the
+bucket if an encoder parameter needs a gradient, d source if it is asked for; a frozen encoder without a source gradient returns early on every
+rank.  A rank with an empty shard (fewer slices than ranks) launches no encoder kernel and contributes zeros.  EVERY RANK OF A GROUP MUST BE FED
+THE SAME BATCH AND THE SAME ``dout`` (the same loss on the same targets): the replicated stage is only replicated if its inputs are.  Under DDP
+over the same or a larger group the summed gradients are already identical within a sharding group, so DDP's mean leaves them as they are.
 """
 from __future__ import annotations
 
@@ -324,24 +335,61 @@ def fusion_bwd(G: "_Grads", model, t, dfeat: torch.Tensor, B: int, D: int, e: in
 
 
 def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], without_linear: bool):
-    import torch.nn as nn
     if model.rotary is not None and model.rotary != "RoPE":
         raise NotImplementedError("training step: the LieRE variant of the slice transformer is not on the HIP backward (its rotation "
                                   "generators are learned: the adjoint of the matrix exponential is not built); RoPE is")
     enc = model.encoder
-    R = int(enc.num_register_tokens)                     # register tokens (vision_transformer.py:222-230): extra prefix rows without a position
     dev = model.device
-    x = source.to(dev)
+    sh = _sharding_of(model)
+    x = source.to(dev) if sh is None else source         # a shard moves its own slices only
     B, C, D0, H, W = x.shape
     if C != 1:
         x = x.permute(0, 2, 1, 3, 4)
     D = D0 * C
-    vol = x.reshape(B * D, H, W).float().contiguous()
     assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
     assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
-    sv = {"B": B, "D": D, "H": H, "W": W, "vol": vol, "without_linear": without_linear, "src_shape": (B, C, D0, H, W)}
+    n_stored = enc.pos_embed.shape[1] - 1
+    interp = not ((H // PATCH) * (W // PATCH) == n_stored and H == W)
+    if interp and int(enc.num_register_tokens):
+        # register encoders are the hub's dinov2_vit*14_reg (anti-aliased, size-based resampling: models/dino.py::_pos_patch); the
+        # adjoint of that filter is not built -- train them at the stored grid (518 x 518 for the hub weights)
+        raise NotImplementedError("training step: register-token encoders train at their stored position grid only (the adjoint of the "
+                                  "anti-aliased position resampling is not on the HIP backward)")
+    d0, d1, dpad = sh.shard_range(D) if sh is not None else (0, D, D)
+    dl = d1 - d0                                         # this rank's slices [d0, d1) of every volume: all of them without sharding
+    vol = (x.reshape(B, D, H, W)[:, d0:d1].to(dev) if sh is not None else x).reshape(B * dl, H, W).float().contiguous()
+    mode = train_mode.resolve(model)                     # before the first collective: a refused mode raises on every rank alike
+    sv = {"B": B, "D": D, "H": H, "W": W, "vol": vol, "without_linear": without_linear, "src_shape": (B, C, D0, H, W),
+          "interp": interp, "shard": (d0, d1, dpad) if sh is not None else None}
+    sv["mp"], sv["storage16"] = mode.mp, mode.storage16   # the backward reads the resolved mode from here (an autocast region may have ended)
+    if sh is None:
+        emb = _encoder_fwd(model, sv, mode, vol, B * D, H, W)
+    else:
+        # slice sharding: the encoder on this rank's rows alone (no kernel at all on an empty shard: zeros travel), ONE all-gather of the
+        # padded shards' slice embeddings, and everything behind the encoder replicated on the full [B*D, E].  Every rank of the group
+        # must be given the same batch: the replicated stage and its gradients are only identical across ranks if it is.
+        E = enc.embed_dim
+        emb_l = torch.zeros((B, dpad, E), dtype=torch.float32, device=dev)
+        if dl:
+            emb_l[:, :dl].copy_(_encoder_fwd(model, sv, mode, vol, B * dl, H, W).view(B, dl, E))
+        emb = sh.all_gather_slices(emb_l, D).reshape(B * D, E)
+    sv["emb"] = emb
+    return _fusion_head_fwd(model, sv, emb, B, D, mask, without_linear)
+
+
+def _sharding_of(model):
+    """The model's SliceSharding if it spans more than one rank, else None."""
+    sh = getattr(model, "_sharding", None)
+    return sh if sh is not None and sh.world_size > 1 else None
+
+
+def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, W: int) -> torch.Tensor:
+    """Tokens, blocks and the final LayerNorm's CLS rows of the n slices in `vol`; what the backward needs goes into sv.  Returns the slice
+    embeddings [n, E]."""
+    enc = model.encoder
+    R = int(enc.num_register_tokens)                     # register tokens (vision_transformer.py:222-230): extra prefix rows without a position
+    dev = vol.device
     E, heads = enc.embed_dim, enc.num_heads
-    n = B * D
     gh, gw = H // PATCH, W // PATCH
     Np = gh * gw
     N = 1 + R + Np
@@ -349,14 +397,7 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     sv["R"] = R
     # ---- tokens (patch_embed.py:68-81; vision_transformer.py:213-232)
     pos = enc.pos_embed.detach()[0]
-    n_stored = pos.shape[0] - 1
-    Mg = int(math.isqrt(n_stored))
-    sv["interp"] = not (Np == n_stored and H == W)
-    if sv["interp"] and R:
-        # register encoders are the hub's dinov2_vit*14_reg (anti-aliased, size-based resampling: models/dino.py::_pos_patch); the
-        # adjoint of that filter is not built -- train them at the stored grid (518 x 518 for the hub weights)
-        raise NotImplementedError("training step: register-token encoders train at their stored position grid only (the adjoint of the "
-                                  "anti-aliased position resampling is not on the HIP backward)")
+    Mg = int(math.isqrt(pos.shape[0] - 1))
     pos_patch = hip.pos_embed_interp(pos[1:].contiguous(), Mg, gh, gw, 0.1) if sv["interp"] else pos[1:].contiguous()
     prefix = torch.zeros((1 + R, E), dtype=torch.float32, device=dev)
     prefix[:1].copy_(pos[:1])
@@ -370,8 +411,6 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     sv["wsum"] = wsum                                    # the source gradient's kernel (mst_patch_embed_dgrad) reads the same sum
     xt = hip.patch_embed(vol, wsum, enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
     # ---- blocks (block.py:89-114)
-    mode = train_mode.resolve(model)
-    sv["mp"], sv["storage16"] = mode.mp, mode.storage16   # the backward reads the resolved mode from here (an autocast region may have ended)
     blist = list(enc.block_list())
     block_fwd = _block_fwd_16 if mode.storage16 else _block_fwd
     xn = hip.layernorm(xt, blist[0].norm1.weight.detach(), blist[0].norm1.bias.detach(), 1e-6, out_dtype=mode.mp) if mode.storage16 else None
@@ -380,9 +419,13 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
         s, xt, xn = block_fwd(blk, nxt, xt, xn, mode, n, N, heads, E)
         blocks.append(s)
     sv["blocks"], sv["xL"] = blocks, xt
-    emb = hip.layernorm_rows(xt, N * E, n, E, enc.norm.weight.detach(), enc.norm.bias.detach(), 1e-6)     # CLS rows
-    sv["emb"] = emb
-    # ---- across-slice stage (dino.py:134-166)
+    return hip.layernorm_rows(xt, N * E, n, E, enc.norm.weight.detach(), enc.norm.bias.detach(), 1e-6)     # CLS rows
+
+
+def _fusion_head_fwd(model, sv, emb: torch.Tensor, B: int, D: int, mask: Optional[torch.Tensor], without_linear: bool):
+    """The across-slice stage (dino.py:134-166) and the head on the slice embeddings [B*D, E] of whole volumes."""
+    import torch.nn as nn
+    dev = emb.device
     e = model.emb_ch
     tok = _lin_fwd(emb, model.bottleneck) if hasattr(model, "bottleneck") else emb
     if hasattr(model, "slice_pos_emb"):
@@ -438,11 +481,44 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
     demb = G.lin_bwd(dtok, sv["emb"], model.bottleneck) if hasattr(model, "bottleneck") else dtok
     if not need_src and not any(p.requires_grad for p in enc.parameters()):
         return G.by_param, None                                                  # frozen encoder (dino.py:65-67)
-    # ---- encoder
+    if sv["shard"] is None:
+        return G.by_param, _encoder_bwd(G, enc, sv, demb, B * D, need_src)
+    # ---- slice sharding: this rank's rows of d emb through its own slices, then the encoder's parameter gradients summed over the group
+    # (the replicated parameters above are complete and identical on every rank already: they do not travel) and d source gathered.
+    # Every rank issues the same collectives whatever its shard holds; an empty shard launches no kernel and contributes zeros.
+    sh = _sharding_of(model)
+    d0, d1, dpad = sv["shard"]
+    dl = d1 - d0
+    dvol = _encoder_bwd(G, enc, sv, demb.reshape(B, D, -1)[:, d0:d1].reshape(B * dl, -1).contiguous(), B * dl, need_src) if dl else None
+    wanted = [p for p in enc.parameters() if G.need(p) and p is not enc.mask_token]                      # (the forward never reads mask_token)
+    if wanted:
+        # ONE flat fp32 bucket: a single concatenation fills it, the gradients handed back are views of the reduced bucket
+        if dl:
+            missing = [tuple(p.shape) for p in wanted if id(p) not in G.by_param]
+            if missing:
+                raise RuntimeError(f"training step under slice sharding: no gradient for encoder parameters of shapes {missing}")
+            flat = torch.cat([G.by_param[id(p)].reshape(-1) for p in wanted])
+        else:
+            flat = torch.zeros(sum(p.numel() for p in wanted), dtype=torch.float32, device=dev)
+        sh.all_reduce_sum(flat)
+        for p, g in zip(wanted, flat.split([p.numel() for p in wanted])):
+            G.by_param[id(p)] = g.view(p.shape)
+    if not need_src:
+        return G.by_param, None
+    dvol_l = torch.zeros((B, dpad, H * W), dtype=torch.float32, device=dev)
+    if dl:
+        dvol_l[:, :dl].copy_(dvol.view(B, dl, H * W))
+    return G.by_param, sh.all_gather_slices(dvol_l, D).view(B * D, H, W)
+
+
+def _encoder_bwd(G: "_Grads", enc, sv, demb: torch.Tensor, n: int, need_src: bool) -> Optional[torch.Tensor]:
+    """Backward of `_encoder_fwd` over its n slices from the gradient of their embeddings [n, E]: parameter gradients into G; returns d volume
+    ([n, H, W] fp32) with `need_src`."""
+    dev = demb.device
+    H, W = sv["H"], sv["W"]
     G.mp = sv["mp"]                                      # the blocks' nn.Linear products on 16-bit operands, as the forward resolved them
     act_bwd = hip.act_bwd16 if sv["storage16"] else hip.act_bwd
     E, heads = enc.embed_dim, enc.num_heads
-    n = B * D
     gh, gw = H // PATCH, W // PATCH
     Np = gh * gw
     R = sv["R"]
@@ -500,7 +576,7 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
             hip.colsum(dx.view(n, N * E)[:, (1 + r) * E:(2 + r) * E], dreg[r])
         G.put(enc.register_tokens, dreg.view(1, R, E))
     if not (G.need(enc.pos_embed) or G.need(pe.bias) or G.need(pe.weight)):
-        return G.by_param, dsrc
+        return dsrc
     dpatch = dx.view(n, N, E)[:, 1 + R:].contiguous().view(n * Np, E)
     if G.need(enc.pos_embed):
         dposp = torch.zeros(Np * E, dtype=torch.float32, device=dev)
@@ -520,7 +596,7 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
         dW = torch.empty((E, 196), dtype=torch.float32, device=dev)
         hip.gemm_ex(dpatch, col, dW, E, 196, n * Np, sa=(1, E), sb=(196, 1), sc=(196, 1))
         G.put(pe.weight, dW.view(E, 1, PATCH, PATCH).expand(E, 3, PATCH, PATCH).contiguous())
-    return G.by_param, dsrc
+    return dsrc
 
 
 def _source_grad(dvol: torch.Tensor, sv, dtype: torch.dtype, device: torch.device) -> torch.Tensor:

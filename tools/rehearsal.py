@@ -14,3 +14,8 @@ class HostStagedSharding(SliceSharding):
         host = torch.empty(out.shape, dtype=out.dtype)
         dist.all_gather_into_tensor(host, local.cpu(), group=self.group)
         out.copy_(host)
+
+    def _all_reduce(self, flat: torch.Tensor):
+        host = flat.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group)
+        flat.copy_(host)
