@@ -8,7 +8,7 @@
 //   plan        row blocks of ceil(rows * cblocks / 2,048) rows (at least 64, a multiple of 32): about 2,048 workgroups at most, each
 //               striding over its rows.  A pure function of (rows, C).
 //   reductions  no floating-point atomics: a lane sums its rows in ascending order, the 32 row lanes meet in LDS in ascending ty, ONE
-//               plain store per column goes to slab[rb], and slab_reduce (k_ordered.hip) adds the row blocks in ascending order.
+//               plain store per column goes to slab[rb], and slab_reduce (k_colsum.hip) adds the row blocks in ascending order.
 //               Bit-reproducible for fixed (rows, C), whatever the determinism flag says.
 //   rounding    an fp32 result goes through f32_rounded before its conversion: the stored bits are T(the fp32 value).
 //   bn16_reduce      SUM: sum_r z;  SQDEV: sum_r (z - mean)^2;  BWD: d gamma = sum_r m dy xhat, d beta = sum_r m dy  (m = y > 0)
@@ -20,6 +20,7 @@
 
 namespace {
 
+// This file's own load8 / store8 (they hide mst_common.h's here): the 16-bit store8 rounds inside, through f32_rounded.
 template <typename T>
 __device__ __forceinline__ void load8(const T* p, float v[8]) {
     const typename V8<T>::type t = *reinterpret_cast<const typename V8<T>::type*>(p);

@@ -1,12 +1,7 @@
 // Fixed-order reductions of the training steps (torch.use_deterministic_algorithms): the forms the step takes instead of the
-// floating-point atomics of colsum / colsqdev / bn_bwd_reduce (k_train.hip, k_conv.hip), col2im / max-pool backward (k_conv.hip)
-// and the bicubic pos-embed adjoint (k_train.hip).  Every order below is a pure function of the shape arguments: no float atomic,
-// no dependence on which workgroup finishes first.
-//   ocolsum  pass 1: workgroup (rb, cb) owns rows [rb*rpb, (rb+1)*rpb) x 64 columns; its 16 row lanes run down the rows in sequence
-//            (row r0 + ty + 16 k), the 16 lane sums meet in LDS in ascending ty and ONE plain store per column goes to slab[rb].
-//            pass 2 (slab_reduce): every column sums slab[0..nrb) -- 16 row phases, each in ascending rb, then ascending phase -- and
-//            adds the total to the output.  With one row block the first pass adds to the output itself.
-//            The row-block size depends on (rows, cols) only (the plan of launch_colsum: about 2,048 workgroups).
+// floating-point atomics of col2im / max-pool backward (k_conv.hip) and the bicubic pos-embed adjoint (k_train.hip).  Every order
+// below is a pure function of the shape arguments: no float atomic, no dependence on which workgroup finishes first.  (The ordered
+// column sums -- colsum / colsqdev / bn_bwd_reduce -- and slab_reduce are the SLAB form of k_colsum.hip's one kernel.)
 //   col2im_gather    dx[n][iy][ix][c] += sum over (ky, kx) in ascending order of the im2col entries that read this input
 //   maxpool_bwd      pass 1 stores every window's first-maximum position (0..8, torch's scan order ky, kx with a strict >);
 //                    pass 2 gives each input the dy of the (at most 4) windows whose argument it is, windows in ascending (oy, ox)
@@ -15,103 +10,6 @@
 #include "mst_common.h"
 
 namespace {
-
-enum { OP_SUM = 0, OP_SQDEV = 1, OP_BN_BWD = 2 };
-
-// OP_SUM:    acc0 = sum_r a[r][c] * (b ? b[r][c] : 1)
-// OP_SQDEV:  acc0 = sum_r (a[r][c] - m[c])^2
-// OP_BN_BWD: acc0 = sum_r b[r][c] (a[r][c] - m[c]) rs[c]  (d gamma; a = z, b = dy),  acc1 = sum_r b[r][c]  (d beta)
-// Output j of row block rb: o_j[rb * ostride + c] (= the slab), or o_j[c] += when `direct` (one row block).
-template <int OP, bool VEC>
-__global__ __launch_bounds__(256) void ocolsum_kernel(const float* __restrict__ a, int64_t as, const float* __restrict__ b, int64_t bs,
-                                                      const float* __restrict__ m, const float* __restrict__ rs, int64_t rows, int cols,
-                                                      int64_t rpb, int cblocks, float* o0, float* o1, int64_t ostride, int direct) {
-    constexpr int NA = OP == OP_BN_BWD ? 2 : 1;
-    __shared__ float red[NA][16][64 + 4];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int64_t rb = blockIdx.x / cblocks;
-    const int cb = (int)(blockIdx.x - rb * cblocks);
-    const int64_t r0 = rb * rpb, r1 = r0 + rpb < rows ? r0 + rpb : rows;
-    const int c0 = cb * 64 + tx * 4;
-    float acc[NA][4];
-    float mc[4], rc[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        acc[0][e] = acc[NA - 1][e] = 0.f;
-        const bool in = c0 + e < cols;
-        mc[e] = (OP != OP_SUM && in) ? m[c0 + e] : 0.f;
-        rc[e] = (OP == OP_BN_BWD && in) ? rs[c0 + e] : 0.f;
-    }
-    if (c0 < cols) {
-        for (int64_t r = r0 + ty; r < r1; r += 16) {
-            float av[4], bv[4];
-            if (VEC) {
-                const float4 x = *reinterpret_cast<const float4*>(a + r * as + c0);
-                av[0] = x.x; av[1] = x.y; av[2] = x.z; av[3] = x.w;
-                if (b) {
-                    const float4 y = *reinterpret_cast<const float4*>(b + r * bs + c0);
-                    bv[0] = y.x; bv[1] = y.y; bv[2] = y.z; bv[3] = y.w;
-                } else {
-                    bv[0] = bv[1] = bv[2] = bv[3] = 1.f;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const bool in = c0 + e < cols;
-                    av[e] = in ? a[r * as + c0 + e] : 0.f;
-                    bv[e] = (in && b) ? b[r * bs + c0 + e] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (OP == OP_SUM) acc[0][e] = fmaf(av[e], bv[e], acc[0][e]);
-                else if (OP == OP_SQDEV) { const float d = av[e] - mc[e]; acc[0][e] = fmaf(d, d, acc[0][e]); }
-                else {
-                    acc[0][e] = fmaf(bv[e], (av[e] - mc[e]) * rc[e], acc[0][e]);
-                    acc[NA - 1][e] += bv[e];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[j][ty][tx * 4 + e] = acc[j][e];
-    __syncthreads();
-    if (threadIdx.x < 64 * NA) {
-        const int j = threadIdx.x >> 6, cl = threadIdx.x & 63, cc = cb * 64 + cl;
-        float t = 0.f;
-#pragma unroll
-        for (int y = 0; y < 16; ++y) t += red[j][y][cl];
-        if (cc < cols) {
-            float* p = (j ? o1 : o0) + rb * ostride + cc;
-            *p = direct ? *p + t : t;
-        }
-    }
-}
-
-// out[col] += sum_{rb < nrb} slab[rb][col] for col < width; columns below `split` go to o0, the rest to o1[col - split] (either
-// nullable).  64 columns x 16 row phases per workgroup; phase p sums rb = p, p + 16, ... in sequence, the phases meet in ascending p.
-__global__ __launch_bounds__(1024) void slab_reduce_kernel(const float* __restrict__ slab, int64_t nrb, int64_t width, int64_t split,
-                                                           float* o0, float* o1) {
-    __shared__ float red[16][64];
-    const int cl = threadIdx.x & 63, p = threadIdx.x >> 6;
-    const int64_t col = (int64_t)blockIdx.x * 64 + cl;
-    float s = 0.f;
-    if (col < width) {
-#pragma unroll 8
-        for (int64_t rb = p; rb < nrb; rb += 16) s += slab[rb * width + col];
-    }
-    red[p][cl] = s;
-    __syncthreads();
-    if (p == 0 && col < width) {
-        float t = 0.f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) t += red[q][cl];
-        float* o = col < split ? (o0 ? o0 + col : nullptr) : (o1 ? o1 + (col - split) : nullptr);
-        if (o) *o += t;
-    }
-}
 
 // dx[n][iy][ix][c] += sum over (ky, kx) ascending of dcol[(n, oy, ox)][(ky, kx, c)] with oy*s - p + ky = iy, ox*s - p + kx = ix
 __global__ void col2im_gather_kernel(const float* __restrict__ dcol, int H, int W, int C, int kh, int kw, int stride, int pad, int Ho,
@@ -201,16 +99,6 @@ __global__ void maxpool_bwd_gather_kernel(const uint8_t* __restrict__ arg, const
     }
 }
 
-__device__ __forceinline__ void cubic_w(float x, float w[4]) {   // F.interpolate bicubic, A = -0.75 (as k_patch.hip, k_train.hip)
-    const float A = -0.75f;
-    float t = x + 1.0f;
-    w[0] = ((A * t - 5.0f * A) * t + 8.0f * A) * t - 4.0f * A;
-    w[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
-    t = 1.0f - x;
-    w[2] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    t = 2.0f - x;
-    w[3] = ((A * t - 5.0f * A) * t + 8.0f * A) * t - 4.0f * A;
-}
 // entry [o][m] of the dense tap matrix: the weights of output o's four taps that land on stored cell m after clamping, in tap order;
 // `hit` is false when none does
 __device__ __forceinline__ float tap_weight(int o, int m, float scale, int M, bool& hit) {
@@ -265,68 +153,7 @@ inline unsigned ogrid(int64_t n) {
 
 inline size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 
-// row blocks of the ordered column sums: the plan of launch_colsum (about 2,048 workgroups, at least 64 rows each)
-void ocolsum_plan(int64_t rows, int cols, int64_t& rpb, int64_t& rblocks) {
-    const int64_t cblocks = (cols + 63) / 64;
-    rpb = (rows * cblocks + 2047) / 2048;
-    rpb = rpb < 64 ? 64 : (rpb + 15) / 16 * 16;
-    rblocks = (rows + rpb - 1) / rpb;
-}
-
-template <int OP>
-int ocolsum_launch(const float* a, int64_t as, const float* b, int64_t bs, const float* m, const float* rs, int64_t rows, int cols,
-                   float* out0, float* out1, void* ws, size_t ws_bytes, const char* what, hipStream_t s) {
-    constexpr int NA = OP == OP_BN_BWD ? 2 : 1;
-    MST_CHECK_ARG(rows > 0 && cols > 0, "%s: rows=%lld cols=%d out of range", what, (long long)rows, cols);
-    int64_t rpb, rblocks;
-    ocolsum_plan(rows, cols, rpb, rblocks);
-    const int64_t cblocks = (cols + 63) / 64;
-    MST_CHECK_ARG(rblocks * cblocks < (1ll << 31), "%s: rows=%lld cols=%d out of range", what, (long long)rows, cols);
-    const size_t need = rblocks > 1 ? round256(sizeof(float) * (size_t)rblocks * NA * cols) : 0;
-    MST_CHECK_ARG(ws_bytes >= need && (need == 0 || ws), "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
-    const bool vec = cols % 4 == 0 && as % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 &&
-                     (!b || (bs % 4 == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0));
-    const bool direct = rblocks == 1;
-    float* slab = (float*)ws;
-    float* o0 = direct ? out0 : slab;
-    float* o1 = direct ? out1 : slab + cols;
-    const dim3 grid((unsigned)(rblocks * cblocks));
-    if (vec) ocolsum_kernel<OP, true><<<grid, dim3(256), 0, s>>>(a, as, b, bs, m, rs, rows, cols, rpb, (int)cblocks, o0, o1, (int64_t)NA * cols, direct);
-    else ocolsum_kernel<OP, false><<<grid, dim3(256), 0, s>>>(a, as, b, bs, m, rs, rows, cols, rpb, (int)cblocks, o0, o1, (int64_t)NA * cols, direct);
-    int rc = mst_check_launch(what);
-    if (rc || direct) return rc;
-    return launch_slab_reduce(slab, rblocks, (int64_t)NA * cols, cols, out0, out1, s);
-}
-
 }  // namespace
-
-size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs) {
-    if (rows <= 0 || cols <= 0) return 0;
-    int64_t rpb, rblocks;
-    ocolsum_plan(rows, cols, rpb, rblocks);
-    return rblocks > 1 ? round256(sizeof(float) * (size_t)rblocks * outputs * cols) : 0;
-}
-
-int launch_slab_reduce(const float* slab, int64_t nrb, int64_t width, int64_t split, float* o0, float* o1, hipStream_t s) {
-    MST_CHECK_ARG(nrb > 0 && width > 0 && (width + 63) / 64 < (1ll << 31), "slab_reduce: nrb=%lld width=%lld out of range", (long long)nrb,
-                  (long long)width);
-    slab_reduce_kernel<<<dim3((unsigned)((width + 63) / 64)), dim3(1024), 0, s>>>(slab, nrb, width, split, o0, o1);
-    return mst_check_launch("slab_reduce");
-}
-
-int launch_colsum_ordered(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, void* ws,
-                          size_t ws_bytes, hipStream_t s) {
-    return ocolsum_launch<OP_SUM>(a, as, b, bs, nullptr, nullptr, rows, cols, out, nullptr, ws, ws_bytes, "colsum_ordered", s);
-}
-
-int launch_colsqdev_ordered(const float* z, const float* mean, int64_t rows, int C, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-    return ocolsum_launch<OP_SQDEV>(z, C, nullptr, 0, mean, nullptr, rows, C, out, nullptr, ws, ws_bytes, "colsqdev_ordered", s);
-}
-
-int launch_bn_bwd_reduce_ordered(const float* z, const float* mean, const float* rstd, const float* dy, int64_t rows, int C, float* dgamma,
-                                 float* dbeta, void* ws, size_t ws_bytes, hipStream_t s) {
-    return ocolsum_launch<OP_BN_BWD>(z, C, dy, C, mean, rstd, rows, C, dgamma, dbeta, ws, ws_bytes, "bn_bwd_reduce_ordered", s);
-}
 
 int launch_col2im_gather(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
                          hipStream_t s) {

@@ -164,19 +164,6 @@ __global__ void prefix_rows_kernel(const float* __restrict__ prefix, int n_prefi
     x[(s * N + r) * E + e] = prefix[r * E + e];
 }
 
-// cubic convolution coefficients, A = -0.75 (what F.interpolate(mode='bicubic') uses)
-__device__ __forceinline__ void cubic_coeffs(float t, float w[4]) {
-    const float A = -0.75f;
-    float x = t + 1.0f;
-    w[0] = ((A * x - 5.0f * A) * x + 8.0f * A) * x - 4.0f * A;
-    x = t;
-    w[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
-    x = 1.0f - t;
-    w[2] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
-    x = 2.0f - t;
-    w[3] = ((A * x - 5.0f * A) * x + 8.0f * A) * x - 4.0f * A;
-}
-
 // pos [M*M, E] -> out [gh*gw, E]; source index = scale*(dst+0.5)-0.5 with scale = 1/scale_factor,
 // border taps clamped (align_corners=False, antialias off).
 __global__ void pos_interp_kernel(const float* __restrict__ pos, int M, int E, int gh, int gw, float scale_y,
@@ -190,8 +177,8 @@ __global__ void pos_interp_kernel(const float* __restrict__ pos, int M, int E, i
     const float rx = scale_x * ((float)ox + 0.5f) - 0.5f;
     const int iy = (int)floorf(ry), ix = (int)floorf(rx);
     float wy[4], wx[4];
-    cubic_coeffs(ry - (float)iy, wy);
-    cubic_coeffs(rx - (float)ix, wx);
+    cubic_w(ry - (float)iy, wy);
+    cubic_w(rx - (float)ix, wx);
     float acc = 0.f;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {

@@ -7,8 +7,10 @@
 //                  q|k|v layout of the forward (attention.py:56-66)
 //   softmax_rows / softmax_rows_bwd     P = softmax(S + key-padding mask),  dS = P o (dP - rowsum(dP o P))
 //   layernorm_bwd  dx (+ residual gradient), d gamma, d beta   (nn.LayerNorm; block.py:63,75; transformer_blocks.py:499)
-//   act_bwd        GELU (erf form, mlp.py:22) / ReLU (transformer_blocks.py:484) derivative times the upstream gradient
-//   colsum / colsum_prod / mul_cols     bias and LayerScale gradients (layer_scale.py:25-27)
+//   act_fwd / act_bwd   GELU (erf form, mlp.py:22) / ReLU (transformer_blocks.py:484) and its derivative times the upstream gradient;
+//   swiglu_fwd / _bwd   the SwiGLU FFN's gate (swiglu_ffn.py:54-72): one template per op for fp32 and the 16-bit storage types
+//   axpby_cols     LayerScale on a gradient, residual sums (layer_scale.py:25-27; the column sums of the bias and LayerScale gradients
+//                  are k_colsum.hip)
 //   im2col14       the 14x14 patches of a gray volume as rows (patch_embed.py:68-81): d W_patch = dX^T . im2col
 //   pos_interp_bwd adjoint of the bicubic position-grid resampling (vision_transformer.py:179-211)
 #include "mst_common.h"
@@ -162,87 +164,89 @@ __global__ void rope_rows_kernel(float* __restrict__ qkv, int64_t rows, int L, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// dh = dy * act'(h), in place over dy.  kind 0: GELU (erf form), 1: ReLU.
-__global__ void act_bwd_kernel(const float* __restrict__ h, float* __restrict__ dy, int64_t n, int kind) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = h[i];
-        float d;
-        if (kind == 0) d = 0.5f * (1.0f + erff(v * 0.70710678118654752440f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
-        else d = v > 0.f ? 1.f : 0.f;
-        dy[i] *= d;
-    }
+// The elementwise ops of the MLP, one template each for the three storage types T (fp32, and bf16 / fp16 of train_storage='16bit') and
+// for V = 8 elements per thread in 16-byte accesses or V = 1.  The arithmetic is fp32 and the same expression in every instantiation, so
+// the 16-bit forms return T(the fp32 form on the upcast input) and the V = 8 and V = 1 forms return the same bits.  A 16-bit store goes
+// through f32_rounded (mst_common.h): the conversion must round the fp32 result, not fuse with the product before it.
+template <int V, typename T>
+__device__ __forceinline__ void loadv(const T* p, float v[V]) {
+    if constexpr (V == 8) load8(p, v);
+    else v[0] = to_f32(p[0]);
+}
+template <int V, typename T>
+__device__ __forceinline__ void storev(T* p, const float v[V]) {
+    if constexpr (V == 8) store8(p, v);
+    else p[0] = (T)v[0];
 }
 
-// y = act(h): the forward twin (the training forward keeps the pre-activation h for the backward).
-__global__ void act_fwd_kernel(const float* __restrict__ h, float* __restrict__ y, int64_t n, int kind) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = h[i];
-        y[i] = kind == 0 ? gelu_erf(v) : fmaxf(v, 0.f);
-    }
+// y = act(h): kind 0 GELU (erf form), 1 ReLU (the training forward keeps the pre-activation h for the backward).
+template <int V, typename T>
+__device__ __forceinline__ void act_fwd_at(const T* h, T* y, int kind) {
+    float v[V];
+    loadv<V>(h, v);
+#pragma unroll
+    for (int e = 0; e < V; ++e) v[e] = f32_rounded(kind == 0 ? gelu_erf(v[e]) : fmaxf(v[e], 0.f));
+    storev<V>(y, v);
+}
+// dh = dy * act'(h), in place over dy (fp32).
+template <int V, typename T>
+__device__ __forceinline__ void act_bwd_at(const T* h, float* dy, int kind) {
+    float v[V], d[V];
+    loadv<V>(h, v);
+    loadv<V>(dy, d);
+#pragma unroll
+    for (int e = 0; e < V; ++e) d[e] *= act_deriv(v[e], kind);
+    storev<V>(dy, d);
+}
+// groups of V elements, then threads 0 .. n % V - 1 of the grid take the ragged tail one element each
+template <typename T, int V>
+__global__ __launch_bounds__(256) void act_fwd_kernel(const T* __restrict__ h, T* __restrict__ y, int64_t n, int kind) {
+    const int64_t nv = n / V, gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = gid; i < nv; i += (int64_t)gridDim.x * blockDim.x) act_fwd_at<V>(h + V * i, y + V * i, kind);
+    if (gid < n % V) act_fwd_at<1>(h + V * nv + gid, y + V * nv + gid, kind);
+}
+template <typename T, int V>
+__global__ __launch_bounds__(256) void act_bwd_kernel(const T* __restrict__ h, float* __restrict__ dy, int64_t n, int kind) {
+    const int64_t nv = n / V, gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = gid; i < nv; i += (int64_t)gridDim.x * blockDim.x) act_bwd_at<V>(h + V * i, dy + V * i, kind);
+    if (gid < n % V) act_bwd_at<1>(h + V * nv + gid, dy + V * nv + gid, kind);
 }
 
-// SwiGLU (layers/swiglu_ffn.py:54-72) on rows x12 = [x1 | x2] of 2 H columns: h[r][c] = silu(x1[r][c]) x2[r][c], and with s = sigmoid(x1)
-// dx12[r] = [dh x2 s (1 + x1 (1 - s)) | dh x1 s].  One thread per element of h; no reduction, one form for both determinism modes.
-__global__ void swiglu_fwd_kernel(const float* __restrict__ x12, float* __restrict__ h, int64_t rows, int H) {
-    const int64_t n = rows * H;
+// SwiGLU (layers/swiglu_ffn.py:54-72) on rows x12 = [x1 | x2] of 2 H columns of T: h[r][c] = silu(x1[r][c]) x2[r][c] in T, and with
+// s = sigmoid(x1) the fp32 dx12[r] = [dh x2 s (1 + x1 (1 - s)) | dh x1 s].  One thread per V columns of h (V = 8 needs H % 8 == 0: every
+// half row is then 16-byte aligned); no reduction, one form for both determinism modes.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ x12, T* __restrict__ h, int64_t rows, int H) {
+    const int hv = H / V;
+    const int64_t n = rows * hv;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = i / H;
-        const int c = (int)(i - r * H);
-        const float* x = x12 + r * 2 * H + c;
-        h[i] = swiglu_fwd_value(x[0], x[H]);
+        const int64_t r = i / hv;
+        const int c = (int)(i - r * hv) * V;
+        float a[V], b[V];
+        loadv<V>(x12 + r * 2 * H + c, a);
+        loadv<V>(x12 + r * 2 * H + c + H, b);
+#pragma unroll
+        for (int e = 0; e < V; ++e) a[e] = f32_rounded(swiglu_fwd_value(a[e], b[e]));
+        storev<V>(h + r * H + c, a);
     }
 }
-__global__ void swiglu_bwd_kernel(const float* __restrict__ x12, const float* __restrict__ dh, float* __restrict__ dx12, int64_t rows, int H) {
-    const int64_t n = rows * H;
+template <typename T, int V>
+__global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ x12, const float* __restrict__ dh, float* __restrict__ dx12,
+                                                         int64_t rows, int H) {
+    const int hv = H / V;
+    const int64_t n = rows * hv;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = i / H;
-        const int c = (int)(i - r * H);
+        const int64_t r = i / hv;
+        const int c = (int)(i - r * hv) * V;
         const int64_t o = r * 2 * H + c;
-        float d1, d2;
-        swiglu_bwd_values(x12[o], x12[o + H], dh[i], &d1, &d2);
-        dx12[o] = d1;
-        dx12[o + H] = d2;
-    }
-}
-
-// out[j] += sum_i a[i][j] * (b ? b[i][j] : 1).  A 256-thread block owns 64 columns x a chunk of rows: 16 threads x float4 across the
-// columns (VEC) or 64 threads x 1, the other 16 (4) thread rows stride down the chunk; the partial sums meet in LDS and ONE atomic per
-// column per block goes out (the round-2 kernel ran one thread per column down 256 rows: 34 workgroups for a [4112, 384] bias gradient).
-template <bool VEC>
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a, int64_t as, const float* __restrict__ b, int64_t bs, int64_t rows,
-                                                     int cols, int rows_per_block, float* __restrict__ out) {
-    // row blocks on gridDim.x (2^31 - 1 blocks), column blocks on gridDim.y: the stem's BatchNorm sums of a 2 x 128 x 512^2 ResNet
-    // step have 16.8 M rows, more row blocks than gridDim.y takes
-    constexpr int CW = VEC ? 4 : 1, TX = 64 / CW, TY = 256 / TX;
-    __shared__ float red[TY][64 + 4];
-    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    const int c = blockIdx.y * 64 + tx * CW;
-    float acc[CW];
+        float a[V], b[V], d[V], d1[V], d2[V];
+        loadv<V>(x12 + o, a);
+        loadv<V>(x12 + o + H, b);
+        loadv<V>(dh + r * H + c, d);
 #pragma unroll
-    for (int e = 0; e < CW; ++e) acc[e] = 0.f;
-    if (c < cols) {
-        for (int64_t r = r0 + ty; r < r1; r += TY) {
-            if (VEC) {
-                const float4 av = *reinterpret_cast<const float4*>(a + r * as + c);
-                const float4 bv = b ? *reinterpret_cast<const float4*>(b + r * bs + c) : make_float4(1.f, 1.f, 1.f, 1.f);
-                acc[0] = fmaf(av.x, bv.x, acc[0]); acc[CW > 1 ? 1 : 0] = fmaf(av.y, bv.y, acc[CW > 1 ? 1 : 0]);
-                acc[CW > 2 ? 2 : 0] = fmaf(av.z, bv.z, acc[CW > 2 ? 2 : 0]); acc[CW > 3 ? 3 : 0] = fmaf(av.w, bv.w, acc[CW > 3 ? 3 : 0]);
-            } else {
-                acc[0] = fmaf(a[r * as + c], b ? b[r * bs + c] : 1.f, acc[0]);
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < CW; ++e) red[ty][tx * CW + e] = acc[e];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int cc = blockIdx.y * 64 + threadIdx.x;
-        float t = 0.f;
-#pragma unroll
-        for (int y = 0; y < TY; ++y) t += red[y][threadIdx.x];
-        if (cc < cols) atomicAdd(out + cc, t);
+        for (int e = 0; e < V; ++e) swiglu_bwd_values(a[e], b[e], d[e], &d1[e], &d2[e]);
+        storev<V>(dx12 + o, d1);
+        storev<V>(dx12 + o + H, d2);
     }
 }
 
@@ -271,16 +275,6 @@ __global__ void im2col14_kernel(const T* __restrict__ vol, int H, int W, int gw,
     }
 }
 
-__device__ __forceinline__ void cubic_w(float x, float w[4]) {   // F.interpolate bicubic, A = -0.75 (as k_patch.hip)
-    const float A = -0.75f;
-    float t = x + 1.0f;
-    w[0] = ((A * t - 5.0f * A) * t + 8.0f * A) * t - 4.0f * A;
-    w[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
-    t = 1.0f - x;
-    w[2] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    t = 2.0f - x;
-    w[3] = ((A * t - 5.0f * A) * t + 8.0f * A) * t - 4.0f * A;
-}
 // adjoint of pos_interp_kernel: dpos[yy][xx][e] += wy[a] wx[b] dout[oy][ox][e]
 __global__ void pos_interp_bwd_kernel(const float* __restrict__ dout, int M, int E, int gh, int gw, float scale_y, float scale_x,
                                       float* __restrict__ dpos) {
@@ -324,22 +318,28 @@ int launch_softmax_rows_bwd(const float* P, float* dP, int64_t rows, int L, floa
     return mst_check_launch("softmax_rows_bwd");
 }
 
-int launch_layernorm_bwd(const float* x, int64_t xs, const float* gamma, const float* dy, int64_t dys, const float* dres, int64_t drs,
-                         float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, hipStream_t s) {
-    MST_CHECK_ARG(cols > 0 && cols <= 2048, "layernorm_bwd: cols=%d unsupported (<= 2048)", cols);
-    // four rows per wave at least, 1,024 workgroups at most: the d gamma / d beta atomics are per workgroup
-    const unsigned grid = (unsigned)(rows < 16 ? 1 : (rows / 16 < 1024 ? rows / 16 : 1024));
-#define LNB(CI) layernorm_bwd_kernel<CI><<<dim3(grid), dim3(256), 0, s>>>(x, xs, gamma, dy, dys, dres, drs, dx, dxs, dgamma, dbeta, rows, cols, eps)
-    if (cols <= 128) LNB(2);
-    else if (cols <= 384) LNB(6);
-    else if (cols <= 768) LNB(12);
-    else if (cols <= 1024) LNB(16);
-    else LNB(32);
-#undef LNB
-    return mst_check_launch("layernorm_bwd");
+// four rows per wave at least, 1,024 workgroups at most (the d gamma / d beta atomics or slabs are per workgroup); a function of rows
+// only: so is the summation order of the ordered form
+static unsigned layernorm_bwd_grid(int64_t rows) { return (unsigned)(rows < 16 ? 1 : (rows / 16 < 1024 ? rows / 16 : 1024)); }
+
+template <bool SLAB>
+static int layernorm_bwd_go(const char* what, const float* x, int64_t xs, const float* gamma, const float* dy, int64_t dys, const float* dres,
+                            int64_t drs, float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, float* slab,
+                            hipStream_t s) {
+    MST_CHECK_ARG(cols > 0 && cols <= 2048, "%s: cols=%d unsupported (<= 2048)", what, cols);
+    const auto kernel = cols <= 128    ? layernorm_bwd_kernel<2, SLAB>
+                        : cols <= 384  ? layernorm_bwd_kernel<6, SLAB>
+                        : cols <= 768  ? layernorm_bwd_kernel<12, SLAB>
+                        : cols <= 1024 ? layernorm_bwd_kernel<16, SLAB>
+                                       : layernorm_bwd_kernel<32, SLAB>;
+    kernel<<<dim3(layernorm_bwd_grid(rows)), dim3(256), 0, s>>>(x, xs, gamma, dy, dys, dres, drs, dx, dxs, dgamma, dbeta, rows, cols, eps, slab);
+    return mst_check_launch(what);
 }
 
-static unsigned layernorm_bwd_grid(int64_t rows) { return (unsigned)(rows < 16 ? 1 : (rows / 16 < 1024 ? rows / 16 : 1024)); }
+int launch_layernorm_bwd(const float* x, int64_t xs, const float* gamma, const float* dy, int64_t dys, const float* dres, int64_t drs,
+                         float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, hipStream_t s) {
+    return layernorm_bwd_go<false>("layernorm_bwd", x, xs, gamma, dy, dys, dres, drs, dx, dxs, dgamma, dbeta, rows, cols, eps, nullptr, s);
+}
 
 size_t layernorm_bwd_ordered_workspace_bytes(int64_t rows, int cols) {
     return rows > 0 && cols > 0 ? ((size_t)layernorm_bwd_grid(rows) * 2 * cols * sizeof(float) + 255) / 256 * 256 : 0;
@@ -348,21 +348,12 @@ size_t layernorm_bwd_ordered_workspace_bytes(int64_t rows, int cols) {
 int launch_layernorm_bwd_ordered(const float* x, int64_t xs, const float* gamma, const float* dy, int64_t dys, const float* dres, int64_t drs,
                                  float* dx, int64_t dxs, float* dgamma, float* dbeta, int64_t rows, int cols, float eps, void* ws,
                                  size_t ws_bytes, hipStream_t s) {
-    MST_CHECK_ARG(cols > 0 && cols <= 2048, "layernorm_bwd_ordered: cols=%d unsupported (<= 2048)", cols);
     const size_t need = layernorm_bwd_ordered_workspace_bytes(rows, cols);
     MST_CHECK_ARG(ws && ws_bytes >= need, "layernorm_bwd_ordered: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    const unsigned grid = layernorm_bwd_grid(rows);                     // a function of rows only: so is the summation order
     float* slab = (float*)ws;
-#define LNB(CI) layernorm_bwd_kernel<CI, true><<<dim3(grid), dim3(256), 0, s>>>(x, xs, gamma, dy, dys, dres, drs, dx, dxs, dgamma, dbeta, rows, cols, eps, slab)
-    if (cols <= 128) LNB(2);
-    else if (cols <= 384) LNB(6);
-    else if (cols <= 768) LNB(12);
-    else if (cols <= 1024) LNB(16);
-    else LNB(32);
-#undef LNB
-    int rc = mst_check_launch("layernorm_bwd_ordered");
+    int rc = layernorm_bwd_go<true>("layernorm_bwd_ordered", x, xs, gamma, dy, dys, dres, drs, dx, dxs, dgamma, dbeta, rows, cols, eps, slab, s);
     if (rc || (!dgamma && !dbeta)) return rc;
-    return launch_slab_reduce(slab, grid, 2 * (int64_t)cols, cols, dgamma, dbeta, s);
+    return launch_slab_reduce(slab, layernorm_bwd_grid(rows), 2 * (int64_t)cols, cols, dgamma, dbeta, s);
 }
 
 int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const float* freqs, float sign, hipStream_t s) {
@@ -371,41 +362,80 @@ int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const f
     return mst_check_launch("rope_rows");
 }
 
-int launch_act_bwd(const float* h, float* dy, int64_t n, int kind, hipStream_t s) {
-    act_bwd_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(h, dy, n, kind);
-    return mst_check_launch("act_bwd");
+// The elementwise launchers: V = 8 when `v8` (every base 16-byte aligned; SwiGLU: H % 8 == 0 as well), one element per thread otherwise.
+// The fp32 entry points take any pointer; the 16-bit ones refuse misaligned bases, so act has no 16-bit V = 1 kernel.
+template <typename T>
+static int act_fwd_t(const char* what, const void* h, void* y, int64_t n, int kind, bool v8, hipStream_t s) {
+    if (v8) act_fwd_kernel<T, 8><<<dim3(grid_for(n >> 3)), dim3(256), 0, s>>>((const T*)h, (T*)y, n, kind);
+    else if constexpr (sizeof(T) == 4) act_fwd_kernel<T, 1><<<dim3(grid_for(n)), dim3(256), 0, s>>>((const T*)h, (T*)y, n, kind);
+    return mst_check_launch(what);
 }
-
-int launch_swiglu_fwd(const float* x12, float* h, int64_t rows, int H, hipStream_t s) {
-    swiglu_fwd_kernel<<<dim3(grid_for(rows * H)), dim3(256), 0, s>>>(x12, h, rows, H);
-    return mst_check_launch("swiglu_fwd");
+template <typename T>
+static int act_bwd_t(const char* what, const void* h, float* dy, int64_t n, int kind, bool v8, hipStream_t s) {
+    if (v8) act_bwd_kernel<T, 8><<<dim3(grid_for(n >> 3)), dim3(256), 0, s>>>((const T*)h, dy, n, kind);
+    else if constexpr (sizeof(T) == 4) act_bwd_kernel<T, 1><<<dim3(grid_for(n)), dim3(256), 0, s>>>((const T*)h, dy, n, kind);
+    return mst_check_launch(what);
 }
-
-int launch_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s) {
-    swiglu_bwd_kernel<<<dim3(grid_for(rows * H)), dim3(256), 0, s>>>(x12, dh, dx12, rows, H);
-    return mst_check_launch("swiglu_bwd");
+template <typename T>
+static int swiglu_fwd_t(const char* what, const void* x12, void* h, int64_t rows, int H, bool v8, hipStream_t s) {
+    if (v8) swiglu_fwd_kernel<T, 8><<<dim3(grid_for(rows * (H / 8))), dim3(256), 0, s>>>((const T*)x12, (T*)h, rows, H);
+    else swiglu_fwd_kernel<T, 1><<<dim3(grid_for(rows * H)), dim3(256), 0, s>>>((const T*)x12, (T*)h, rows, H);
+    return mst_check_launch(what);
+}
+template <typename T>
+static int swiglu_bwd_t(const char* what, const void* x12, const float* dh, float* dx12, int64_t rows, int H, bool v8, hipStream_t s) {
+    if (v8) swiglu_bwd_kernel<T, 8><<<dim3(grid_for(rows * (H / 8))), dim3(256), 0, s>>>((const T*)x12, dh, dx12, rows, H);
+    else swiglu_bwd_kernel<T, 1><<<dim3(grid_for(rows * H)), dim3(256), 0, s>>>((const T*)x12, dh, dx12, rows, H);
+    return mst_check_launch(what);
 }
 
 int launch_act_fwd(const float* h, float* y, int64_t n, int kind, hipStream_t s) {
-    act_fwd_kernel<<<dim3(grid_for(n)), dim3(256), 0, s>>>(h, y, n, kind);
-    return mst_check_launch("act_fwd");
+    return act_fwd_t<float>("act_fwd", h, y, n, kind, aligned(h, 16) && aligned(y, 16), s);
 }
 
-int launch_colsum(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, hipStream_t s) {
-    MST_CHECK_ARG(rows > 0 && cols > 0, "colsum: rows=%lld cols=%d out of range", (long long)rows, cols);
-    const int cblocks = (cols + 63) / 64;
-    MST_CHECK_ARG(cblocks <= 65535, "colsum: cols=%d out of range", cols);
-    // enough blocks to fill the chip (about 2,048), chunks of at least 64 rows so that the atomics stay few
-    int64_t rpb = (rows * cblocks + 2047) / 2048;
-    rpb = rpb < 64 ? 64 : (rpb + 15) / 16 * 16;
-    const int64_t rblocks = (rows + rpb - 1) / rpb;
-    MST_CHECK_ARG(rblocks < (1ll << 31) && rpb < (1ll << 31), "colsum: rows=%lld out of range", (long long)rows);
-    const bool vec = cols % 4 == 0 && as % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 &&
-                     (!b || (bs % 4 == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0));
-    const dim3 grid((unsigned)rblocks, cblocks);
-    if (vec) colsum_kernel<true><<<grid, dim3(256), 0, s>>>(a, as, b, bs, rows, cols, (int)rpb, out);
-    else colsum_kernel<false><<<grid, dim3(256), 0, s>>>(a, as, b, bs, rows, cols, (int)rpb, out);
-    return mst_check_launch("colsum");
+int launch_act_bwd(const float* h, float* dy, int64_t n, int kind, hipStream_t s) {
+    return act_bwd_t<float>("act_bwd", h, dy, n, kind, aligned(h, 16) && aligned(dy, 16), s);
+}
+
+int launch_swiglu_fwd(const float* x12, float* h, int64_t rows, int H, hipStream_t s) {
+    return swiglu_fwd_t<float>("swiglu_fwd", x12, h, rows, H, H % 8 == 0 && aligned(x12, 16) && aligned(h, 16), s);
+}
+
+int launch_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s) {
+    return swiglu_bwd_t<float>("swiglu_bwd", x12, dh, dx12, rows, H, H % 8 == 0 && aligned(x12, 16) && aligned(dh, 16) && aligned(dx12, 16), s);
+}
+
+static int bad_dtype16(const char* what, int dt) {
+    mst_set_error("%s: dtype %d (bf16 / f16)", what, dt);
+    return MST_EINVAL;
+}
+
+int launch_act_fwd16(const void* h, void* y, int dt, int64_t n, int kind, hipStream_t s) {
+    MST_CHECK_ARG(aligned(h, 16) && aligned(y, 16), "act_fwd16: bases must be 16-byte aligned");
+    if (dt == MST_BF16) return act_fwd_t<bf16_t>("act_fwd16", h, y, n, kind, true, s);
+    if (dt == MST_F16) return act_fwd_t<f16_t>("act_fwd16", h, y, n, kind, true, s);
+    return bad_dtype16("act_fwd16", dt);
+}
+
+int launch_act_bwd16(const void* h, int dt, float* dy, int64_t n, int kind, hipStream_t s) {
+    MST_CHECK_ARG(aligned(h, 16) && aligned(dy, 16), "act_bwd16: bases must be 16-byte aligned");
+    if (dt == MST_BF16) return act_bwd_t<bf16_t>("act_bwd16", h, dy, n, kind, true, s);
+    if (dt == MST_F16) return act_bwd_t<f16_t>("act_bwd16", h, dy, n, kind, true, s);
+    return bad_dtype16("act_bwd16", dt);
+}
+
+int launch_swiglu_fwd16(const void* x12, void* h, int dt, int64_t rows, int H, hipStream_t s) {
+    MST_CHECK_ARG(aligned(x12, 16) && aligned(h, 16), "swiglu_fwd16: bases must be 16-byte aligned");
+    if (dt == MST_BF16) return swiglu_fwd_t<bf16_t>("swiglu_fwd16", x12, h, rows, H, H % 8 == 0, s);
+    if (dt == MST_F16) return swiglu_fwd_t<f16_t>("swiglu_fwd16", x12, h, rows, H, H % 8 == 0, s);
+    return bad_dtype16("swiglu_fwd16", dt);
+}
+
+int launch_swiglu_bwd16(const void* x12, int dt, const float* dh, float* dx12, int64_t rows, int H, hipStream_t s) {
+    MST_CHECK_ARG(aligned(x12, 16) && aligned(dh, 16) && aligned(dx12, 16), "swiglu_bwd16: bases must be 16-byte aligned");
+    if (dt == MST_BF16) return swiglu_bwd_t<bf16_t>("swiglu_bwd16", x12, dh, dx12, rows, H, H % 8 == 0, s);
+    if (dt == MST_F16) return swiglu_bwd_t<f16_t>("swiglu_bwd16", x12, dh, dx12, rows, H, H % 8 == 0, s);
+    return bad_dtype16("swiglu_bwd16", dt);
 }
 
 int launch_axpby_cols(const float* x, int64_t xs, const float* g, float alpha, float beta, float* y, int64_t ys, int64_t rows,

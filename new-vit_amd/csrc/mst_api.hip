@@ -257,7 +257,7 @@ int mst_swiglu_bwd(const float* x12, const float* dh, float* dx12, int64_t rows,
     MST_CHECK_ARG(x12 && dh && dx12 && rows > 0 && hidden > 0, "swiglu_bwd: bad arguments");
     return launch_swiglu_bwd(x12, dh, dx12, rows, hidden, (hipStream_t)stream);
 }
-// ---- 16-bit storage mode of the training step (k_train16.hip)
+// ---- 16-bit storage mode of the training step (k_train16.hip; act / swiglu in k_train.hip, the column sums in k_colsum.hip)
 int mst_residual_layernorm16(const float* x_in, const void* br, int dtype, const float* gamma, float* x_out, const float* ln_w,
                              const float* ln_b, void* y, int64_t rows, int cols, float eps, mst_stream_t stream) {
     MST_CHECK_ARG(x_in && br && x_out && (!y || (ln_w && ln_b)), "residual_layernorm16: null pointer");

@@ -72,6 +72,51 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ float gelu_erf(float v) {  // nn.GELU() exact form (mlp.py:22)
     return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
 }
+// act'(v) of the training step's act_bwd.  kind 0: GELU (erf form), 1: ReLU.
+__device__ __forceinline__ float act_deriv(float v, int kind) {
+    if (kind == 0) return 0.5f * (1.0f + erff(v * 0.70710678118654752440f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
+    return v > 0.f ? 1.f : 0.f;
+}
+
+// eight consecutive elements as fp32, in 16-byte accesses (two for fp32).  The 16-bit store rounds to nearest even what it is given: a
+// kernel whose output must be T(its fp32 result) passes the values through f32_rounded first.
+template <typename T>
+__device__ __forceinline__ void load8(const T* p, float v[8]) {
+    const typename V8<T>::type t = *reinterpret_cast<const typename V8<T>::type*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+}
+template <typename T>
+__device__ __forceinline__ void store8(T* p, const float v[8]) {
+    typename V8<T>::type t;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t[e] = (T)v[e];                     // round to nearest even
+    *reinterpret_cast<typename V8<T>::type*>(p) = t;
+}
+__device__ __forceinline__ void load8(const float* p, float v[8]) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+}
+__device__ __forceinline__ void store8(float* p, const float v[8]) {
+    f32x4 a, b;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { a[e] = v[e]; b[e] = v[4 + e]; }
+    *reinterpret_cast<f32x4*>(p) = a;
+    *reinterpret_cast<f32x4*>(p + 4) = b;
+}
+
+// cubic convolution coefficients of the four taps around fraction x, A = -0.75 (what F.interpolate(mode='bicubic') uses)
+__device__ __forceinline__ void cubic_w(float x, float w[4]) {
+    const float A = -0.75f;
+    float t = x + 1.0f;
+    w[0] = ((A * t - 5.0f * A) * t + 8.0f * A) * t - 4.0f * A;
+    w[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
+    t = 1.0f - x;
+    w[2] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+    t = 2.0f - x;
+    w[3] = ((A * t - 5.0f * A) * t + 8.0f * A) * t - 4.0f * A;
+}
 
 // GELU for 16-bit outputs: erf by Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7 on erf, <= 5e-7 abs /
 // 2e-4 rel on gelu: far below one fp16/bf16 ulp), one v_rcp + one v_exp instead of libm erff.
@@ -138,9 +183,9 @@ __device__ __forceinline__ float swiglu_gate(float g, float v) {
 }
 
 // SwiGLU of the training step (layers/swiglu_ffn.py:54-72; x12 = [x1 | x2] as chunk(2, dim=-1) gives it): h = silu(x1) x2 and its
-// gradient, in fp32 with every product spelled out (no contraction left to the compiler), so that the fp32 kernels of k_train.hip and
-// the 16-bit-storage kernels of k_train16.hip return the same bits on the same values.  x1 -> -inf side: expf overflows to inf, s = 0,
-// h = (x1 / inf) * x2 = -0 * x2; nothing is NaN for finite inputs.
+// gradient, in fp32 with every product spelled out (no contraction left to the compiler), so that every instantiation of the
+// swiglu kernels of k_train.hip (fp32 / 16-bit storage, 8 or 1 columns per thread) returns the same bits on the same values.
+// x1 -> -inf side: expf overflows to inf, s = 0, h = (x1 / inf) * x2 = -0 * x2; nothing is NaN for finite inputs.
 __device__ __forceinline__ float swiglu_sigmoid(float x1) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x1))); }
 __device__ __forceinline__ float swiglu_fwd_value(float x1, float x2) { return __fmul_rn(__fdiv_rn(x1, __fadd_rn(1.0f, expf(-x1))), x2); }
 __device__ __forceinline__ void swiglu_bwd_values(float x1, float x2, float dh, float* d1, float* d2) {
@@ -168,6 +213,7 @@ void mst_set_error(const char* fmt, ...);
         }                                       \
     } while (0)
 int mst_check_launch(const char* what);
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): the attribute is per device, and a process may drive
 // several GPUs.  Thread-safe; `slot` is a static per-kernel token owned by the call site.
 struct mst_lds_once { unsigned long long done_mask = 0; };
@@ -283,7 +329,7 @@ size_t attn_train_workspace_bytes(int n_seq, int N, int heads);
 int launch_attn_train_fwd(const void* qkv, int dt, int n_seq, int N, int heads, void* out, int out16, float* lse, hipStream_t s);
 int launch_attn_train_bwd(const void* qkv, int dt, const void* out, int out16, const float* dout, const float* lse, int n_seq, int N, int heads,
                           float dq_scale, float* dqkv, void* ws, size_t ws_bytes, hipStream_t s);
-// row kernels of the 16-bit storage mode (k_train16.hip)
+// row kernels of the 16-bit storage mode (k_train16.hip; the act / swiglu forms in k_train.hip, the column sums in k_colsum.hip)
 int launch_residual_layernorm16(const float* xin, const void* br, int dt, const float* gamma, float* xout, const float* w, const float* b,
                                 void* y, int64_t rows, int cols, float eps, hipStream_t s);
 int launch_act_fwd16(const void* h, void* y, int dt, int64_t n, int kind, hipStream_t s);
@@ -388,7 +434,7 @@ int launch_pad_axis(float* v, int n0, int n1, int n2, int axis, int lo, int hi, 
 int launch_copy_block(const float* src, int sn1, int sn2, int s0, int s1, int s2, float* dst, int dn1, int dn2, int d0, int d1,
                       int d2, int c0, int c1, int c2, hipStream_t s);
 int launch_znorm(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, hipStream_t s);
-// fixed-order reductions (k_ordered.hip, and the ordered forms in k_train.hip / k_conv.hip / k_input.hip): bit-reproducible for fixed
+// fixed-order reductions (k_colsum.hip, k_ordered.hip, and the ordered forms in k_train.hip / k_conv.hip / k_input.hip): bit-reproducible for fixed
 // shape arguments, no floating-point atomics
 size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs);
 int launch_slab_reduce(const float* slab, int64_t nrb, int64_t width, int64_t split, float* o0, float* o1, hipStream_t s);

@@ -91,7 +91,7 @@ SIGNATURES = {
     "mst_im2col14": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_pos_embed_interp_bwd": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp]),
     "mst_patch_embed_dgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    # 16-bit storage mode of the training step (csrc/k_train16.hip)
+    # 16-bit storage mode of the training step (csrc/k_train16.hip; act / swiglu in k_train.hip, the column sums in k_colsum.hip)
     "mst_residual_layernorm16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "mst_act_fwd16": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
     "mst_act_bwd16": (_i, [_vp, _i, _vp, _i64, _i, _vp]),
@@ -785,13 +785,21 @@ def layernorm_bwd(x, x_stride, gamma, dy, dy_stride, dres, dres_stride, dx, dx_s
 
 
 def act_fwd(h: torch.Tensor, kind: int) -> torch.Tensor:
+    """mst_act_fwd / mst_act_fwd16 by h's dtype: act(h) in h's dtype (kind 0: GELU, 1: ReLU)."""
     y = torch.empty_like(h)
-    _check(load().mst_act_fwd(ptr(h), ptr(y), h.numel(), kind, stream_of(h)), "mst_act_fwd")
+    if h.dtype == torch.float32:
+        _check(load().mst_act_fwd(ptr(h), ptr(y), h.numel(), kind, stream_of(h)), "mst_act_fwd")
+    else:
+        _check(load().mst_act_fwd16(ptr(h), ptr(y), dt_of(h), h.numel(), kind, stream_of(h)), "mst_act_fwd16")
     return y
 
 
 def act_bwd(h: torch.Tensor, dy: torch.Tensor, kind: int) -> torch.Tensor:
-    _check(load().mst_act_bwd(ptr(h), ptr(dy), h.numel(), kind, stream_of(h)), "mst_act_bwd")
+    """mst_act_bwd / mst_act_bwd16 by h's dtype: dy (fp32, in place) *= act'(h)."""
+    if h.dtype == torch.float32:
+        _check(load().mst_act_bwd(ptr(h), ptr(dy), h.numel(), kind, stream_of(h)), "mst_act_bwd")
+    else:
+        _check(load().mst_act_bwd16(ptr(h), dt_of(h), ptr(dy), h.numel(), kind, stream_of(h)), "mst_act_bwd16")
     return dy
 
 

@@ -23,7 +23,7 @@ patch-embedding data gradient only for ``source``.
 
 Determinism: while ``torch.use_deterministic_algorithms(True)`` is set (``warn_only`` too; read at every call, so it may be toggled
 between steps) every floating-point reduction of the step -- bias / LayerScale / token / pos-embed column sums, the split-K weight-gradient
-partials, LayerNorm d gamma / d beta, the bicubic pos-embed adjoint -- takes its fixed-order entry point (csrc/k_ordered.hip: per-workgroup
+partials, LayerNorm d gamma / d beta, the bicubic pos-embed adjoint -- takes its fixed-order entry point (csrc/k_colsum.hip, csrc/k_ordered.hip: per-workgroup
 slabs summed in ascending order, no floating-point atomics), and two steps on the same state and inputs give bit-identical logits, loss and
 gradients.  Flag off: the atomic kernels, as before.  The patch embedding's data gradient has no reduction across workgroups (every pixel is
 written once by one workgroup), so one entry point serves both modes.
@@ -74,7 +74,7 @@ def _block_fwd_16(blk, nxt, xt: torch.Tensor, xn: torch.Tensor, mode: TrainMode,
         s["br2"] = hip.gemm(s["h"], _w16(blk.mlp.w3, mp), blk.mlp.w3.bias.detach())
     else:
         s["hpre"] = hip.gemm(s["xn2"], _w16(blk.mlp.fc1, mp), blk.mlp.fc1.bias.detach())
-        s["hact"] = hip.act_fwd16(s["hpre"], 0)
+        s["hact"] = hip.act_fwd(s["hpre"], 0)
         s["br2"] = hip.gemm(s["hact"], _w16(blk.mlp.fc2, mp), blk.mlp.fc2.bias.detach())
     x2, xn_next = hip.residual_layernorm16(s["x1"], s["br2"], g2, nxt.norm1.weight.detach() if nxt is not None else None,
                                            nxt.norm1.bias.detach() if nxt is not None else None, 1e-6)
@@ -517,7 +517,6 @@ def _encoder_bwd(G: "_Grads", enc, sv, demb: torch.Tensor, n: int, need_src: boo
     dev = demb.device
     H, W = sv["H"], sv["W"]
     G.mp = sv["mp"]                                      # the blocks' nn.Linear products on 16-bit operands, as the forward resolved them
-    act_bwd = hip.act_bwd16 if sv["storage16"] else hip.act_bwd
     E, heads = enc.embed_dim, enc.num_heads
     gh, gw = H // PATCH, W // PATCH
     Np = gh * gw
@@ -541,7 +540,7 @@ def _encoder_bwd(G: "_Grads", enc, sv, demb: torch.Tensor, n: int, need_src: boo
             dxn2 = G.lin_bwd(dx12, s["xn2"], blk.mlp.w12, X16=x16.get(id(blk.mlp.w12)))
         else:
             dh = G.lin_bwd(dbr, s["hact"], blk.mlp.fc2, X16=x16.get(id(blk.mlp.fc2)))
-            act_bwd(s["hpre"], dh, 0)
+            hip.act_bwd(s["hpre"], dh, 0)
             dxn2 = G.lin_bwd(dh, s["xn2"], blk.mlp.fc1, X16=x16.get(id(blk.mlp.fc1)))
         dx1 = torch.empty_like(dx)
         G.ln_bwd(s["x1"], E, blk.norm2, dxn2, E, dx, E, dx1, E, M, E, 1e-6)

@@ -18,7 +18,7 @@
                   block i), xn1, xn2, a, br1, br2 [E] and qkv16 [3E], hpre, hact [4E] in 16 bits (SwiGLU blocks: x12 [2H] and h [H] in their place,
                   2H + H = 8E values as well) -- 40 E bytes plus the log-sum-exp instead of 66 E, and no 16-bit operand images beside them.  Each is written in 16 bits by its producer (the LayerNorm,
                   the GEMM epilogue, the attention epilogue, the GELU or mst_swiglu_fwd16) and is itself the operand of the forward product behind it, of that
-                  product's weight gradient and of the elementwise backward kernels (csrc/k_train16.hip: residual + LayerScale + LayerNorm
+                  product's weight gradient and of the elementwise backward kernels (csrc/k_train16.hip, k_train.hip, k_colsum.hip: residual + LayerScale + LayerNorm
                   in one pass, GELU 16 -> 16 and its derivative, the LayerScale gradient with a 16-bit factor, the transposed operand image
                   above 12,288 tokens; the flash kernels with a 16-bit output).
                   ResNet (csrc/k_bn16.hip): z and y of every convolution + BatchNorm unit.  A unit takes its input in T, writes z in T

@@ -1,4 +1,4 @@
-"""torch.use_deterministic_algorithms(True) on the HIP training steps and znormalize: the fixed-order entry points (csrc/k_ordered.hip and
+"""torch.use_deterministic_algorithms(True) on the HIP training steps and znormalize: the fixed-order entry points (csrc/k_colsum.hip, csrc/k_ordered.hip and
 the ordered forms beside the atomic kernels) are bit-reproducible on inputs where the summation order visibly matters, agree with an fp64
 reference and with the atomic kernels within fp32 reassociation error, are the ONLY reductions a step reaches under the flag, and make whole
 training steps -- logits, loss, every gradient, BatchNorm running statistics -- bit-identical from run to run."""
@@ -85,6 +85,28 @@ def test_ordered_colsum_into_a_nonzero_out_with_b_and_a_strided_view(det):
     wide = _cancelling(777, 3 * 388, 4)                                   # a column block of a wider matrix (the CLS / register rows)
     _colsum_case(wide[:, 388:2 * 388], out0=torch.randn(388, device="cuda"))
     _colsum_case(_cancelling(301, 37, 5))                                 # odd columns: the scalar loads
+
+
+@pytest.mark.parametrize("bdt", [None, torch.float32, torch.bfloat16, torch.float16], ids=["no_b", "b_fp32", "b_bf16", "b_fp16"])
+def test_colsum_single_row_block_atomic_equals_ordered_bits(det, bdt):
+    """One row block (rows <= 64, the plan's minimum): the atomic and the ordered entry points are instantiations of one kernel
+    (csrc/k_colsum.hip), walk the rows in the same order and add one total per column to `out` -- so the bits are equal.  cols: 4 and 64
+    one column block, 68 a ragged second one, 388 the register-token width; contiguous 16-byte-aligned operands (the vector layout)."""
+    g = torch.Generator(device="cuda").manual_seed(21)
+    for rows in (1, 17, 64):
+        for cols in (4, 64, 68, 388):
+            a = torch.randn(rows, cols, device="cuda", generator=g) * 1e3
+            b = None if bdt is None else torch.randn(rows, cols, device="cuda", generator=g).to(bdt)
+            out0 = torch.randn(cols, device="cuda", generator=g) * 100
+            ordered = hip.colsum(a, out0.clone(), b=b)
+            _flag(False)
+            try:
+                atomic = hip.colsum(a, out0.clone(), b=b)
+            finally:
+                _flag(True)
+            assert torch.equal(atomic, ordered), (rows, cols)
+            prod = a.double() if b is None else a.double() * b.double()
+            assert float(((ordered.double() - out0.double() - prod.sum(0)).abs() - 2e-5 * (out0.double().abs() + prod.abs().sum(0))).max()) <= 0.0
 
 
 def test_gather_maxpool_backward_equals_the_atomic_kernel_on_ties(det):

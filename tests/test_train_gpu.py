@@ -170,6 +170,35 @@ def test_strided_batched_gemm_every_staging_mode(M, N, K, a_layout, b_layout):
         assert float((got - want).abs().max()) < 1e-4 * float(want.abs().max())
 
 
+def test_fp32_row_ops_vector_and_scalar_paths_agree_bitwise():
+    """The fp32 act / SwiGLU entry points take 16-byte accesses (8 elements per thread) when every base is 16-byte aligned -- and for
+    SwiGLU H % 8 == 0 -- and one element per thread otherwise (csrc/k_train.hip, one kernel template for both).  The same values at a
+    one-element offset into a larger buffer (an unaligned base) give the same bits; H = 12 takes the scalar path at any alignment."""
+    from mst import hip
+    g = torch.Generator().manual_seed(31)
+
+    def shifted(t):                                     # t's values behind one spare element: base 4 bytes off a 16-byte boundary
+        buf = torch.cat([torch.zeros(1), t.reshape(-1)]).cuda()
+        view = buf[1:].view(t.shape)
+        assert view.data_ptr() % 16 == 4
+        return view
+
+    for n in (5, 8, 1543):
+        h, dy = torch.randn(n, generator=g) * 3, torch.randn(n, generator=g)
+        assert h.cuda().data_ptr() % 16 == 0
+        for kind in (0, 1):
+            assert torch.equal(hip.act_fwd(h.cuda(), kind), hip.act_fwd(shifted(h), kind))
+            assert torch.equal(hip.act_bwd(h.cuda(), dy.cuda(), kind), hip.act_bwd(shifted(h), shifted(dy), kind))
+            assert torch.equal(hip.act_bwd(h.cuda(), dy.cuda(), kind), hip.act_bwd(h.cuda(), shifted(dy), kind))
+    for rows, H in ((3, 8), (5, 12), (2, 1368)):
+        x12, dh = torch.randn(rows, 2 * H, generator=g) * 3, torch.randn(rows, H, generator=g)
+        assert torch.equal(hip.swiglu_fwd(x12.cuda()), hip.swiglu_fwd(shifted(x12)))
+        assert torch.equal(hip.swiglu_bwd(x12.cuda(), dh.cuda()), hip.swiglu_bwd(shifted(x12), shifted(dh)))
+        assert torch.equal(hip.swiglu_bwd(x12.cuda(), dh.cuda()), hip.swiglu_bwd(x12.cuda(), shifted(dh)))
+        ref = torch.nn.functional.silu(x12[:, :H].double()) * x12[:, H:].double()
+        assert float((hip.swiglu_fwd(x12.cuda()).cpu().double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
+
+
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
 def test_operand_images_and_split_k_product(dt):
     """mst_cvt16 (row-major and transposed, zero-padded images) is torch's round-to-nearest cast bit for bit, and mst_gemm16_splitk's

@@ -1,4 +1,5 @@
-"""train_storage='16bit' of the DINOv2 training step (csrc/k_train16.hip, the 16-bit-output forms of csrc/k_attn16_train.hip) and the
+"""train_storage='16bit' of the DINOv2 training step (csrc/k_train16.hip, the 16-bit instantiations of the row kernels of csrc/k_train.hip and csrc/k_colsum.hip,
+the 16-bit-output forms of csrc/k_attn16_train.hip) and the
 autocast rule of train_precision: every new entry point against the existing fp32 entry points on the upcast inputs and against fp64
 torch, the step against the fp32 step and the parent's flash step, the memory the saved state takes, determinism, autocast."""
 
