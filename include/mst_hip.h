@@ -417,7 +417,7 @@ int mst_colsum_b16_ordered(const float* a, int64_t a_stride, const void* b, int 
 int mst_transpose16(const void* x, int dtype, int64_t ldx, int64_t rows, int cols, void* out, int64_t ldo, int64_t rows_pad,
                     mst_stream_t stream);
 
-/* 16-bit storage mode of the ResNet training step (mst/train_resnet.py, train_storage='16bit'; csrc/k_bn16.hip): the convolution output z
+/* 16-bit storage mode of the ResNet training step (mst/train_resnet.py, train_storage='16bit'; csrc/k_bn.hip): the convolution output z
  * and the unit's output y of a convolution + BatchNorm2d (+ residual, ReLU) unit live in T = dtype (MST_BF16 / MST_F16), as the reference's
  * autocast keeps them; statistics, gradients and every sum are fp32 and all arithmetic is fp32 on the upcast values.  Activations are
  * [rows, C] NHWC.  C must be a multiple of 8 and EVERY pointer 16-byte aligned; anything else, another dtype or a short workspace returns

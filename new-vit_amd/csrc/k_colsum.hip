@@ -1,18 +1,20 @@
 // Column reductions of the training steps: out[c] += sum_r f(a[r][c], b[r][c]) over [rows, cols] -- the bias, LayerScale and BatchNorm
-// sums.  ONE kernel template serves the atomic and the fixed-order (torch.use_deterministic_algorithms) entry points and the fp32 and
-// 16-bit factors b, so every form walks the rows in the same order and returns the same bits where the forms can meet
-// (mst_colsum_b16_ordered = mst_colsum_ordered on the upcast factor; one row block: atomic = ordered).
+// sums.  ONE kernel template serves the atomic and the fixed-order (torch.use_deterministic_algorithms) entry points, the fp32 and 16-bit
+// factors b and the fp32 and 16-bit BatchNorm inputs a, so every form walks the rows in the same order and returns the same bits where the
+// forms can meet (mst_colsum_b16_ordered = mst_colsum_ordered on the upcast factor; one row block: atomic = ordered; at most one row per
+// thread row: the sums of a 16-bit z = those of the upcast z).
 //   pass 1   workgroup (rb, cb) owns rows [rb*rpb, (rb+1)*rpb) x 64 columns; thread row ty runs down rows r0 + ty + TY k in sequence, the TY
 //            partial sums meet in LDS in ascending ty.  ATOMIC: one atomicAdd per column per workgroup.  SLAB: one plain store per column
 //            into slab[rb] -- with one row block, out += instead.
 //   pass 2   (SLAB, slab_reduce) every column sums slab[0..nrb) -- 16 row phases, each in ascending rb, then ascending phase -- and adds
 //            the total to the output: an order that is a pure function of the shape arguments.
-//   plan     the row-block size depends on (rows, cols) only: about 2,048 workgroups, at least 64 rows each.
+//   plan     the row-block size depends on (rows, cols) and the thread-row count only: about 2,048 workgroups, at least 64 rows each, a
+//            multiple of 16 rows (fp32 a) or of 32 (16-bit a: CW = 8, so TY = 32).
 #include "mst_common.h"
 
 namespace {
 
-enum { OP_SUM = 0, OP_SQDEV = 1, OP_BN_BWD = 2 };
+enum { OP_SUM = COL_SUM, OP_SQDEV = COL_SQDEV, OP_BN_BWD = COL_BN_BWD };
 enum { ATOMIC = 0, SLAB = 1 };
 
 __device__ __forceinline__ void load4(const float* p, float v[4]) {
@@ -29,18 +31,21 @@ __device__ __forceinline__ void load4(const T* p, float v[4]) {
 
 // OP_SUM:    acc0 = sum_r a[r][c] * (b ? b[r][c] : 1)
 // OP_SQDEV:  acc0 = sum_r (a[r][c] - m[c])^2
-// OP_BN_BWD: acc0 = sum_r b[r][c] (a[r][c] - m[c]) rs[c]  (d gamma; a = z, b = dy),  acc1 = sum_r b[r][c]  (d beta)
-// A 256-thread block: 16 threads x 4 columns across and 16 thread rows down the chunk (VEC: 16-byte loads of a, 16 or 8 bytes of b), or
-// -- the scalar ATOMIC form -- 64 threads x 1 column and 4 thread rows.
+// OP_BN_BWD: acc0 = sum_r g (a[r][c] - m[c]) rs[c]  (d gamma; a = z),  acc1 = sum_r g  (d beta);  g = b[r][c] (= dy), times the ReLU mask
+//            (y[r][c] > 0 ? 1 : 0) when a is 16-bit and y is given
+// A 256-thread block: TX = 64 / CW threads x CW columns across and TY = 256 / TX thread rows down the chunk.  CW = 4 (VEC: 16-byte loads of
+// the fp32 a, 16 or 8 bytes of b; the scalar SLAB form: four guarded loads), CW = 1 (the scalar ATOMIC form) or CW = 8 (a 16-bit a: ONE
+// 16-byte load of a and of y, two of the fp32 b and of the per-column vectors; cols % 8 == 0).
 // Output j of row block rb.  ATOMIC: o_j[c] by atomicAdd.  SLAB: o_j[rb * ostride + c] (= the slab), or o_j[c] += when `direct`.
 // Argument order: what the atomic column sum reads comes first and fills one 64-byte line of the kernel-argument segment.  Its
 // workgroups live for four loop iterations at the step's shapes, and a second line to fetch showed as +0.1 .. 0.4 us per launch.
-template <int OP, typename BT, bool VEC, int OUT>
-__global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ a, int64_t as, const BT* __restrict__ b, int64_t bs, int64_t rows,
+template <int OP, typename AT, typename BT, int CW, bool VEC, int OUT>
+__global__ __launch_bounds__(256) void colreduce_kernel(const AT* __restrict__ a, int64_t as, const BT* __restrict__ b, int64_t bs, int64_t rows,
                                                         int64_t rpb, float* o0, int cols, int cblocks, const float* __restrict__ m,
-                                                        const float* __restrict__ rs, float* o1, int64_t ostride, int direct) {
+                                                        const float* __restrict__ rs, float* o1, int64_t ostride, int direct,
+                                                        const AT* __restrict__ y) {
     constexpr int NA = OP == OP_BN_BWD ? 2 : 1;
-    constexpr int CW = (VEC || OUT == SLAB) ? 4 : 1, TX = 64 / CW, TY = 256 / TX;
+    constexpr int TX = 64 / CW, TY = 256 / TX;
     __shared__ float red[NA][TY][64 + 4];
     const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
     // ATOMIC: row blocks on gridDim.x (2^31 - 1 blocks), column blocks on gridDim.y: the stem's BatchNorm sums of a 2 x 128 x 512^2 ResNet
@@ -54,14 +59,39 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < CW; ++e) {
         acc[0][e] = acc[NA - 1][e] = 0.f;
-        const bool in = c0 + e < cols;
-        mc[e] = (OP != OP_SUM && in) ? m[c0 + e] : 0.f;
-        rc[e] = (OP == OP_BN_BWD && in) ? rs[c0 + e] : 0.f;
+        if constexpr (CW == 8) {
+            mc[e] = rc[e] = 0.f;
+        } else {
+            const bool in = c0 + e < cols;
+            mc[e] = (OP != OP_SUM && in) ? m[c0 + e] : 0.f;
+            rc[e] = (OP == OP_BN_BWD && in) ? rs[c0 + e] : 0.f;
+        }
     }
     if (c0 < cols) {
+        if constexpr (CW == 8) {
+            if (OP != OP_SUM) load8(m + c0, mc);
+            if (OP == OP_BN_BWD) load8(rs + c0, rc);
+        }
+        constexpr int UNROLL = CW == 8 ? 2 : 1;                          // CW = 8: two rows' 16-byte loads in flight; 1: the loop as written
+#pragma unroll UNROLL
         for (int64_t r = r0 + ty; r < r1; r += TY) {
             float av[CW], bv[CW];
-            if constexpr (VEC) {
+            if constexpr (CW == 8) {
+                const int64_t off = r * as + c0;                         // a, b and y share their row stride
+                load8(a + off, av);
+                if constexpr (OP == OP_BN_BWD) {
+                    load8(b + off, bv);
+                    if (y) {
+                        float yv[CW];
+                        load8(y + off, yv);
+#pragma unroll
+                        for (int e = 0; e < CW; ++e) bv[e] *= act_deriv(yv[e], 1);
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < CW; ++e) bv[e] = 1.f;
+                }
+            } else if constexpr (VEC) {
                 load4(a + r * as + c0, av);
                 if (b) load4(b + r * bs + c0, bv);
                 else bv[0] = bv[1] = bv[2] = bv[3] = 1.f;
@@ -93,7 +123,7 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
         const int j = threadIdx.x >> 6, cl = threadIdx.x & 63, cc = cb * 64 + cl;
         float t = 0.f;
 #pragma unroll
-        for (int y = 0; y < TY; ++y) t += red[j][y][cl];
+        for (int q = 0; q < TY; ++q) t += red[j][q][cl];
         if (cc < cols) {
             if constexpr (OUT == ATOMIC) {
                 atomicAdd((j ? o1 : o0) + cc, t);
@@ -128,22 +158,30 @@ __global__ __launch_bounds__(1024) void slab_reduce_kernel(const float* __restri
     }
 }
 
-// the row blocks: enough workgroups to fill the chip (about 2,048), chunks of at least 64 rows so that the atomics / slabs stay few
-void colsum_plan(int64_t rows, int cols, int64_t& rpb, int64_t& rblocks) {
+}  // namespace
+
+// the row blocks: enough workgroups to fill the chip (about 2,048), chunks of at least 64 rows so that the atomics / slabs stay few;
+// whole sweeps of the `ty` thread rows
+void colsum_plan(int64_t rows, int cols, int ty, int64_t& rpb, int64_t& rblocks) {
     const int64_t cblocks = (cols + 63) / 64;
     rpb = (rows * cblocks + 2047) / 2048;
-    rpb = rpb < 64 ? 64 : (rpb + 15) / 16 * 16;
+    rpb = rpb < 64 ? 64 : (rpb + ty - 1) / ty * ty;
     rblocks = (rows + rpb - 1) / rpb;
 }
 
-// Every entry point's argument checks; returns the plan and whether the 16-byte path applies.  A 16-bit b has no scalar path.
-int colreduce_args(const char* what, const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, bool ordered,
+namespace {
+
+// Every entry point's argument checks; returns the plan and whether the 16-byte path applies.  A 16-bit a or b has no scalar path.
+int colreduce_args(const char* what, const void* a, int adt, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, bool ordered,
                    int outputs, const void* ws, size_t ws_bytes, int64_t& rpb, int64_t& rblocks, bool& vec) {
     MST_CHECK_ARG(rows > 0 && cols > 0, "%s: rows=%lld cols=%d out of range", what, (long long)rows, cols);
     vec = cols % 4 == 0 && as % 4 == 0 && aligned(a, 16) && (!b || (bs % 4 == 0 && aligned(b, dt == MST_F32 ? 16 : 8)));
     MST_CHECK_ARG(dt == MST_F32 || (vec && as >= cols && bs >= cols),
                   "%s: cols=%d and the row strides must be multiples of 4 (strides >= cols), a 16-byte and b 8-byte aligned", what, cols);
-    colsum_plan(rows, cols, rpb, rblocks);
+    MST_CHECK_ARG(adt == MST_F32 || (ordered && dt == MST_F32 && vec && cols % 8 == 0 && as % 8 == 0 && (!b || bs == as)),
+                  "%s: a 16-bit input takes the fixed order, cols=%d and ONE row stride that are multiples of 8, 16-byte aligned operands", what, cols);
+    const int ty = adt == MST_F32 ? 16 : 32;
+    colsum_plan(rows, cols, ty, rpb, rblocks);
     const int64_t cblocks = (cols + 63) / 64;
     if (!ordered) {
         MST_CHECK_ARG(cblocks <= 65535, "%s: cols=%d out of range", what, cols);
@@ -151,33 +189,38 @@ int colreduce_args(const char* what, const float* a, int64_t as, const void* b, 
         return MST_OK;
     }
     MST_CHECK_ARG(rblocks * cblocks < (1ll << 31), "%s: rows=%lld cols=%d out of range", what, (long long)rows, cols);
-    const size_t need = colsum_ordered_workspace_bytes(rows, cols, outputs);
+    const size_t need = colsum_ordered_workspace_bytes(rows, cols, outputs, ty);
     MST_CHECK_ARG(ws_bytes >= need && (need == 0 || ws), "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
     return MST_OK;
 }
 
-// b: fp32, or (OP_SUM) bf16 / fp16 as `dt` says.  ordered: the SLAB form with its workspace; otherwise (OP_SUM only) the ATOMIC form.
+// a: fp32, or (the BatchNorm sums, ordered only) bf16 / fp16 as `adt` says, with y (nullable) the mask operand of OP_BN_BWD.  b: fp32, or
+// (OP_SUM) bf16 / fp16 as `dt` says.  ordered: the SLAB form with its workspace; otherwise the ATOMIC form.
 template <int OP>
-int colreduce_launch(const char* what, const float* a, int64_t as, const void* b, int dt, int64_t bs, const float* m, const float* rs,
-                     int64_t rows, int cols, float* out0, float* out1, bool ordered, void* ws, size_t ws_bytes, hipStream_t s) {
+int colreduce_launch(const char* what, const void* a, int adt, int64_t as, const void* b, int dt, int64_t bs, const float* m, const float* rs,
+                     const void* y, int64_t rows, int cols, float* out0, float* out1, bool ordered, void* ws, size_t ws_bytes, hipStream_t s) {
     constexpr int NA = OP == OP_BN_BWD ? 2 : 1;
     int64_t rpb, rblocks;
     bool vec;
-    if (int rc = colreduce_args(what, a, as, b, dt, bs, rows, cols, ordered, NA, ws, ws_bytes, rpb, rblocks, vec)) return rc;
+    if (int rc = colreduce_args(what, a, adt, as, b, dt, bs, rows, cols, ordered, NA, ws, ws_bytes, rpb, rblocks, vec)) return rc;
+    MST_CHECK_ARG(adt == MST_F32 || (aligned(y, 16) && aligned(m, 16) && aligned(rs, 16)), "%s: every pointer must be 16-byte aligned", what);
     const int cblocks = (cols + 63) / 64;
     const bool direct = rblocks == 1;
     float* slab = (float*)ws;
     float* o0 = (!ordered || direct) ? out0 : slab;
     float* o1 = (!ordered || direct) ? out1 : slab + cols;
     const dim3 grid = ordered ? dim3((unsigned)(rblocks * cblocks)) : dim3((unsigned)rblocks, cblocks);
-#define COLREDUCE_AS(BT, VEC, OUT) \
-    colreduce_kernel<OP, BT, VEC, OUT><<<grid, dim3(256), 0, s>>>(a, as, (const BT*)b, bs, rows, rpb, o0, cols, cblocks, m, rs, o1, (int64_t)NA * cols, direct)
-#define COLREDUCE(BT, VEC)                                       \
-    do {                                                         \
-        if (ordered) COLREDUCE_AS(BT, VEC, SLAB);                \
-        else if constexpr (OP == OP_SUM) COLREDUCE_AS(BT, VEC, ATOMIC); \
+#define COLREDUCE_AS(AT, BT, CW, VEC, OUT)                                                                                                  \
+    colreduce_kernel<OP, AT, BT, CW, VEC, OUT><<<grid, dim3(256), 0, s>>>((const AT*)a, as, (const BT*)b, bs, rows, rpb, o0, cols, cblocks, m, rs, \
+                                                                          o1, (int64_t)NA * cols, direct, (const AT*)y)
+#define COLREDUCE(BT, VEC)                                        \
+    do {                                                          \
+        if (ordered) COLREDUCE_AS(float, BT, 4, VEC, SLAB);       \
+        else COLREDUCE_AS(float, BT, (VEC ? 4 : 1), VEC, ATOMIC); \
     } while (0)
-    if (dt == MST_F32) {
+    if (adt == MST_BF16) COLREDUCE_AS(bf16_t, float, 8, true, SLAB);
+    else if (adt == MST_F16) COLREDUCE_AS(f16_t, float, 8, true, SLAB);
+    else if (dt == MST_F32) {
         if (vec) COLREDUCE(float, true);
         else COLREDUCE(float, false);
     } else if constexpr (OP == OP_SUM) {
@@ -191,19 +234,23 @@ int colreduce_launch(const char* what, const float* a, int64_t as, const void* b
     return launch_slab_reduce(slab, rblocks, (int64_t)NA * cols, cols, out0, out1, s);
 }
 
+int colsum_b(const char* what, const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out, bool ordered,
+             void* ws, size_t ws_bytes, hipStream_t s) {
+    return colreduce_launch<OP_SUM>(what, a, MST_F32, as, b, dt, bs, nullptr, nullptr, nullptr, rows, cols, out, nullptr, ordered, ws, ws_bytes, s);
+}
 int colsum_b16(const char* what, const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out,
                bool ordered, void* ws, size_t ws_bytes, hipStream_t s) {
     MST_CHECK_ARG(dt == MST_BF16 || dt == MST_F16, "%s: dtype %d (bf16 / f16)", what, dt);
-    return colreduce_launch<OP_SUM>(what, a, as, b, dt, bs, nullptr, nullptr, rows, cols, out, nullptr, ordered, ws, ws_bytes, s);
+    return colsum_b(what, a, as, b, dt, bs, rows, cols, out, ordered, ws, ws_bytes, s);
 }
 
 }  // namespace
 
-size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs) {
+size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs, int ty) {
     if (rows <= 0 || cols <= 0) return 0;
     int64_t rpb, rblocks;
-    colsum_plan(rows, cols, rpb, rblocks);
-    return rblocks > 1 ? (sizeof(float) * (size_t)rblocks * outputs * cols + 255) / 256 * 256 : 0;
+    colsum_plan(rows, cols, ty, rpb, rblocks);
+    return rblocks > 1 ? round256(sizeof(float) * (size_t)rblocks * outputs * cols) : 0;
 }
 
 int launch_slab_reduce(const float* slab, int64_t nrb, int64_t width, int64_t split, float* o0, float* o1, hipStream_t s) {
@@ -214,12 +261,12 @@ int launch_slab_reduce(const float* slab, int64_t nrb, int64_t width, int64_t sp
 }
 
 int launch_colsum(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, hipStream_t s) {
-    return colreduce_launch<OP_SUM>("colsum", a, as, b, MST_F32, bs, nullptr, nullptr, rows, cols, out, nullptr, false, nullptr, 0, s);
+    return colsum_b("colsum", a, as, b, MST_F32, bs, rows, cols, out, false, nullptr, 0, s);
 }
 
 int launch_colsum_ordered(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, void* ws,
                           size_t ws_bytes, hipStream_t s) {
-    return colreduce_launch<OP_SUM>("colsum_ordered", a, as, b, MST_F32, bs, nullptr, nullptr, rows, cols, out, nullptr, true, ws, ws_bytes, s);
+    return colsum_b("colsum_ordered", a, as, b, MST_F32, bs, rows, cols, out, true, ws, ws_bytes, s);
 }
 
 int launch_colsum_b16(const float* a, int64_t as, const void* b, int dt, int64_t bs, int64_t rows, int cols, float* out, hipStream_t s) {
@@ -231,11 +278,14 @@ int launch_colsum_b16_ordered(const float* a, int64_t as, const void* b, int dt,
     return colsum_b16("colsum_b16_ordered", a, as, b, dt, bs, rows, cols, out, true, ws, ws_bytes, s);
 }
 
-int launch_colsqdev_ordered(const float* z, const float* mean, int64_t rows, int C, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-    return colreduce_launch<OP_SQDEV>("colsqdev_ordered", z, C, nullptr, MST_F32, 0, mean, nullptr, rows, C, out, nullptr, true, ws, ws_bytes, s);
-}
-
-int launch_bn_bwd_reduce_ordered(const float* z, const float* mean, const float* rstd, const float* dy, int64_t rows, int C, float* dgamma,
-                                 float* dbeta, void* ws, size_t ws_bytes, hipStream_t s) {
-    return colreduce_launch<OP_BN_BWD>("bn_bwd_reduce_ordered", z, C, dy, MST_F32, C, mean, rstd, rows, C, dgamma, dbeta, true, ws, ws_bytes, s);
+int launch_bn_reduce(int op, const void* z, int dt, const void* y, const float* dy, const float* mean, const float* rstd, int64_t rows, int C,
+                     float* out0, float* out1, bool ordered, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (op == COL_SUM)
+        return colreduce_launch<OP_SUM>(ordered ? "colsum_ordered" : "colsum", z, dt, C, nullptr, MST_F32, 0, nullptr, nullptr, nullptr, rows, C,
+                                        out0, nullptr, ordered, ws, ws_bytes, s);
+    if (op == COL_SQDEV)
+        return colreduce_launch<OP_SQDEV>(ordered ? "colsqdev_ordered" : "colsqdev", z, dt, C, nullptr, MST_F32, 0, mean, nullptr, nullptr, rows, C,
+                                          out0, nullptr, ordered, ws, ws_bytes, s);
+    return colreduce_launch<OP_BN_BWD>(ordered ? "bn_bwd_reduce_ordered" : "bn_bwd_reduce", z, dt, C, dy, MST_F32, C, mean, rstd, y, rows, C, out0,
+                                       out1, ordered, ws, ws_bytes, s);
 }

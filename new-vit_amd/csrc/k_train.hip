@@ -168,16 +168,6 @@ __global__ void rope_rows_kernel(float* __restrict__ qkv, int64_t rows, int L, i
 // for V = 8 elements per thread in 16-byte accesses or V = 1.  The arithmetic is fp32 and the same expression in every instantiation, so
 // the 16-bit forms return T(the fp32 form on the upcast input) and the V = 8 and V = 1 forms return the same bits.  A 16-bit store goes
 // through f32_rounded (mst_common.h): the conversion must round the fp32 result, not fuse with the product before it.
-template <int V, typename T>
-__device__ __forceinline__ void loadv(const T* p, float v[V]) {
-    if constexpr (V == 8) load8(p, v);
-    else v[0] = to_f32(p[0]);
-}
-template <int V, typename T>
-__device__ __forceinline__ void storev(T* p, const float v[V]) {
-    if constexpr (V == 8) store8(p, v);
-    else p[0] = (T)v[0];
-}
 
 // y = act(h): kind 0 GELU (erf form), 1 ReLU (the training forward keeps the pre-activation h for the backward).
 template <int V, typename T>

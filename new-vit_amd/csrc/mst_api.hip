@@ -360,37 +360,18 @@ int mst_im2col_nhwc16(const float* x, int n, int H, int W, int C, int kh, int kw
 }
 int mst_maxpool_nhwc16(const void* x, int dtype, int n, int H, int W, int C, void* y, mst_stream_t stream) {
     MST_CHECK_ARG(x && y && n > 0 && H > 0 && W > 0 && C > 0, "maxpool16: bad arguments");
-    return launch_maxpool_nhwc16(x, dtype, n, H, W, C, y, (hipStream_t)stream);
+    return launch_maxpool_nhwc(x, dtype, n, H, W, C, y, (hipStream_t)stream);
 }
 int mst_cvt32(const void* x, int dtype, int64_t n, float* out, mst_stream_t stream) { return launch_cvt32(x, dtype, n, out, (hipStream_t)stream); }
 int mst_maxpool_nhwc(const float* x, int n, int H, int W, int C, float* y, mst_stream_t stream) {
     MST_CHECK_ARG(x && y && n > 0 && H > 0 && W > 0 && C > 0, "maxpool_nhwc: bad arguments");
-    return launch_maxpool_nhwc(x, n, H, W, C, y, (hipStream_t)stream);
+    return launch_maxpool_nhwc(x, MST_F32, n, H, W, C, y, (hipStream_t)stream);
 }
 int mst_avgpool_nhwc(const float* x, int n, int HW, int C, float* y, mst_stream_t stream) {
     MST_CHECK_ARG(x && y && n > 0 && HW > 0 && C > 0, "avgpool_nhwc: bad arguments");
-    return launch_avgpool_nhwc(x, n, HW, C, y, (hipStream_t)stream);
+    return launch_avgpool_nhwc(x, MST_F32, n, HW, C, y, (hipStream_t)stream);
 }
 
-int mst_batchnorm_train(const float* z, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
-                        const float* residual, int relu, float* y, float* mean, float* rstd, float* running_mean,
-                        float* running_var, float* scratch, mst_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    MST_CHECK_ARG(z && gamma && beta && y && mean && rstd && scratch && rows > 0 && C > 0, "batchnorm_train: bad arguments");
-    if (hipMemsetAsync(scratch, 0, sizeof(float) * C, s) != hipSuccess) { mst_set_error("batchnorm_train: memset failed"); return MST_ELAUNCH; }
-    int rc = launch_colsum(z, C, nullptr, 0, rows, C, scratch, s);
-    if (rc) return rc;
-    if ((rc = launch_bn_finalize(0, scratch, rows, C, eps, momentum, mean, rstd, nullptr, nullptr, s))) return rc;
-    if (hipMemsetAsync(scratch, 0, sizeof(float) * C, s) != hipSuccess) { mst_set_error("batchnorm_train: memset failed"); return MST_ELAUNCH; }
-    if ((rc = launch_colsqdev(z, mean, rows, C, scratch, s))) return rc;
-    if ((rc = launch_bn_finalize(1, scratch, rows, C, eps, momentum, mean, rstd, running_mean, running_var, s))) return rc;
-    return launch_bn_apply(z, mean, rstd, gamma, beta, residual, relu, rows, C, y, s);
-}
-int mst_batchnorm_bwd(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, int64_t rows, int C,
-                      float* dgamma, float* dbeta, float* dz, mst_stream_t stream) {
-    MST_CHECK_ARG(z && mean && rstd && gamma && dy && dgamma && dbeta && dz && rows > 0 && C > 0, "batchnorm_bwd: bad arguments");
-    return launch_bn_bwd(z, mean, rstd, gamma, dy, rows, C, dgamma, dbeta, dz, (hipStream_t)stream);
-}
 int mst_col2im_nhwc(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
                     mst_stream_t stream) {
     MST_CHECK_ARG(dcol && dx && n > 0 && H > 0 && W > 0 && C > 0, "col2im_nhwc: bad arguments");
@@ -401,10 +382,7 @@ int mst_maxpool_bwd_nhwc(const float* x, const float* dy, int n, int H, int W, i
     return launch_maxpool_bwd_nhwc(x, dy, n, H, W, C, dx, (hipStream_t)stream);
 }
 // ---- fixed-order forms (torch.use_deterministic_algorithms): no floating-point atomics, bit-reproducible for fixed shapes -----------
-static int ws_short(const char* what, size_t have, size_t need) {
-    mst_set_error("%s: workspace of %zu bytes, %zu needed", what, have, need);
-    return MST_EINVAL;
-}
+// (the BatchNorm and pooling entry points, of every mode, are in k_bn.hip)
 size_t mst_colsum_ordered_workspace_bytes(int64_t rows, int cols) { return colsum_ordered_workspace_bytes(rows, cols, 1); }
 int mst_colsum_ordered(const float* a, int64_t a_stride, const float* b, int64_t b_stride, int64_t rows, int cols, float* out,
                        void* workspace, size_t workspace_bytes, mst_stream_t stream) {
@@ -419,38 +397,6 @@ int mst_layernorm_bwd_ordered(const float* x, int64_t x_stride, const float* gam
     return launch_layernorm_bwd_ordered(x, x_stride, gamma, dy, dy_stride, dres, dres_stride, dx, dx_stride, dgamma, dbeta, rows, cols, eps,
                                         workspace, workspace_bytes, (hipStream_t)stream);
 }
-static size_t bn_acc_bytes(int C) { return ((size_t)C * sizeof(float) + 255) / 256 * 256; }
-size_t mst_batchnorm_train_ordered_workspace_bytes(int64_t rows, int C) {
-    return rows > 0 && C > 0 ? bn_acc_bytes(C) + colsum_ordered_workspace_bytes(rows, C, 1) : 0;
-}
-int mst_batchnorm_train_ordered(const float* z, int64_t rows, int C, const float* gamma, const float* beta, float eps, float momentum,
-                                const float* residual, int relu, float* y, float* mean, float* rstd, float* running_mean,
-                                float* running_var, void* workspace, size_t workspace_bytes, mst_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    MST_CHECK_ARG(z && gamma && beta && y && mean && rstd && workspace && rows > 0 && C > 0, "batchnorm_train_ordered: bad arguments");
-    const size_t need = mst_batchnorm_train_ordered_workspace_bytes(rows, C);
-    if (workspace_bytes < need) return ws_short("batchnorm_train_ordered", workspace_bytes, need);
-    float* acc = (float*)workspace;                                     // C floats, then the slab of the column sums
-    void* slab = (char*)workspace + bn_acc_bytes(C);
-    const size_t slab_bytes = workspace_bytes - bn_acc_bytes(C);
-    if (hipMemsetAsync(acc, 0, sizeof(float) * C, s) != hipSuccess) { mst_set_error("batchnorm_train_ordered: memset failed"); return MST_ELAUNCH; }
-    int rc = launch_colsum_ordered(z, C, nullptr, 0, rows, C, acc, slab, slab_bytes, s);
-    if (rc) return rc;
-    if ((rc = launch_bn_finalize(0, acc, rows, C, eps, momentum, mean, rstd, nullptr, nullptr, s))) return rc;
-    if (hipMemsetAsync(acc, 0, sizeof(float) * C, s) != hipSuccess) { mst_set_error("batchnorm_train_ordered: memset failed"); return MST_ELAUNCH; }
-    if ((rc = launch_colsqdev_ordered(z, mean, rows, C, acc, slab, slab_bytes, s))) return rc;
-    if ((rc = launch_bn_finalize(1, acc, rows, C, eps, momentum, mean, rstd, running_mean, running_var, s))) return rc;
-    return launch_bn_apply(z, mean, rstd, gamma, beta, residual, relu, rows, C, y, s);
-}
-size_t mst_batchnorm_bwd_ordered_workspace_bytes(int64_t rows, int C) { return colsum_ordered_workspace_bytes(rows, C, 2); }
-int mst_batchnorm_bwd_ordered(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, int64_t rows, int C,
-                              float* dgamma, float* dbeta, float* dz, void* workspace, size_t workspace_bytes, mst_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    MST_CHECK_ARG(z && mean && rstd && gamma && dy && dgamma && dbeta && dz && rows > 0 && C > 0, "batchnorm_bwd_ordered: bad arguments");
-    int rc = launch_bn_bwd_reduce_ordered(z, mean, rstd, dy, rows, C, dgamma, dbeta, workspace, workspace_bytes, s);
-    if (rc) return rc;
-    return launch_bn_bwd_apply(z, mean, rstd, gamma, dy, dgamma, dbeta, rows, C, dz, s);
-}
 int mst_col2im_nhwc_gather(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
                            mst_stream_t stream) {
     MST_CHECK_ARG(dcol && dx && n > 0 && H > 0 && W > 0 && C > 0, "col2im_nhwc_gather: bad arguments");
@@ -460,7 +406,7 @@ size_t mst_maxpool_bwd_nhwc_gather_workspace_bytes(int n, int H, int W, int C) {
 int mst_maxpool_bwd_nhwc_gather(const float* x, const float* dy, int n, int H, int W, int C, float* dx, void* workspace, size_t workspace_bytes,
                                 mst_stream_t stream) {
     MST_CHECK_ARG(x && dy && dx && n > 0 && H > 0 && W > 0 && C > 0, "maxpool_bwd_nhwc_gather: bad arguments");
-    return launch_maxpool_bwd_gather(x, dy, n, H, W, C, dx, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_maxpool_bwd_gather("maxpool_bwd_gather", x, MST_F32, dy, n, H, W, C, dx, workspace, workspace_bytes, (hipStream_t)stream);
 }
 size_t mst_pos_embed_interp_bwd_ordered_workspace_bytes(int M, int E, int gh, int gw) { return pos_interp_bwd_ordered_workspace_bytes(M, E, gh, gw); }
 int mst_pos_embed_interp_bwd_ordered(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, void* workspace,

@@ -77,6 +77,18 @@ __device__ __forceinline__ float act_deriv(float v, int kind) {
     if (kind == 0) return 0.5f * (1.0f + erff(v * 0.70710678118654752440f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
     return v > 0.f ? 1.f : 0.f;
 }
+// BatchNorm with batch statistics (k_bn.hip), each expression once and with every rounding spelled out (no contraction left to the
+// compiler), so that every instantiation of the apply kernels -- fp32 / 16-bit storage, 8 or 1 channels per thread -- returns the same bits
+// on the same values.  y = gamma (z - mean) rstd + beta;  dz = gamma rstd (dy - d beta / rows - xhat d gamma / rows) with inv = 1 / rows
+// (d beta inv as a rounded product: it does not depend on the row, and a compiler that hoists it out of a row loop must not change the bits).
+__device__ __forceinline__ float bn_fwd_value(float z, float mean, float rstd, float gamma, float beta) {
+    return fmaf(__fmul_rn(gamma, __fsub_rn(z, mean)), rstd, beta);
+}
+__device__ __forceinline__ float bn_bwd_value(float z, float mean, float rstd, float gamma, float dy, float dgamma, float dbeta, float inv) {
+    const float xh = __fmul_rn(__fsub_rn(z, mean), rstd);
+    const float t = __fsub_rn(dy, __fmul_rn(dbeta, inv));
+    return __fmul_rn(__fmul_rn(gamma, rstd), fmaf(-__fmul_rn(xh, dgamma), inv, t));
+}
 
 // eight consecutive elements as fp32, in 16-byte accesses (two for fp32).  The 16-bit store rounds to nearest even what it is given: a
 // kernel whose output must be T(its fp32 result) passes the values through f32_rounded first.
@@ -104,6 +116,17 @@ __device__ __forceinline__ void store8(float* p, const float v[8]) {
     for (int e = 0; e < 4; ++e) { a[e] = v[e]; b[e] = v[4 + e]; }
     *reinterpret_cast<f32x4*>(p) = a;
     *reinterpret_cast<f32x4*>(p + 4) = b;
+}
+// V = 8 elements as above, or one
+template <int V, typename T>
+__device__ __forceinline__ void loadv(const T* p, float v[V]) {
+    if constexpr (V == 8) load8(p, v);
+    else v[0] = to_f32(p[0]);
+}
+template <int V, typename T>
+__device__ __forceinline__ void storev(T* p, const float v[V]) {
+    if constexpr (V == 8) store8(p, v);
+    else p[0] = (T)v[0];
 }
 
 // cubic convolution coefficients of the four taps around fraction x, A = -0.75 (what F.interpolate(mode='bicubic') uses)
@@ -214,6 +237,12 @@ void mst_set_error(const char* fmt, ...);
     } while (0)
 int mst_check_launch(const char* what);
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline size_t round256(size_t b) { return (b + 255) / 256 * 256; }
+// workgroups of 256 threads striding over n items: 16,384 at most
+inline unsigned grid256(int64_t n) {
+    const int64_t g = (n + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
+}
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): the attribute is per device, and a process may drive
 // several GPUs.  Thread-safe; `slot` is a static per-kernel token owned by the call site.
 struct mst_lds_once { unsigned long long done_mask = 0; };
@@ -342,7 +371,6 @@ int launch_colsum_b16_ordered(const float* a, int64_t as, const void* b, int dt,
 int launch_transpose16(const void* x, int dt, int64_t ldx, int64_t rows, int cols, void* out, int64_t ldo, int64_t rows_pad, hipStream_t s);
 int launch_rope_rows(float* qkv, int64_t rows, int L, int heads, int hd, const float* freqs, float sign, hipStream_t s);
 int launch_im2col_nhwc16(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, void* col, int dt, hipStream_t s);
-int launch_maxpool_nhwc16(const void* x, int dt, int n, int H, int W, int C, void* y, hipStream_t s);
 int launch_cvt32(const void* x, int dt, int64_t n, float* out, hipStream_t s);
 int launch_conv_gemm16(const void* x, int dt, int n, int H, int W, int Cin, int kh, int kw, int stride, int pad, const void* Wg, const float* bias,
                        void* out, int cdt, int Cout, int epi, hipStream_t s);
@@ -413,17 +441,11 @@ int launch_patch_embed_dgrad(const float* dx, int tok, int first, const float* w
 // convolutional backbone (k_conv.hip)
 int launch_im2col_nhwc(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* col,
                        hipStream_t s);
-int launch_maxpool_nhwc(const float* x, int n, int H, int W, int C, float* y, hipStream_t s);
-int launch_avgpool_nhwc(const float* x, int n, int HW, int C, float* y, hipStream_t s);
-int launch_colsqdev(const float* z, const float* mean, int64_t rows, int C, float* out, hipStream_t s);
-int launch_bn_finalize(int stage, const float* acc, int64_t rows, int C, float eps, float momentum, float* mean, float* rstd,
-                       float* running_mean, float* running_var, hipStream_t s);
-int launch_bn_apply(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* res,
-                    int relu, int64_t rows, int C, float* y, hipStream_t s);
-int launch_bn_bwd(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, int64_t rows, int C,
-                  float* dgamma, float* dbeta, float* dz, hipStream_t s);
 int launch_col2im_nhwc(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
                        hipStream_t s);
+// pooling (k_bn.hip, beside the BatchNorm entry points); x of type dt
+int launch_maxpool_nhwc(const void* x, int dt, int n, int H, int W, int C, void* y, hipStream_t s);
+int launch_avgpool_nhwc(const void* x, int dt, int n, int HW, int C, float* y, hipStream_t s);
 int launch_maxpool_bwd_nhwc(const float* x, const float* dy, int n, int H, int W, int C, float* dx, hipStream_t s);
 int launch_avgpool_bwd_nhwc(const float* dy, int n, int HW, int C, float* dx, hipStream_t s);
 int launch_gradcampp(const float* act, const float* out, int O, const float* W, int n, int HW, int C, float* cam, float* state,
@@ -434,22 +456,25 @@ int launch_pad_axis(float* v, int n0, int n1, int n2, int axis, int lo, int hi, 
 int launch_copy_block(const float* src, int sn1, int sn2, int s0, int s1, int s2, float* dst, int dn1, int dn2, int d0, int d1,
                       int d2, int c0, int c1, int c2, hipStream_t s);
 int launch_znorm(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, hipStream_t s);
-// fixed-order reductions (k_colsum.hip, k_ordered.hip, and the ordered forms in k_train.hip / k_conv.hip / k_input.hip): bit-reproducible for fixed
+// fixed-order reductions (k_colsum.hip, k_ordered.hip, and the ordered forms in k_train.hip / k_bn.hip / k_input.hip): bit-reproducible for fixed
 // shape arguments, no floating-point atomics
-size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs);
+size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs, int ty = 16);
 int launch_slab_reduce(const float* slab, int64_t nrb, int64_t width, int64_t split, float* o0, float* o1, hipStream_t s);
 int launch_colsum_ordered(const float* a, int64_t as, const float* b, int64_t bs, int64_t rows, int cols, float* out, void* ws,
                           size_t ws_bytes, hipStream_t s);
-int launch_colsqdev_ordered(const float* z, const float* mean, int64_t rows, int C, float* out, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_bn_bwd_reduce_ordered(const float* z, const float* mean, const float* rstd, const float* dy, int64_t rows, int C, float* dgamma,
-                                 float* dbeta, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_bn_bwd_apply(const float* z, const float* mean, const float* rstd, const float* gamma, const float* dy, const float* dgamma,
-                        const float* dbeta, int64_t rows, int C, float* dz, hipStream_t s);
+// the column sums of BatchNorm on z [rows, C] of type dt (k_colsum.hip): COL_SUM out0 += sum z; COL_SQDEV out0 += sum (z - mean)^2;
+// COL_BN_BWD out0 += sum g (z - mean) rstd, out1 += sum g with g = dy (y > 0 ? 1 : 0), y (of z's type, 16-bit only) nullable.  ordered: in
+// fixed order through ws; otherwise by atomics (fp32 z only).  A 16-bit z: C % 8 == 0 and 16-byte aligned operands.
+enum { COL_SUM = 0, COL_SQDEV = 1, COL_BN_BWD = 2 };
+int launch_bn_reduce(int op, const void* z, int dt, const void* y, const float* dy, const float* mean, const float* rstd, int64_t rows, int C,
+                     float* out0, float* out1, bool ordered, void* ws, size_t ws_bytes, hipStream_t s);
+// the row blocks of a column sum whose workgroup has `ty` thread rows
+void colsum_plan(int64_t rows, int cols, int ty, int64_t& rpb, int64_t& rblocks);
 int launch_col2im_gather(const float* dcol, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* dx,
                          hipStream_t s);
 size_t maxpool_bwd_gather_workspace_bytes(int n, int H, int W, int C);
-int launch_maxpool_bwd_gather(const float* x, const float* dy, int n, int H, int W, int C, float* dx, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_maxpool_bwd_from_args(const uint8_t* arg, const float* dy, int n, int H, int W, int C, float* dx, hipStream_t s);
+int launch_maxpool_bwd_gather(const char* what, const void* x, int dt, const float* dy, int n, int H, int W, int C, float* dx, void* ws,
+                              size_t ws_bytes, hipStream_t s);
 size_t pos_interp_bwd_ordered_workspace_bytes(int M, int E, int gh, int gw);
 int launch_pos_interp_bwd_ordered(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, void* ws, size_t ws_bytes,
                                   hipStream_t s);

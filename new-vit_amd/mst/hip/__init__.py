@@ -100,7 +100,7 @@ SIGNATURES = {
     "mst_colsum_b16": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp]),
     "mst_colsum_b16_ordered": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
     "mst_transpose16": (_i, [_vp, _i, _i64, _i64, _i, _vp, _i64, _i64, _vp]),
-    # 16-bit storage mode of the ResNet training step (csrc/k_bn16.hip)
+    # 16-bit storage mode of the ResNet training step (csrc/k_bn.hip)
     "mst_batchnorm_train16_workspace_bytes": (_sz, [_i64, _i]),
     "mst_batchnorm_train16": (_i, [_vp, _i, _i64, _i, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mst_batchnorm_bwd16_workspace_bytes": (_sz, [_i64, _i]),
@@ -1121,26 +1121,38 @@ def avgpool_nhwc(x: torch.Tensor) -> torch.Tensor:
 
 
 def batchnorm_train(z: torch.Tensor, bn, residual: Optional[torch.Tensor], relu: bool, momentum: float = 0.1):
-    """nn.BatchNorm2d in train mode on z [rows, C] (+ residual, ReLU): returns (y, mean, rstd); updates bn.running_* in place."""
+    """nn.BatchNorm2d in train mode on z [rows, C] (+ residual of z's type, ReLU): returns (y in z's type, mean, rstd); updates
+    bn.running_* in place.  By z's dtype: mst_batchnorm_train / mst_batchnorm_train_ordered (fp32, by the determinism flag) or
+    mst_batchnorm_train16 (bf16 / fp16: fixed summation order in both determinism modes)."""
     _dev(z, "batchnorm_train")
+    if residual is not None and (residual.dtype != z.dtype or residual.numel() != z.numel()):
+        raise ValueError(f"batchnorm_train: residual {tuple(residual.shape)} {residual.dtype} does not match z {tuple(z.shape)} {z.dtype}")
     rows, Cc = z.shape
     dev = z.device
     y = torch.empty_like(z)
     mean = torch.empty(Cc, dtype=torch.float32, device=dev)
     rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
-    if deterministic():
-        _call_ws("mst_batchnorm_train_ordered", (rows, Cc), z, ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps,
-                 momentum, ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var))
-        return y, mean, rstd
-    scratch = torch.empty(Cc, dtype=torch.float32, device=dev)
-    _check(load().mst_batchnorm_train(ptr(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum, ptr(residual),
-                                      1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var),
-                                      ptr(scratch), stream_of(z)), "mst_batchnorm_train")
+    tail = (ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps, momentum, ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd),
+            ptr(bn.running_mean), ptr(bn.running_var))
+    if z.dtype != torch.float32:
+        _call_ws("mst_batchnorm_train16", (rows, Cc), z, ptr(z), dt_of(z), rows, Cc, *tail)
+    elif deterministic():
+        _call_ws("mst_batchnorm_train_ordered", (rows, Cc), z, ptr(z), rows, Cc, *tail)
+    else:
+        scratch = torch.empty(Cc, dtype=torch.float32, device=dev)
+        _check(load().mst_batchnorm_train(ptr(z), rows, Cc, *tail, ptr(scratch), stream_of(z)), "mst_batchnorm_train")
     return y, mean, rstd
 
 
+def batchnorm_train16(z: torch.Tensor, bn, residual: Optional[torch.Tensor], relu: bool, momentum: float = 0.1):
+    """batchnorm_train on a z that must be bf16 / fp16."""
+    _is16(z, "batchnorm_train16", "z")
+    return batchnorm_train(z, bn, residual, relu, momentum)
+
+
 def batchnorm_bwd(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor):
-    """Returns (dz, dgamma, dbeta)."""
+    """fp32 z and a dy the caller has masked already (act_bwd on the saved output): returns (dz, dgamma, dbeta).  batchnorm_bwd16 is the
+    16-bit form, which takes the mask from the saved y itself."""
     rows, Cc = z.shape
     dg = torch.zeros(Cc, dtype=torch.float32, device=z.device)
     db = torch.zeros(Cc, dtype=torch.float32, device=z.device)
@@ -1152,22 +1164,6 @@ def batchnorm_bwd(z: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma
     _check(load().mst_batchnorm_bwd(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), rows, Cc, ptr(dg), ptr(db), ptr(dz),
                                     stream_of(z)), "mst_batchnorm_bwd")
     return dz, dg, db
-
-
-def batchnorm_train16(z: torch.Tensor, bn, residual: Optional[torch.Tensor], relu: bool, momentum: float = 0.1):
-    """mst_batchnorm_train16: batchnorm_train on z [rows, C] in bf16 / fp16 (+ residual of the same type, ReLU): returns (y in z's type, mean,
-    rstd); updates bn.running_* in place.  Fixed summation order in both determinism modes."""
-    _is16(z, "batchnorm_train16", "z")
-    if residual is not None and (residual.dtype != z.dtype or residual.numel() != z.numel()):
-        raise ValueError(f"batchnorm_train16: residual {tuple(residual.shape)} {residual.dtype} does not match z {tuple(z.shape)} {z.dtype}")
-    rows, Cc = z.shape
-    dev = z.device
-    y = torch.empty_like(z)
-    mean = torch.empty(Cc, dtype=torch.float32, device=dev)
-    rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
-    _call_ws("mst_batchnorm_train16", (rows, Cc), z, ptr(z), dt_of(z), rows, Cc, ptr(bn.weight.detach()), ptr(bn.bias.detach()), bn.eps,
-             momentum, ptr(residual), 1 if relu else 0, ptr(y), ptr(mean), ptr(rstd), ptr(bn.running_mean), ptr(bn.running_var))
-    return y, mean, rstd
 
 
 def batchnorm_bwd16(z: torch.Tensor, y: Optional[torch.Tensor], mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor,

@@ -21,7 +21,7 @@
                   product's weight gradient and of the elementwise backward kernels (csrc/k_train16.hip, k_train.hip, k_colsum.hip: residual + LayerScale + LayerNorm
                   in one pass, GELU 16 -> 16 and its derivative, the LayerScale gradient with a 16-bit factor, the transposed operand image
                   above 12,288 tokens; the flash kernels with a 16-bit output).
-                  ResNet (csrc/k_bn16.hip): z and y of every convolution + BatchNorm unit.  A unit takes its input in T, writes z in T
+                  ResNet (csrc/k_bn.hip): z and y of every convolution + BatchNorm unit.  A unit takes its input in T, writes z in T
                   (mst_conv_gemm16) and y in T (mst_batchnorm_train16); that y IS the next unit's convolution operand, the operand of its
                   weight gradient and the residual of the unit that closes the block -- no fp32 activation, no second 16-bit copy, 4 bytes
                   per activation element instead of 10.  Backward: ONE mst_batchnorm_bwd16 per unit (ReLU mask, both sums, dz rounded to T,

@@ -12,10 +12,11 @@ forward runs the model op by op through the C ABI and whose backward produces ev
                    dx -- only when the source asks for a gradient -- is mst_conv_dgrad_stem (per-tile dz . Wg in LDS, gathered: no atomics)
      16-bit        a 16-bit train_precision: the three products on 16-bit MFMA operands with fp32 accumulation (mst_conv_gemm16,
                    mst_conv_dgrad, mst_conv_wgrad16)
-  BatchNorm2d      batch statistics + running-stat update (mst_batchnorm_train), residual add and ReLU in the same pass
+  BatchNorm2d      batch statistics + running-stat update, residual add and ReLU in the same pass: hip.batchnorm_train, which takes the
+                   entry point by z's dtype (csrc/k_bn.hip: one kernel family, one host sequence for every mode)
      backward      mst_batchnorm_bwd (ReLU mask first: mst_act_bwd on the saved output)
-     16-bit stored train_storage='16bit' (csrc/k_bn16.hip): mst_batchnorm_train16, ONE mst_batchnorm_bwd16 per unit
-  max / avg pool   mst_maxpool_bwd_nhwc / mst_avgpool_bwd_nhwc
+     16-bit stored train_storage='16bit': mst_batchnorm_train16, ONE mst_batchnorm_bwd16 per unit (it takes the mask from the saved y)
+  max / avg pool   mst_maxpool_bwd_nhwc / mst_avgpool_bwd_nhwc (csrc/k_bn.hip as well; by the input's dtype)
   slice fusion     mst.train.fusion_fwd / fusion_bwd with 16 heads over 512-wide tokens
 
 BatchNorm in train mode normalises over ALL (B D) images of the step, so the step is not chunked: activations of the whole batch stay
@@ -96,7 +97,7 @@ def _conv_bn_fwd(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_i
     else:
         mp = None
         z = _conv(x, wg, None, k, stride, pad, wg.shape[1], hip.EPI_BIAS)    # implicit GEMM behind the stem
-    y, mean, rstd = (hip.batchnorm_train16 if storage16 else hip.batchnorm_train)(z, bn, residual, relu)
+    y, mean, rstd = hip.batchnorm_train(z, bn, residual, relu)             # by z's dtype: fp32, or the 16-bit storage form
     bn.num_batches_tracked += 1
     rec = {"x": x, "z": z, "y": y if relu else None, "mean": mean, "rstd": rstd, "wg": None if storage16 else wg, "k": k, "stride": stride,
            "pad": pad, "sum_in": sum_in, "relu": relu, "conv": conv, "bn": bn, "mp": mp, "x16": x16, "col16": col16, "storage16": storage16}

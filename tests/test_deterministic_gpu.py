@@ -109,6 +109,44 @@ def test_colsum_single_row_block_atomic_equals_ordered_bits(det, bdt):
             assert float(((ordered.double() - out0.double() - prod.sum(0)).abs() - 2e-5 * (out0.double().abs() + prod.abs().sum(0))).max()) <= 0.0
 
 
+def test_batchnorm_single_row_block_atomic_equals_ordered_bits(det):
+    """fp32 BatchNorm forward and backward with residual and ReLU, flag off against flag on, at one row block (rows <= 64, the plan's
+    minimum).  Every sum of both modes -- sum z, sum (z - mean)^2, d gamma, d beta -- is an instantiation of ONE kernel
+    (colreduce_kernel, csrc/k_colsum.hip) that walks the rows in the same order and adds one total per column to a zeroed output, and y
+    and dz come from the same apply kernels (csrc/k_bn.hip): so every output has the same bits.  C: 4 and 64 one column block, 68 a ragged
+    second one, 512 eight; contiguous 16-byte-aligned operands.
+    Expected to FAIL on the library before the BatchNorm kernels were unified: its atomic sum (z - mean)^2, d gamma and d beta were
+    kernels of their own (one thread per column down 256 rows), whose row order is not the ordered form's."""
+    from mst.models.resnet import _BN
+    g = torch.Generator(device="cuda").manual_seed(23)
+    for rows in (1, 17, 64):
+        for C in (4, 64, 68, 512):
+            z = torch.randn(rows, C, device="cuda", generator=g) * 3 + 1
+            res = torch.randn(rows, C, device="cuda", generator=g)
+            dy = torch.randn(rows, C, device="cuda", generator=g)
+            bn0 = _BN(C).cuda()
+            with torch.no_grad():
+                bn0.weight.copy_(torch.rand(C, device="cuda", generator=g) + 0.5)
+                bn0.bias.copy_(torch.randn(C, device="cuda", generator=g) * 0.3)
+
+            def run():
+                bn = copy.deepcopy(bn0)
+                y, mean, rstd = hip.batchnorm_train(z, bn, res, True)
+                d = hip.act_bwd(y, dy.clone(), 1)
+                dz, dg, db = hip.batchnorm_bwd(z, mean, rstd, bn.weight.detach(), d)
+                return y, mean, rstd, bn.running_mean, bn.running_var, dz, dg, db
+
+            ordered = run()
+            _flag(False)
+            try:
+                atomic = run()
+            finally:
+                _flag(True)
+            for name, a, o in zip(("y", "mean", "rstd", "running_mean", "running_var", "dz", "dgamma", "dbeta"), atomic, ordered):
+                assert torch.equal(a, o), (rows, C, name)
+            assert float(ordered[0].abs().sum()) > 0 and (rows == 1 or float(ordered[5].abs().sum()) > 0)    # one row: dz = 0
+
+
 def test_gather_maxpool_backward_equals_the_atomic_kernel_on_ties(det):
     g = torch.Generator(device="cuda").manual_seed(6)
     for n, H, W, C in ((2, 65, 64, 64), (1, 32, 33, 16)):

@@ -475,6 +475,98 @@ def test_pool_backward_kernels_match_torch():
     assert torch.equal(da.cpu(), (d / 20)[:, None, :].expand(3, 20, 16))
 
 
+def _bn_case(rows, C, seed):
+    """(z, residual, dy) on the CPU and a BatchNorm module on the GPU: z normal with a per-channel scale in [0.5, 2] and offset in [-1, 1]."""
+    from mst.models.resnet import _BN
+    g = torch.Generator().manual_seed(seed)
+    scale, offset = torch.rand(C, generator=g) * 1.5 + 0.5, torch.rand(C, generator=g) * 2 - 1
+    z = torch.randn(rows, C, generator=g) * scale + offset
+    res, dy = torch.randn(rows, C, generator=g), torch.randn(rows, C, generator=g)
+    bn = _BN(C)
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(C, generator=g) + 0.5)
+        bn.bias.copy_(torch.randn(C, generator=g) * 0.3)
+        bn.running_mean.copy_(torch.randn(C, generator=g) * 0.2)
+        bn.running_var.copy_(torch.rand(C, generator=g) + 0.5)
+    return z, res, dy, bn.cuda()
+
+
+def _bn_fwd_bwd(z, res, dy, bn0):
+    """BatchNorm + residual + ReLU forward, the ReLU mask, the backward: every output, on a copy of the module."""
+    import copy
+    from mst import hip
+    bn = copy.deepcopy(bn0)
+    y, mean, rstd = hip.batchnorm_train(z, bn, res, True)
+    d = hip.act_bwd(y, dy.clone(), 1)
+    dz, dg, db = hip.batchnorm_bwd(z, mean, rstd, bn.weight.detach(), d)
+    return {"y": y, "mean": mean, "rstd": rstd, "running_mean": bn.running_mean, "running_var": bn.running_var, "dz": dz, "dgamma": dg,
+            "dbeta": db}
+
+
+@pytest.fixture
+def _deterministic_flag(request):
+    was = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(bool(getattr(request, "param", True)))
+    yield
+    torch.use_deterministic_algorithms(was)
+
+
+@pytest.mark.parametrize("rows,C", [(385, 64), (33, 2048)])
+def test_fp32_batchnorm_vector_and_scalar_paths_agree_bitwise(_deterministic_flag, rows, C):
+    """The fp32 entry points take 8 channels per lane (16-byte accesses) when C % 8 == 0 and every base is 16-byte aligned, and one channel
+    per lane with scalar loads otherwise.  z, dy and the residual viewed one float into a larger buffer are contiguous but only 4-byte
+    aligned: the same values through the other path.  Under the determinism flag both paths sum the rows in the same order and evaluate the
+    same expressions (csrc/k_bn.hip, csrc/k_colsum.hip), so every output has the same bits."""
+    z, res, dy, bn = _bn_case(rows, C, 300 + rows)
+
+    def shifted(t):
+        buf = torch.empty(t.numel() + 4, device="cuda")
+        v = buf[1:1 + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return v
+
+    aligned = _bn_fwd_bwd(z.cuda(), res.cuda(), dy.cuda(), bn)
+    scalar = _bn_fwd_bwd(shifted(z), shifted(res), shifted(dy), bn)
+    assert aligned["y"].data_ptr() % 16 == 0
+    for name in aligned:
+        assert torch.equal(aligned[name], scalar[name]), name
+    assert float(aligned["y"].abs().sum()) > 0 and float(aligned["dz"].abs().sum()) > 0
+
+
+@pytest.mark.parametrize("_deterministic_flag", [False, True], ids=["atomic", "ordered"], indirect=True)
+@pytest.mark.parametrize("rows,C", [(385, 64), (140, 72), (2051, 36), (33, 2048)])
+def test_fp32_batchnorm_forward_and_backward_against_fp64(_deterministic_flag, rows, C):
+    """mst_batchnorm_train / mst_batchnorm_bwd and their _ordered forms against fp64 on the same fp32 inputs, with residual and ReLU: a
+    ragged column block and C % 8 != 0 (72), C % 8 != 0 with several row blocks (2051 x 36: 33 blocks of 64 rows), the widest layer with fewer
+    rows than one sweep of the thread rows (33 x 2048).  The bars are those of the neighbouring tests, not fitted to this code: the
+    statistics 1e-5 and d gamma / d beta 2e-5 relative (fp32 sums of exactly known inputs in a blocked order: the 16-bit storage test's
+    bars), y and dz 2e-5 (the unit's bar).  The backward is fed the kernel's own y (the ReLU mask) and statistics.
+    Measured (MI355X): every output of every case between 3.4e-8 and 1.5e-7, in both modes; the library before the BatchNorm kernels were
+    unified passes the same bars."""
+    z, res, dy, bn = _bn_case(rows, C, 400 + rows)
+    rm0, rv0 = bn.running_mean.double().cpu(), bn.running_var.double().cpu()
+    gam, bet, eps = bn.weight.detach().double().cpu(), bn.bias.detach().double().cpu(), bn.eps
+    out = {k: v.cpu() for k, v in _bn_fwd_bwd(z.cuda(), res.cuda(), dy.cuda(), bn).items()}
+    zf = z.double()
+    mu = zf.mean(0)
+    var = ((zf - mu) ** 2).mean(0)
+    rs = (var + eps) ** -0.5
+    y64 = (gam * (zf - mu) * rs + bet + res.double()).clamp_min(0)
+    dyf = dy.double() * (out["y"] > 0).double()
+    xh = (zf - mu) * rs
+    db64, dg64 = dyf.sum(0), (dyf * xh).sum(0)
+    dz64 = gam * rs * (dyf - db64 / rows - xh * dg64 / rows)
+    ref = {"mean": (mu, 1e-5), "rstd": (rs, 1e-5), "running_mean": (0.9 * rm0 + 0.1 * mu, 1e-5),
+           "running_var": (0.9 * rv0 + 0.1 * var * rows / (rows - 1), 1e-5), "y": (y64, 2e-5), "dgamma": (dg64, 2e-5), "dbeta": (db64, 2e-5),
+           "dz": (dz64, 2e-5)}
+    errs = {name: rel_l2(out[name], want) for name, (want, _) in ref.items()}
+    print(f"batchnorm fp32 {rows}x{C} ordered={torch.are_deterministic_algorithms_enabled()}: " +
+          " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    for name, (_, bar) in ref.items():
+        assert errs[name] < bar, (name, errs[name])
+
+
 @pytest.mark.parametrize("shape,masked,model", [((2, 1, 3, 64, 64), False, 18), ((2, 1, 4, 96, 64), True, 34)])
 def test_training_step_matches_autograd_of_oracle(shape, masked, model):
     """Whole step: a WIRING check (residual routing, pooling, slice transformer, parameter mapping, running statistics).  The

@@ -1,4 +1,4 @@
-"""train_storage='16bit' of the ResNet / ResNetSliceTrans training step (csrc/k_bn16.hip, mst/train_resnet.py) and the autocast rule of
+"""train_storage='16bit' of the ResNet / ResNetSliceTrans training step (csrc/k_bn.hip, mst/train_resnet.py) and the autocast rule of
 their train_precision: the new entry points against fp64 on the same 16-bit inputs and against the fp32 entry points on the upcast inputs,
 one convolution + BatchNorm unit forward and backward against fp64 torch with the same roundings inserted, whole models (finite gradients,
 loss, the bytes the saved state takes, peak memory), determinism, autocast.
@@ -176,6 +176,39 @@ def test_batchnorm16_rejects_what_it_cannot_take():
         assert "batchnorm" in hip.last_error()
     assert lib.mst_batchnorm_train16_workspace_bytes(rows, 60) == 0
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("residual,relu", [(False, False), (False, True), (True, True)])
+@pytest.mark.parametrize("C", [8, 64, 136])
+@pytest.mark.parametrize("rows", [1, 9, 16])
+@pytest.mark.parametrize("prec", ["fp16", "bf16"])
+def test_batchnorm16_is_the_fp32_entry_point_on_the_upcast_input(prec, rows, C, residual, relu):
+    """Under the determinism flag the 16-bit and the fp32 BatchNorm are one kernel family (csrc/k_bn.hip, colreduce_kernel of
+    csrc/k_colsum.hip): the same expressions on the same fp32 values.  The two column-sum geometries differ in their thread rows (32 for
+    a 16-bit z, 16 for fp32), but up to 16 rows every thread row of either holds at most one row, so the LDS sums add the same values in
+    the same ascending order (the rest are zeros) and the statistics agree BITWISE; y and dz are then T(the fp32 result).  C: 8 one lane,
+    64 one column block, 136 a ragged third one."""
+    from mst import hip
+    dt = DT[prec]
+    g = torch.Generator().manual_seed(2000 + rows + C)
+    z16 = (torch.randn(rows, C, generator=g) * 2 + 0.5).to(dt).cuda()
+    res16 = torch.randn(rows, C, generator=g).to(dt).cuda() if residual else None
+    dy = torch.randn(rows, C, generator=g).cuda()
+    bn16 = _bn(C, g)
+    bn32 = copy.deepcopy(bn16)
+    gamma = bn16.weight.detach()
+    with _deterministic():
+        y32, mean32, rstd32 = hip.batchnorm_train(z16.float(), bn32, None if res16 is None else res16.float(), relu)
+        y16, mean16, rstd16 = hip.batchnorm_train(z16, bn16, res16, relu)
+        assert y16.dtype == dt and y32.dtype == torch.float32
+        assert torch.equal(mean16, mean32) and torch.equal(rstd16, rstd32)
+        assert torch.equal(bn16.running_mean, bn32.running_mean) and torch.equal(bn16.running_var, bn32.running_var)
+        assert torch.equal(y16, y32.to(dt))
+        dy32 = hip.act_bwd(y16.float(), dy.clone(), 1) if relu else dy.clone()
+        dz32, dg32, db32 = hip.batchnorm_bwd(z16.float(), mean32, rstd32, gamma, dy32)
+        dz16, dg16, db16 = hip.batchnorm_bwd16(z16, y16 if relu else None, mean16, rstd16, gamma, dy.clone(), False)
+    assert dz16.dtype == dt and torch.equal(dz16, dz32.to(dt))
+    assert torch.equal(dg16, dg32) and torch.equal(db16, db32)
 
 
 # ---- 2. the pools ------------------------------------------------------------------------------------------------------------------------
