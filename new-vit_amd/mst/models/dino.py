@@ -13,6 +13,8 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
                   'fp8' (BASELINE configs[4]): the blocks' four linear layers with OCP e4m3 operands and
                   per-tensor absmax scales (dynamic for activations), everything else as in bf16 mode.
   train_precision, train_attention, train_storage  the mode of the TRAINING step: see mst/train_mode.py.
+  train_chunk_slices  slices per recomputed encoder chunk of the TRAINING step (0, the default: the encoder's state is kept from forward to
+                  backward); see mst/train_mode.py.  Not ``chunk_slices`` below, which is inference's.
   Gradients: under torch.enable_grad() the forward returns logits with one autograd node (mst/train.py) when a parameter requires grad,
                   or when ``source`` is a floating tensor that requires grad (a frozen model: saliency, attribution) and ``save_attn`` is off;
                   slice-sharded or not.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
@@ -253,6 +255,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         # hyper-parameters (they are the constructor's public locals)
         train_precision, train_attention, train_storage, _precision_given = train_mode.from_kwargs(
             kwargs, storage_env="MST_TRAIN_STORAGE", attention=True)
+        train_chunk_slices = train_mode.chunk_from_kwargs(kwargs)
         if compute_dtype not in hip.DT_NAMES:
             raise ValueError(f"compute_dtype must be one of {sorted(hip.DT_NAMES)}")
         super().__init__(in_ch, out_ch, spatial_dims=spatial_dims, optimizer_kwargs=optimizer_kwargs, **kwargs)
@@ -266,6 +269,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         self.train_precision = train_precision
         self.train_attention = train_attention
         self.train_storage = train_storage
+        self.train_chunk_slices = train_chunk_slices
         self._train_precision_given = _precision_given
         self._graphs = {}
         self.save_attn = save_attn

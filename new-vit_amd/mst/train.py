@@ -38,6 +38,26 @@ bucket if an encoder parameter needs a gradient, d source if it is asked for; a 
 rank.  A rank with an empty shard (fewer slices than ranks) launches no encoder kernel and contributes zeros.  EVERY RANK OF A GROUP MUST BE FED
 THE SAME BATCH AND THE SAME ``dout`` (the same loss on the same targets): the replicated stage is only replicated if its inputs are.  Under DDP
 over the same or a larger group the summed gradients are already identical within a sharding group, so DDP's mean leaves them as they are.
+
+Recomputation per slice chunk (``train_chunk_slices = k > 0``, mst/train_mode.py): the whole model is one autograd node, so torch.utils.checkpoint
+cannot be put around parts of it; this is the library's own form.  The encoder treats every slice alone -- LayerNorm per token, attention per
+slice, no statistic across slices; only the slice transformer behind it couples them -- so encoding the flattened slice rows [B*D] k at a time
+is the same function.  Forward: every chunk runs `_encoder_fwd` into a throw-away dict and only its rows of the embeddings are kept; what does
+not depend on the chunk (the summed patch kernel, the prefix rows, the interpolated position grid: `_encoder_consts`) is made once.  Between
+forward and backward the state holds the volume, the embeddings, the fusion and head state, the resolved mode and k: no per-block tensor.
+Backward: head, fusion, slice_pos_emb and bottleneck as ever down to d emb, then per chunk in the forward's order `_encoder_fwd` again, saving, in
+the mode the state carries (never resolved again: an autocast region may have ended), and `_encoder_bwd` on that chunk's rows of d emb into the
+same `_Grads`, whose `put` adds every later chunk's parameter gradients to the first's (pos_embed, cls_token, register_tokens and the patch
+embedding included); d source is written chunk by chunk into one [B*D, H, W] buffer.  The chunk order is fixed, so the step stays bit-reproducible
+under the deterministic flag; a single chunk (k >= rows) gives the plain step's bits.  The pruning rules are unchanged.  Peak block state falls
+from all slices to k; the price is one more encoder forward per step -- and every chunk issues the launches of two forwards and a backward,
+which on model_size='s' makes the host the bound (measured: DESIGN.md 4b, profiles/train_chunk_slices.jsonl).  Under slice sharding each rank chunks its own rows, the collectives are
+the same, an empty shard still launches nothing.  The ResNet step (mst/train_resnet.py) has no such mode: BatchNorm's batch statistics couple
+the slices of a batch.
+
+A frozen encoder keeps nothing: when no encoder parameter and not ``source`` needs a gradient (the node's needs_input_grad; `forward_train`'s
+``encoder_state``), the forward drops the block state as soon as the embeddings exist, whatever k is -- the backward returns before the
+encoder anyway.  Outputs and the remaining gradients are the same bits.
 """
 from __future__ import annotations
 
@@ -334,7 +354,10 @@ def fusion_bwd(G: "_Grads", model, t, dfeat: torch.Tensor, B: int, D: int, e: in
     return dxs.view(B, L, e)[:, 1:].contiguous().view(B * D, e)
 
 
-def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], without_linear: bool):
+def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], without_linear: bool, encoder_state: Optional[bool] = None):
+    """The training forward: (logits or features, the state `backward_train` reads).  encoder_state: whether a backward will go through the
+    encoder at all -- the autograd node passes its needs_input_grad; None derives it as the node would (an encoder parameter or ``source``
+    requires grad).  Without it nothing of the encoder but the slice embeddings is kept."""
     if model.rotary is not None and model.rotary != "RoPE":
         raise NotImplementedError("training step: the LieRE variant of the slice transformer is not on the HIP backward (its rotation "
                                   "generators are learned: the adjoint of the matrix exponential is not built); RoPE is")
@@ -362,8 +385,12 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     sv = {"B": B, "D": D, "H": H, "W": W, "vol": vol, "without_linear": without_linear, "src_shape": (B, C, D0, H, W),
           "interp": interp, "shard": (d0, d1, dpad) if sh is not None else None}
     sv["mp"], sv["storage16"] = mode.mp, mode.storage16   # the backward reads the resolved mode from here (an autocast region may have ended)
+    sv["mode"], sv["chunk"] = mode, mode.chunk            # (the chunked backward's recomputation runs in the whole of it)
+    if encoder_state is None:
+        encoder_state = bool(torch.is_tensor(source) and source.requires_grad) or any(p.requires_grad for p in enc.parameters())
+    sv["encoder_state"] = bool(encoder_state)
     if sh is None:
-        emb = _encoder_fwd(model, sv, mode, vol, B * D, H, W)
+        emb = _encoder_fwd_kept(model, sv, mode, vol, B * D, H, W)
     else:
         # slice sharding: the encoder on this rank's rows alone (no kernel at all on an empty shard: zeros travel), ONE all-gather of the
         # padded shards' slice embeddings, and everything behind the encoder replicated on the full [B*D, E].  Every rank of the group
@@ -371,7 +398,7 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
         E = enc.embed_dim
         emb_l = torch.zeros((B, dpad, E), dtype=torch.float32, device=dev)
         if dl:
-            emb_l[:, :dl].copy_(_encoder_fwd(model, sv, mode, vol, B * dl, H, W).view(B, dl, E))
+            emb_l[:, :dl].copy_(_encoder_fwd_kept(model, sv, mode, vol, B * dl, H, W).view(B, dl, E))
         emb = sh.all_gather_slices(emb_l, D).reshape(B * D, E)
     sv["emb"] = emb
     return _fusion_head_fwd(model, sv, emb, B, D, mask, without_linear)
@@ -383,22 +410,33 @@ def _sharding_of(model):
     return sh if sh is not None and sh.world_size > 1 else None
 
 
-def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, W: int) -> torch.Tensor:
-    """Tokens, blocks and the final LayerNorm's CLS rows of the n slices in `vol`; what the backward needs goes into sv.  Returns the slice
-    embeddings [n, E]."""
-    enc = model.encoder
+def _encoder_fwd_kept(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, W: int) -> torch.Tensor:
+    """The slice embeddings [n, E] of the n slices in `vol`, and in sv what the forward keeps of the encoder for the backward:
+      mode.chunk == 0, a backward through the encoder to come   one pass, its whole state (`_encoder_fwd`);
+      mode.chunk == 0, none to come (frozen encoder, no source gradient)   one pass into a throw-away dict: nothing;
+      mode.chunk == k > 0   the rows k at a time (the last chunk may be short, a chunk may straddle a volume boundary), each into a
+                            throw-away dict: only what does not depend on the chunk (`_encoder_consts`); `_encoder_bwd_chunked`
+                            recomputes the rest."""
+    if mode.chunk <= 0:
+        return _encoder_fwd(model, sv if sv["encoder_state"] else {"interp": sv["interp"]}, mode, vol, n, H, W)
+    consts = sv["consts"] = _encoder_consts(model.encoder, sv["interp"], H, W, vol.device)
+    emb = torch.empty((n, model.encoder.embed_dim), dtype=torch.float32, device=vol.device)
+    for r0 in range(0, n, mode.chunk):
+        r1 = min(n, r0 + mode.chunk)
+        emb[r0:r1].copy_(_encoder_fwd(model, {}, mode, vol[r0:r1], r1 - r0, H, W, consts))
+    return emb
+
+
+def _encoder_consts(enc, interp: bool, H: int, W: int, dev) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """What the token stage reads besides the volume, the same for every slice: (the position rows of the gh x gw patch grid, the prefix
+    rows [1 + R, E], the channel-summed patch kernel [E, 14 * 16])."""
     R = int(enc.num_register_tokens)                     # register tokens (vision_transformer.py:222-230): extra prefix rows without a position
-    dev = vol.device
-    E, heads = enc.embed_dim, enc.num_heads
+    E = enc.embed_dim
     gh, gw = H // PATCH, W // PATCH
-    Np = gh * gw
-    N = 1 + R + Np
-    M = n * N
-    sv["R"] = R
     # ---- tokens (patch_embed.py:68-81; vision_transformer.py:213-232)
     pos = enc.pos_embed.detach()[0]
     Mg = int(math.isqrt(pos.shape[0] - 1))
-    pos_patch = hip.pos_embed_interp(pos[1:].contiguous(), Mg, gh, gw, 0.1) if sv["interp"] else pos[1:].contiguous()
+    pos_patch = hip.pos_embed_interp(pos[1:].contiguous(), Mg, gh, gw, 0.1) if interp else pos[1:].contiguous()
     prefix = torch.zeros((1 + R, E), dtype=torch.float32, device=dev)
     prefix[:1].copy_(pos[:1])
     hip.axpby_cols(enc.cls_token.detach().reshape(1, E), prefix[:1])
@@ -408,6 +446,19 @@ def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, 
     w = enc.patch_embed.proj.weight.detach()
     for c in range(3):
         hip.axpby_cols(w[:, c].contiguous().view(E * PATCH, PATCH), wsum, x_stride=PATCH, y_stride=16, rows=E * PATCH, cols=PATCH)
+    return pos_patch, prefix, wsum
+
+
+def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, W: int, consts=None) -> torch.Tensor:
+    """Tokens, blocks and the final LayerNorm's CLS rows of the n slices in `vol`; what the backward needs goes into sv.  Returns the slice
+    embeddings [n, E].  consts: `_encoder_consts` of this shape if the caller has them (a chunk of several), else they are made here."""
+    enc = model.encoder
+    R = int(enc.num_register_tokens)
+    E, heads = enc.embed_dim, enc.num_heads
+    N = 1 + R + (H // PATCH) * (W // PATCH)
+    M = n * N
+    sv["R"] = R
+    pos_patch, prefix, wsum = consts if consts is not None else _encoder_consts(enc, sv["interp"], H, W, vol.device)
     sv["wsum"] = wsum                                    # the source gradient's kernel (mst_patch_embed_dgrad) reads the same sum
     xt = hip.patch_embed(vol, wsum, enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
     # ---- blocks (block.py:89-114)
@@ -479,17 +530,21 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
         dp[:D].copy_(acc.view(D, e))
         G.put(model.slice_pos_emb.weight, dp)
     demb = G.lin_bwd(dtok, sv["emb"], model.bottleneck) if hasattr(model, "bottleneck") else dtok
-    if not need_src and not any(p.requires_grad for p in enc.parameters()):
+    if not need_src and not (sv["encoder_state"] and any(p.requires_grad for p in enc.parameters())):
         return G.by_param, None                                                  # frozen encoder (dino.py:65-67)
+    if not sv["encoder_state"]:
+        raise RuntimeError("training step: this forward was told that no backward goes through the encoder (no encoder parameter and no source "
+                           "required grad) and kept nothing of it; a source gradient needs forward_train(..., encoder_state=True)")
+    encoder_bwd = _encoder_bwd_chunked if sv["chunk"] > 0 else _encoder_bwd
     if sv["shard"] is None:
-        return G.by_param, _encoder_bwd(G, enc, sv, demb, B * D, need_src)
+        return G.by_param, encoder_bwd(G, model, sv, demb, B * D, need_src)
     # ---- slice sharding: this rank's rows of d emb through its own slices, then the encoder's parameter gradients summed over the group
     # (the replicated parameters above are complete and identical on every rank already: they do not travel) and d source gathered.
     # Every rank issues the same collectives whatever its shard holds; an empty shard launches no kernel and contributes zeros.
     sh = _sharding_of(model)
     d0, d1, dpad = sv["shard"]
     dl = d1 - d0
-    dvol = _encoder_bwd(G, enc, sv, demb.reshape(B, D, -1)[:, d0:d1].reshape(B * dl, -1).contiguous(), B * dl, need_src) if dl else None
+    dvol = encoder_bwd(G, model, sv, demb.reshape(B, D, -1)[:, d0:d1].reshape(B * dl, -1).contiguous(), B * dl, need_src) if dl else None
     wanted = [p for p in enc.parameters() if G.need(p) and p is not enc.mask_token]                      # (the forward never reads mask_token)
     if wanted:
         # ONE flat fp32 bucket: a single concatenation fills it, the gradients handed back are views of the reduced bucket
@@ -511,9 +566,26 @@ def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = N
     return G.by_param, sh.all_gather_slices(dvol_l, D).view(B * D, H, W)
 
 
-def _encoder_bwd(G: "_Grads", enc, sv, demb: torch.Tensor, n: int, need_src: bool) -> Optional[torch.Tensor]:
+def _encoder_bwd_chunked(G: "_Grads", model, sv, demb: torch.Tensor, n: int, need_src: bool) -> Optional[torch.Tensor]:
+    """`_encoder_bwd`'s results for a forward that kept no encoder state (train_chunk_slices > 0): per chunk of the forward, in its order,
+    the encoder forward again with saving -- in the mode the forward resolved -- and straight into that chunk's backward.  The parameter
+    gradients of the chunks sum in G (`_Grads.put`: the first is kept, every later one added, a fixed order); each chunk's d volume is
+    written into its rows of one [n, H, W] buffer.  One chunk's state lives at a time."""
+    H, W, k = sv["H"], sv["W"], sv["chunk"]
+    dvol = torch.empty((n, H, W), dtype=torch.float32, device=demb.device) if need_src else None
+    for r0 in range(0, n, k):
+        r1 = min(n, r0 + k)
+        cs = {"H": H, "W": W, "mp": sv["mp"], "interp": sv["interp"], "vol": sv["vol"][r0:r1]}
+        _encoder_fwd(model, cs, sv["mode"], cs["vol"], r1 - r0, H, W, sv["consts"])
+        _encoder_bwd(G, model, cs, demb[r0:r1], r1 - r0, need_src, dvol[r0:r1] if need_src else None)
+        del cs                                           # the chunk's state goes before the next chunk's is made
+    return dvol
+
+
+def _encoder_bwd(G: "_Grads", model, sv, demb: torch.Tensor, n: int, need_src: bool, dvol: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Backward of `_encoder_fwd` over its n slices from the gradient of their embeddings [n, E]: parameter gradients into G; returns d volume
-    ([n, H, W] fp32) with `need_src`."""
+    ([n, H, W] fp32; written into `dvol` if the caller brings it) with `need_src`."""
+    enc = model.encoder
     dev = demb.device
     H, W = sv["H"], sv["W"]
     G.mp = sv["mp"]                                      # the blocks' nn.Linear products on 16-bit operands, as the forward resolved them
@@ -563,7 +635,7 @@ def _encoder_bwd(G: "_Grads", enc, sv, demb: torch.Tensor, n: int, need_src: boo
     # ---- tokens
     dsrc = None
     if need_src:                                         # d volume straight from the patch rows of dx (adjoint of the grey -> RGB patch embedding)
-        dsrc = hip.patch_embed_dgrad(dx, sv["wsum"], n, H, W, tokens=N, first=1 + R)
+        dsrc = hip.patch_embed_dgrad(dx, sv["wsum"], n, H, W, tokens=N, first=1 + R, out=dvol)
     pe = enc.patch_embed.proj
     if G.need(enc.cls_token) or G.need(enc.pos_embed):
         dcls = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -627,8 +699,11 @@ class _MSTFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, source, mask, without_linear, *params):
+        # a frozen encoder under a source that needs no gradient: no backward reads its state, so the forward keeps none of it
+        enc_ids = {id(p) for p in model.encoder.parameters()}
+        encoder_state = bool(ctx.needs_input_grad[1]) or any(need and id(p) in enc_ids for p, need in zip(params, ctx.needs_input_grad[4:]))
         with torch.no_grad():
-            out, saved = forward_train(model, source, mask, without_linear)
+            out, saved = forward_train(model, source, mask, without_linear, encoder_state)
         ctx.model, ctx.saved, ctx.params = model, saved, params
         ctx.src_dtype, ctx.src_device = source.dtype, source.device
         return out

@@ -1,4 +1,5 @@
-"""The training mode of the HIP training steps (mst/train.py, mst/train_resnet.py): three model attributes, one validator, one resolver.
+"""The training mode of the HIP training steps (mst/train.py, mst/train_resnet.py): three model attributes, one validator, one resolver -- and
+train_chunk_slices, the fourth attribute of DinoV2ClassifierSlice alone.
 
   train_precision 'fp32' (default) | 'bf16' | 'fp16' (env MST_TRAIN_PRECISION): MFMA operand type of the step's products -- the encoder
                   blocks' nn.Linear (forward, d input, d weight) of DinoV2ClassifierSlice, the convolutions and their two gradients of
@@ -28,6 +29,18 @@
                   the masked dy for the shortcut); its BatchNorm sums are fixed-order always.
                   Gradients stay fp32 in both (they are ~1e-6: csrc/k_attn16_train.hip), as do the residual stream, the weight-gradient
                   partials, the token stage, the slice transformer and the head.
+  train_chunk_slices  0 (default) | k > 0 (env MST_TRAIN_CHUNK_SLICES; DinoV2ClassifierSlice only): recompute the encoder per chunk of k slices
+                  instead of keeping its block state from forward to backward.  0 is the plain step.  With k > 0 the forward encodes the
+                  flattened slice rows [B * D] (under slice sharding this rank's B * dl) k at a time and keeps only their embeddings; the
+                  backward, behind the head and the slice transformer, runs per chunk the encoder forward again -- now saving -- and straight
+                  into that chunk's backward, in the forward's chunk order.  The encoder has no statistic across slices (LayerNorm per token,
+                  attention per slice), so this is the same function: the block state (66 E or 40 E bytes per token and block, above) is held
+                  for k slices instead of all, at the price of one more encoder forward per step, issued chunk by chunk (on 's' the host's
+                  issue time then bounds the step: take the largest k that fits).  A non-negative integer (`check_chunk`), never
+                  inferred from the three attributes above and free to combine with each of their values; it may be changed between steps.
+                  It is not the inference keyword chunk_slices / MST_CHUNK_SLICES.  ResNet and ResNetSliceTrans do not take it and the
+                  variable does not reach them: their BatchNorm normalises with the statistics of the whole batch of slices, so a chunk's
+                  forward is a different function from the batch's.
 
 Every illegal combination is a ValueError from `check`, at construction (`from_kwargs`) and again at every call (`resolve`: the
 attributes may have been changed since).
@@ -53,6 +66,7 @@ class TrainMode(NamedTuple):
     mp: Optional[torch.dtype]                            # MFMA operand type of the step's products; None: exact fp32
     flash: bool                                          # train_attention == 'flash'
     storage16: bool                                      # train_storage == '16bit'
+    chunk: int = 0                                       # train_chunk_slices: slices per recomputed encoder chunk; 0: the state is kept
 
 
 def _dtype(precision: str) -> Optional[torch.dtype]:
@@ -77,6 +91,28 @@ def check(precision_is_16bit: bool, attention: str, storage: str, *, needs_flash
     return attention == "flash", storage == "16bit"
 
 
+def check_chunk(value) -> int:
+    """train_chunk_slices as a non-negative int.  Integers and their decimal strings (the environment's form) pass; a negative number, a
+    fraction or anything else is a ValueError."""
+    k = value
+    if isinstance(k, str):
+        try:
+            k = int(k.strip())
+        except ValueError:
+            k = None
+    elif isinstance(k, float) and k.is_integer():
+        k = int(k)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"train_chunk_slices must be a non-negative integer: the slices per recomputed encoder chunk, 0 to keep the encoder's "
+                         f"state (got {value!r})")
+    return k
+
+
+def chunk_from_kwargs(kwargs: dict) -> int:
+    """DinoV2ClassifierSlice's constructor: pops train_chunk_slices from `kwargs`, defaulting to MST_TRAIN_CHUNK_SLICES and then 0."""
+    return check_chunk(kwargs.pop("train_chunk_slices", os.environ.get("MST_TRAIN_CHUNK_SLICES", 0)))
+
+
 def from_kwargs(kwargs: dict, *, storage_env: str, attention: bool) -> Tuple[str, str, str, bool]:
     """A model constructor's share: pops train_precision, train_attention (with `attention`: the model has attention blocks) and
     train_storage from `kwargs`, each defaulting to its environment variable (`storage_env`: the family's own), lower-cased and checked.
@@ -99,4 +135,5 @@ def resolve(model) -> TrainMode:
             mp = dt
     flash, storage16 = check(mp is not None, getattr(model, "train_attention", "stored"), getattr(model, "train_storage", "fp32"),
                              needs_flash=hasattr(model, "train_attention"))
-    return TrainMode(mp, flash, storage16)
+    # train_chunk_slices exists on DinoV2ClassifierSlice only: a ResNet resolves to 0 whatever the environment says
+    return TrainMode(mp, flash, storage16, check_chunk(getattr(model, "train_chunk_slices", 0)))

@@ -8,7 +8,10 @@ keeps the ResNet lines, --resnet-only skips the DinoV2ClassifierSlice cases).
 --train-storage 16bit (beside --train-attention flash and a 16-bit precision): the encoder blocks' saved activations in 16 bits.  A comma
 list (fp32,16bit,fp32) times those modes one after the other in this process: the repeated mode gives the spread the other is read against.
 The same list drives the ResNet cases (train_storage of ResNetSliceTrans: --c3 for the configs[3] shape, --only-resnet for 2 x 32 x 224^2; add
---c3-only to --c3 to leave the smaller shape out)."""
+--c3-only to --c3 to leave the smaller shape out).
+--train-chunk-slices K[,K...] (DinoV2ClassifierSlice cases only; the ResNets have no such mode): train_chunk_slices of the model, one arm per
+value in the given order in this process -- 0 is the plain step, the same-process baseline the others are read against.  --model-size g
+(with it --steps N and --warmup W in place of the defaults) runs the arms on that encoder; --out FILE appends the DINOv2 lines to FILE."""
 import json
 import sys
 import time
@@ -306,7 +309,7 @@ def resnet_input_grad_cases(c3, out_path):
         sys.exit("gate: mst_conv_dgrad_stem is slower than the explicit gather form")
 
 
-def train_case(name, model, shape, n=5):
+def train_case(name, model, shape, n=5, warm=2, extra=None):
     model = model.cuda().train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-5)
     src = synth.synth_volume(shape, 3).cuda()
@@ -322,14 +325,28 @@ def train_case(name, model, shape, n=5):
         with torch.no_grad():
             model(src)
     torch.cuda.reset_peak_memory_stats()
-    ms = timed(step, n)
+    issued = []
+
+    def steps_then_mark():                               # the host's share: how long issuing the n steps takes, the device still running
+        for _ in range(n):
+            step()
+        issued.append(time.perf_counter())
+    for _ in range(warm):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ms = timed(steps_then_mark, 1, 0) / n
+    if extra is not None:
+        extra = {**extra, "host_issue_ms": round((issued[0] - t0) / n * 1e3, 2)}
     peak = torch.cuda.max_memory_allocated() / 2 ** 30
     model.eval()
-    ms_f = timed(fwd, n)
-    print(json.dumps({"case": name, "shape": list(shape), "train_step_ms": round(ms, 2), "eval_forward_ms": round(ms_f, 2),
-                      "volumes_per_s_training": round(shape[0] / ms * 1e3, 2), "peak_GiB": round(peak, 2),
-                      "deterministic": torch.are_deterministic_algorithms_enabled(),
-                      "fill_uninitialized_memory": torch.utils.deterministic.fill_uninitialized_memory}), flush=True)
+    ms_f = timed(fwd, n, warm)
+    line = json.dumps({"case": name, "shape": list(shape), **(extra or {}), "train_step_ms": round(ms, 2), "eval_forward_ms": round(ms_f, 2),
+                       "volumes_per_s_training": round(shape[0] / ms * 1e3, 2), "peak_GiB": round(peak, 2),
+                       "deterministic": torch.are_deterministic_algorithms_enabled(),
+                       "fill_uninitialized_memory": torch.utils.deterministic.fill_uninitialized_memory})
+    print(line, flush=True)
+    return line
 
 
 def main():
@@ -351,23 +368,36 @@ def main():
     attn = sys.argv[sys.argv.index("--train-attention") + 1] if "--train-attention" in sys.argv else "stored"
     # --train-storage 16bit | fp32,16bit,fp32: the blocks' saved activations (16-bit precisions with flash attention only; others keep 'fp32')
     storages = sys.argv[sys.argv.index("--train-storage") + 1].split(",") if "--train-storage" in sys.argv else ["fp32"]
+    # --train-chunk-slices 0,16,8: the encoder recomputed per chunk of that many slices in the backward (0: its state kept), an arm per value
+    chunked = "--train-chunk-slices" in sys.argv
+    chunks = [int(v) for v in sys.argv[sys.argv.index("--train-chunk-slices") + 1].split(",")] if chunked else [0]
+    size = sys.argv[sys.argv.index("--model-size") + 1] if "--model-size" in sys.argv else "s"
+    steps = int(sys.argv[sys.argv.index("--steps") + 1]) if "--steps" in sys.argv else None
+    warm = int(sys.argv[sys.argv.index("--warmup") + 1]) if "--warmup" in sys.argv else 2
+    out = Path(sys.argv[sys.argv.index("--out") + 1]) if "--out" in sys.argv else None
     all_shapes = (("--only-dino-c1", (1, 1, 16, 224, 224)), ("--only-dino-2x32", (2, 1, 32, 224, 224)), ("--only-dino-518", (1, 1, 64, 518, 518)))
     dino_shapes = tuple(sh for flag, sh in all_shapes if flag in sys.argv) or tuple(sh for _, sh in all_shapes)    # several --only-dino-* add up
     for shape in (() if "--only-resnet" in sys.argv else dino_shapes):
-        for prec in (("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("fp32",)):
+        for prec in (("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("bf16",) if "--bf16" in sys.argv else ("fp32",)):
             a = attn if prec != "fp32" else "stored"
-            for st in (storages if a == "flash" else ["fp32"]):
-                m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, train_precision=prec, train_attention=a, train_storage=st)
-                m.load_state_dict(synth.synth_state_dict("s", 0))
-                train_case(f"DinoV2ClassifierSlice training step ({prec} linear products, {a} attention, {st} storage, HIP backward)", m, shape,
-                           n=3 if shape[2] >= 64 else 5)
+            for st, k in ((st, k) for st in (storages if a == "flash" else ["fp32"]) for k in chunks):
+                m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, model_size=size, train_precision=prec, train_attention=a,
+                                          train_storage=st, train_chunk_slices=k)
+                m.load_state_dict(synth.synth_state_dict(size, 0))
+                line = train_case(f"DinoV2ClassifierSlice training step ({prec} linear products, {a} attention, {st} storage, HIP backward)"
+                                  + (f", model_size {size}" if size != "s" else ""), m, shape, n=steps or (3 if shape[2] >= 64 else 5), warm=warm,
+                                  extra={"model_size": size, "train_chunk_slices": k} if chunked else None)
+                if out is not None:
+                    out.parent.mkdir(parents=True, exist_ok=True)
+                    with out.open("a") as f:
+                        f.write(line + "\n")
                 del m
                 torch.cuda.empty_cache()
     if "--only-dino-c1" in sys.argv or "--only-dino-2x32" in sys.argv or "--only-dino-518" in sys.argv:
         return
     # the ResNet arms: --train-storage drives them too (the backbone's saved activations; 16-bit precisions only, fp32 keeps 'fp32'), one
     # model per arm in the given order in this process
-    precs = ("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("fp32",)
+    precs = ("fp32", "bf16", "fp16") if "--mixed" in sys.argv else ("fp16",) if "--fp16" in sys.argv else ("bf16",) if "--bf16" in sys.argv else ("fp32",)
 
     def resnet_arms(case, shape, precs, n):
         for prec in precs:
