@@ -19,7 +19,8 @@
 // conflict-free ds_read_b128 at lane*16).  The stream runs through a 6-slot LDS ring by LDS-DMA four elements ahead; a "phase"
 // consumes one element in 24 slots of [fragment read 6 ahead | counted lgkmcnt | MFMA | a few vector instructions of the GELU
 // of a neighbouring chunk], with one s_barrier per phase.  Fragment reads run across the phase boundaries (the barrier of phase e
-// also publishes element e + 1), so the LDS latency never surfaces.
+// also publishes element e + 1), so the LDS latency never surfaces.  A tile consumes 108 = 18 x 6 elements: the ring slot of every
+// phase is a compile-time constant, and the MLP loop is rolled over one ring period (12 phases; profiles/NOTES_block_mlp_loop.md).
 // The twelve out-projection elements are fetched from that stream in another order, (accumulator tile pair, K half)-major, so that
 // pair P is first touched in phase 2P: the finished rows of the previous tile leave, and this tile's x arrives, pair by pair from
 // inside those phases, and only pair 0 and the attention rows stand between two tiles (see "row traffic" below).
@@ -65,8 +66,18 @@ constexpr int BIAS_SLOT = 8;                            // slot of a phase in wh
 template <int OFF, typename V> __device__ __forceinline__ void lds_read_b128(V& dst, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
 }
-template <int OFF, typename V> __device__ __forceinline__ void lds_read_b128_acc(V& dst, unsigned addr) {   // into the accumulator file
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(dst) : "v"(addr), "i"(OFF));
+// b1 of a chunk goes into quarter Q of the sixteen registers the chunk's GEMM1 accumulates in.  The registers are named: left to
+// choose, hipcc put the four quarters of a chunk into registers that do not form one MFMA accumulator and moved them there at the
+// head of the GEMM1 phase (76 v_accvgpr moves per twelve phases of the rolled MLP loop, 16 with the names).
+template <int OFF, int Q, int HS> __device__ __forceinline__ void lds_read_b128_hq(f32x4& dst, unsigned addr) {
+    if constexpr (HS == 0 && Q == 0) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[192:195]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 0 && Q == 1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[196:199]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 0 && Q == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[200:203]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 0 && Q == 3) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[204:207]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 1 && Q == 0) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[208:211]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 1 && Q == 1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[212:215]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 1 && Q == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[216:219]}"(dst) : "v"(addr), "i"(OFF));
+    if constexpr (HS == 1 && Q == 3) asm volatile("ds_read_b128 %0, %1 offset:%2" : "={a[220:223]}"(dst) : "v"(addr), "i"(OFF));
 }
 template <int N> __device__ __forceinline__ void wait_lgkm() {       // + fence: no MFMA above the wait (rule 18)
     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
@@ -164,14 +175,15 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     // this wave's share: the six consecutive 1 KiB pieces 6 wave .. 6 wave + 5 (one lane address, one M0, six immediates).
     // The stream simply wraps: the four elements issued beyond the last tile land in slots nobody reads (drained before exit).
     // buffer form: the piece base rides in soffset (SGPR), the lane part is ONE 32-bit VGPR: half the address traffic per issue
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wseq, 0, ELEMS * ELEM_BYTES, 0x00020000);
-    const int wlane_off = wave * 6144 + lane16;
+    // (the descriptor starts at the wave's share, so the lane part is the lane address the fragment reads use as well)
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(wseq + wave * 6144), 0, ELEMS * ELEM_BYTES - wave * 6144, 0x00020000);
     char* const wdst_wave = smem + wave * 6144;
-    auto dma_piece = [&](int src_off, int slot, auto u_tag) {
-        constexpr int u = decltype(u_tag)::value;
+    // (the ring slot is a constant of the call site everywhere: M0 is the wave's base plus an immediate)
+    auto dma_piece = [&](int src_off, auto slot_tag, auto u_tag) {
+        constexpr int u = decltype(u_tag)::value, slot = decltype(slot_tag)::value;
         // (the 12-bit immediate moves the source AND the LDS address: pieces 4 and 5 take a second base 4 KiB further on both sides)
         constexpr int hi = u >= 4 ? 4096 : 0;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, wlane_off, src_off + hi, u * 1024 - hi, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, (int)lane16, src_off + hi, u * 1024 - hi, 0);
     };
     // Out-projection element (P, H) is gathered from the unchanged stream: piece n = 6 wave + u of the ring element is fragment
     // (4P + n % 4) of stream element 6H + n / 4.  Same lane address form, the per-piece source offset rides in an SGPR.
@@ -179,15 +191,14 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
         const int n = 6 * wave + u;
-        pair_piece_off[u] = (n >> 2) * ELEM_BYTES + (n & 3) * 1024 - (u >= 4 ? u * 1024 - 4096 : u * 1024);
+        pair_piece_off[u] = (n >> 2) * ELEM_BYTES + (n & 3) * 1024 - (u >= 4 ? u * 1024 - 4096 : u * 1024) - wave * 6144;   // (>= 0)
     }
-    auto dma_pair_piece = [&](auto pe_tag, int slot, auto u_tag) {
-        constexpr int u = decltype(u_tag)::value, pe = decltype(pe_tag)::value, hi = u >= 4 ? 4096 : 0;
+    auto dma_pair_piece = [&](auto pe_tag, auto slot_tag, auto u_tag) {
+        constexpr int u = decltype(u_tag)::value, pe = decltype(pe_tag)::value, hi = u >= 4 ? 4096 : 0, slot = decltype(slot_tag)::value;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(wdst_wave + slot * ELEM_BYTES + hi), 16, (int)lane16,
                                                  pair_piece_off[u] + ((pe & 1) * 6 * ELEM_BYTES + (pe >> 1) * 4096), u * 1024 - hi, 0);
     };
-    static_for<0, AHEAD>([&](auto e0) { static_for<0, 6>([&](auto u) { dma_pair_piece(e0, decltype(e0)::value, u); }); });
-    int dsrc = AHEAD * ELEM_BYTES, dslot = AHEAD;         // stream byte offset / ring slot of the next element to request
+    static_for<0, AHEAD>([&](auto e0) { static_for<0, 6>([&](auto u) { dma_pair_piece(e0, e0, u); }); });
 
     f32x16 acc[12];
     u32x4 xa[24];                                        // out-projection: attention-output fragments; MLP: normalised rows
@@ -196,7 +207,14 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     vec8 w[R];                                           // weight fragment ring
     float ga[8], gb[8], gc[8];                           // GELU scratch of the eight values in flight
 
-    int slot = 0;                                        // ring slot of the element the next phase consumes
+    // Ring schedule: a tile consumes ELEMS = 18 NSLOT elements, so every tile starts at ring slot 0 and element e of a tile lies in
+    // slot e % 6 whatever the tile: the slot a phase reads, the next one (tail prefetch) and the one it requests (four ahead) are
+    // constants of the call site.  A fragment read is then one of three lane bases (64 KiB of ds_read offset reach two slots) plus an
+    // immediate; nothing of the ring lives in scalar registers except the stream offset inside the rolled MLP loop.
+    static_assert(ELEMS % NSLOT == 0, "every tile must start at ring slot 0");
+    static_assert(ELEM_BYTES + (NF - 1) * 1024 < 65536, "two slots per lane base must fit the 16-bit ds_read offset");
+    const unsigned ring0 = lds_base + lane16;
+    unsigned b1v = 0;                                    // LDS address of b1 (lane part included) of the chunk the MLP loop trip starts at
     // LDS addresses of the bias tables: lane part + a wave-uniform offset, added where they are used (volatile: kept as loop
     // invariants, the handful of variants beyond the 16-bit instruction offset were spilled around the tile boundary)
     auto bias_addr = [&](unsigned uniform_off) {          // uniform_off + 16 * (lane >> 5)
@@ -211,9 +229,9 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         return __builtin_bit_cast(float, own) + __builtin_bit_cast(float, other);
     };
 
-    // ---- one phase: 24 slots over ring element `slot` (prefetching the head of the next element), MFMA `mf(i, fragment)`,
-    // vector filler `fill(i)`; BQ >= 0: b1 of chunk `bias_chunk` is read INTO hq[BQ] (dead at that point), where the GEMM1 of that
-    // chunk accumulates on top of it a phase later.
+    // ---- one phase: 24 slots over the element in ring slot SLOT (prefetching the head of the next element), MFMA `mf(i, fragment)`,
+    // vector filler `fill(i)`; BQ >= 0: the b1 of a chunk, at b1v + BOFF, is read INTO hq[BQ] (dead at that point), where the GEMM1
+    // of that chunk accumulates on top of it a phase later.
 #ifdef BLOCKS_STAMPS
     unsigned long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long tstart = bstamp();
@@ -221,8 +239,13 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
     // ord_tag / nord_tag: how this / the next phase walks its fragments (ORD_STREAM: GEMM1 k-steps, ORD_TILE: frag_of, ORD_PAIR:
     // pair_frag_of).  dma_tag: the element requested here (four ahead) is out-projection element 0..11 of the pair-major walk, or
     // -1 = the next one of the stream as it lies.  rows_tag: row loads issued in the two phases before this one (below).
-    auto phase = [&](auto head_tag, auto tail_tag, auto bq_tag, int bias_chunk, auto&& mf, auto&& fill, auto cat_tag, auto ord_tag, auto nord_tag,
-                     auto dma_tag, auto rows_tag) {
+    // slot_tag: the ring slot of the element consumed.  boff_tag: byte offset of the b1 read from b1v.  src: stream byte offset of
+    // the element requested (dma_tag = STREAM only).
+    auto phase = [&](auto slot_tag, auto head_tag, auto tail_tag, auto bq_tag, auto boff_tag, auto&& mf, auto&& fill, auto cat_tag, auto ord_tag,
+                     auto nord_tag, auto dma_tag, int src, auto rows_tag) {
+        constexpr int SLOT = decltype(slot_tag)::value, NXT = (SLOT + 1) % NSLOT, BOFF = decltype(boff_tag)::value;
+        constexpr std::integral_constant<int, (SLOT + AHEAD) % NSLOT> DSLOT{};
+        constexpr int CUR_IMM = (SLOT % 2) * ELEM_BYTES, NXT_IMM = (NXT % 2) * ELEM_BYTES;
         constexpr bool HEAD = decltype(head_tag)::value, TAIL = decltype(tail_tag)::value;
         constexpr int ORD = decltype(ord_tag)::value, NORD = decltype(nord_tag)::value, DMA_PE = decltype(dma_tag)::value;
         auto fr = [](int i, int ord) constexpr { return frag_in_order(i, ord); };
@@ -235,25 +258,18 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(12 + decltype(rows_tag)::value) : "memory");
         BST(p1);
         BACC(CAT, p0, p1);
-        const unsigned cur = lds_base + slot * ELEM_BYTES + lane16;
-        const int nslot = slot + 1 == NSLOT ? 0 : slot + 1;
-        const unsigned nxt = lds_base + nslot * ELEM_BYTES + lane16;
-        const int my_dsrc = dsrc, my_dslot = dslot;
-        dsrc = dsrc + ELEM_BYTES == ELEMS * ELEM_BYTES ? 0 : dsrc + ELEM_BYTES;
-        dslot = dslot + 1 == NSLOT ? 0 : dslot + 1;
-        unsigned baddr = 0;                               // b1 of the chunk: + 32 * q
-        if constexpr (decltype(bq_tag)::value >= 0) baddr = bias_addr(B1_OFF + 128 * bias_chunk);
+        const unsigned cur = ring0 + (SLOT / 2) * 2 * ELEM_BYTES, nxt = ring0 + (NXT / 2) * 2 * ELEM_BYTES;
         f32x4 bt0, bt1, bt2, bt3;
-        if constexpr (HEAD) static_for<0, D>([&](auto q) { lds_read_b128<fr(decltype(q)::value, ORD) * 1024>(w[decltype(q)::value % R], cur); });
+        if constexpr (HEAD) static_for<0, D>([&](auto q) { lds_read_b128<CUR_IMM + fr(decltype(q)::value, ORD) * 1024>(w[decltype(q)::value % R], cur); });
         static_for<0, NF>([&](auto it) {
             constexpr int i = decltype(it)::value;
-            if constexpr (i + D < NF) lds_read_b128<fr(i + D, ORD) * 1024>(w[(i + D) % R], cur);
-            else if constexpr (TAIL) lds_read_b128<fr(i + D - NF, NORD) * 1024>(w[(i + D) % R], nxt);
+            if constexpr (i + D < NF) lds_read_b128<CUR_IMM + fr(i + D, ORD) * 1024>(w[(i + D) % R], cur);
+            else if constexpr (TAIL) lds_read_b128<NXT_IMM + fr(i + D - NF, NORD) * 1024>(w[(i + D) % R], nxt);
             if constexpr (BQ >= 0 && i == BIAS_SLOT) {
-                lds_read_b128_acc<0>(bt0, baddr);
-                lds_read_b128_acc<32>(bt1, baddr);
-                lds_read_b128_acc<64>(bt2, baddr);
-                lds_read_b128_acc<96>(bt3, baddr);
+                lds_read_b128_hq<BOFF, 0, BQ>(bt0, b1v);
+                lds_read_b128_hq<BOFF + 32, 1, BQ>(bt1, b1v);
+                lds_read_b128_hq<BOFF + 64, 2, BQ>(bt2, b1v);
+                lds_read_b128_hq<BOFF + 96, 3, BQ>(bt3, b1v);
             }
             // ONE counted wait per two slots: at an even slot fragments i and i + 1 have landed once only the reads behind
             // fragment i + 1 are outstanding (fragments i + 2 .. last issued, plus the four b1 reads where they are younger).
@@ -277,12 +293,11 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
             }
             mf(it, w[i % R]);
             if constexpr (i % 4 == 3) {
-                if constexpr (DMA_PE >= 0) dma_pair_piece(dma_tag, my_dslot, std::integral_constant<int, i / 4>{});
-                else dma_piece(my_dsrc, my_dslot, std::integral_constant<int, i / 4>{});
+                if constexpr (DMA_PE >= 0) dma_pair_piece(dma_tag, DSLOT, std::integral_constant<int, i / 4>{});
+                else dma_piece(src, DSLOT, std::integral_constant<int, i / 4>{});
             }
             fill(it);
         });
-        slot = nslot;
         BST(p2);
         BACC(CAT + 1, p1, p2);
     };
@@ -488,9 +503,11 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
             constexpr int rows = e == 0 ? HEAD_LOADS : e == 1 ? HEAD_LOADS + PAIR_LOADS : e <= 10 ? PAIR_LOADS : 0;
             constexpr std::integral_constant<int, rows> ROWS{};
             constexpr std::integral_constant<int, (e + AHEAD < PJ ? e + AHEAD : -1)> DMA{};
-            if constexpr (e == 0) phase(YES, YES, NOBIAS, 0, mf, fill, C_PROJ, I2, I2, DMA, ROWS);
-            else if constexpr (e == PJ - 1) phase(NO, NO, NOBIAS, 0, mf, fill, C_PROJ, I2, I2, DMA, ROWS);   // no prefetch across LayerNorm2
-            else phase(NO, YES, NOBIAS, 0, mf, fill, C_PROJ, I2, I2, DMA, ROWS);
+            constexpr std::integral_constant<int, e % NSLOT> SLOT{};
+            constexpr int src = (e + AHEAD) * ELEM_BYTES;                     // (elements 12..15: the first of the stream as it lies)
+            if constexpr (e == 0) phase(SLOT, YES, YES, NOBIAS, I0, mf, fill, C_PROJ, I2, I2, DMA, src, ROWS);
+            else if constexpr (e == PJ - 1) phase(SLOT, NO, NO, NOBIAS, I0, mf, fill, C_PROJ, I2, I2, DMA, src, ROWS);   // no prefetch across LayerNorm2
+            else phase(SLOT, NO, YES, NOBIAS, I0, mf, fill, C_PROJ, I2, I2, DMA, src, ROWS);
         });
         BST(q2);
         // ---- LayerNorm2 on the accumulators (+ b_proj first), normalised rows -> xa, then + b2.  Vector-typed arithmetic on
@@ -549,39 +566,53 @@ __global__ __launch_bounds__(256) void block16s_kernel(float* x, const T* attn, 
         BACC(9, q2, q3);
         // ---- b1 of chunk 0 -> hq[0] (behind LayerNorm2: sixteen more registers across it were sixteen spilled ones)
         {
-            const unsigned baddr = bias_addr(B1_OFF);
+            b1v = bias_addr(B1_OFF);
             f32x4 bt[4];
-            static_for<0, 4>([&](auto q) { lds_read_b128_acc<32 * decltype(q)::value>(bt[decltype(q)::value], baddr); });
+            static_for<0, 4>([&](auto q) { lds_read_b128_hq<32 * decltype(q)::value, decltype(q)::value, 0>(bt[decltype(q)::value], b1v); });
             wait_lgkm<0>();
             asm volatile("" : "+a"(bt[0]), "+a"(bt[1]), "+a"(bt[2]), "+a"(bt[3]));     // (only now do the values exist for hipcc)
             static_for<0, 4>([&](auto q) { hq[0][decltype(q)::value] = bt[decltype(q)::value]; });
         }
-        // ---- GEMM1 of chunk 0 (b1 of chunk 1 -> hq[1]), then the first half of its GELU
-        phase(YES, YES, I1, 1, gemm1_mf(I0), no_fill, C_G10, I0, I0, STREAM, ROWS0);
+        // ---- GEMM1 of chunk 0 = element 12, slot 0 (b1 of chunk 1 -> hq[1]), then the first half of its GELU
+        phase(I0, YES, YES, I1, std::integral_constant<int, 128>{}, gemm1_mf(I0), no_fill, C_G10, I0, I0, STREAM, (PJ + AHEAD) * ELEM_BYTES, ROWS0);
         wait_lgkm<0>();
         gelu_now(I0, I0);
         // ---- chunks: A(c) = GEMM1(c + 1) beside the second half of GELU(c); B(c) = GEMM2(c) beside the first half of GELU(c + 1)
-        // (+ b1 of chunk c + 2 into the buffer GELU(c) has just left).  The last four phases of a tile request the first four
-        // out-projection elements of the next one (dma_a / dma_b).
-        auto iter = [&](auto par_tag, auto bias_tag, int c, auto dma_a, auto dma_b) {
-            constexpr int cur = decltype(par_tag)::value, nx = cur ^ 1;
-            phase(NO, YES, NOBIAS, 0, gemm1_mf(std::integral_constant<int, nx>{}), gelu_fill(std::integral_constant<int, cur>{}, I1), C_A, I0, I1, dma_a, ROWS0);
+        // (+ b1 of chunk c + 2 into the buffer GELU(c) has just left).  A(c) consumes element 13 + 2c, B(c) element 14 + 2c: the
+        // slots repeat every three chunks and the buffer parity every two, so chunk c = c0 + j of a six-chunk group starting at c0
+        // (a multiple of six) has everything but its stream offset and its b1 base as constants of j.  The last four phases of a
+        // tile request the first four out-projection elements of the next one (dma_a / dma_b).
+        auto iter = [&](auto j_tag, auto bias_tag, int src_a, auto dma_a, auto dma_b) {
+            constexpr int j = decltype(j_tag)::value, cur = j & 1, nx = cur ^ 1;
+            constexpr std::integral_constant<int, (PJ + 1 + 2 * j) % NSLOT> SA{};
+            constexpr std::integral_constant<int, (PJ + 2 + 2 * j) % NSLOT> SB{};
+            constexpr std::integral_constant<int, 128 * (j + 2)> BOFF{};
+            phase(SA, NO, YES, NOBIAS, I0, gemm1_mf(std::integral_constant<int, nx>{}), gelu_fill(std::integral_constant<int, cur>{}, I1), C_A, I0, I1, dma_a, src_a, ROWS0);
             if constexpr (decltype(bias_tag)::value)
-                phase(NO, YES, std::integral_constant<int, cur>{}, c + 2, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I0, dma_b, ROWS0);
+                phase(SB, NO, YES, std::integral_constant<int, cur>{}, BOFF, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I0, dma_b, src_a + ELEM_BYTES, ROWS0);
             else                                         // chunk 46: the next phase is GEMM2(47)
-                phase(NO, YES, NOBIAS, 0, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I1, dma_b, ROWS0);
+                phase(SB, NO, YES, NOBIAS, I0, gemm2_mf(std::integral_constant<int, cur>{}), gelu_fill(std::integral_constant<int, nx>{}, I0), C_B, I1, I1, dma_b, src_a + ELEM_BYTES, ROWS0);
         };
+        constexpr int GROUP = 6, TRIPS = NCHUNK / GROUP - 1;                 // rolled body = one ring period = 12 phases; chunks 0 .. 41
+        static_assert(GROUP % (NSLOT / 2) == 0 && GROUP % 2 == 0 && (TRIPS + 1) * GROUP == NCHUNK, "the peeled tail below is chunks 42 .. 47");
+        constexpr int SRC0 = (PJ + 1 + AHEAD) * ELEM_BYTES;                  // A(0) requests element 17
+        int msrc = SRC0;
 #pragma unroll 1
-        for (int c = 0; c < NCHUNK - 4; c += 2) {        // chunks 0 .. 43
-            iter(I0, YES, c, STREAM, STREAM);
-            iter(I1, YES, c + 1, STREAM, STREAM);
+        for (int trip = 0; trip < TRIPS; ++trip) {
+            static_for<0, GROUP>([&](auto j) { iter(j, YES, msrc + 2 * decltype(j)::value * ELEM_BYTES, STREAM, STREAM); });
+            msrc += 2 * GROUP * ELEM_BYTES;
+            b1v += 128 * GROUP;
         }
-        iter(I0, YES, NCHUNK - 4, STREAM, STREAM);       // chunk 44
-        iter(I1, YES, NCHUNK - 3, STREAM, I0);           // chunk 45
-        iter(I0, NO, NCHUNK - 2, I1, I2);                // chunk 46
+        constexpr int C0 = TRIPS * GROUP;                // 42: b1v stands at its b1
+        auto src_of = [](int c) constexpr { return SRC0 + 2 * c * ELEM_BYTES; };
+        iter(I0, YES, src_of(C0), STREAM, STREAM);        // chunk 42
+        iter(I1, YES, src_of(C0 + 1), STREAM, STREAM);    // chunk 43
+        iter(I2, YES, src_of(C0 + 2), STREAM, STREAM);    // chunk 44
+        iter(I3, YES, src_of(C0 + 3), STREAM, I0);        // chunk 45: A requests element 107, the last of the tile
+        iter(std::integral_constant<int, 4>{}, NO, 0, I1, I2);            // chunk 46
         wait_lgkm<0>();
         gelu_now(I1, I1);
-        phase(NO, NO, NOBIAS, 0, gemm2_mf(I1), no_fill, C_B, I1, I1, I3, ROWS0); // GEMM2 of chunk 47
+        phase(std::integral_constant<int, (ELEMS - 1) % NSLOT>{}, NO, NO, NOBIAS, I0, gemm2_mf(I1), no_fill, C_B, I1, I1, I3, 0, ROWS0);   // GEMM2 of chunk 47
         // ---- tile boundary: the next block's LayerNorm statistics (they need all twelve tiles), pair 0 out, the next tile's
         // attention rows and pair 0 in.  Pairs 1..5 leave from inside the next out-projection, or behind the loop.
         BST(q4);
