@@ -125,6 +125,37 @@ int mst_attention_cls_probs(const void* qkv, int dtype, int n_seq, int N, int he
 int mst_attention_probs_full(const void* qkv, int dtype, int n_seq, int N, int heads, int head_dim,
                              float* probs, mst_stream_t stream);
 
+/* The kernels and kernel modes that only mst_vit_encode's fused 16-bit pipeline launches, callable on their own (each entry forwards
+ * to the launcher the encoder uses; additive, the ABI version does not change).
+ * mst_attention_ex: mst_attention for the 16-bit dtypes (head_dim 64; anything else returns MST_EINVAL) with the encoder's two options,
+ *   a combination of mst_attention_flags.  MST_ATTN_LOG2Q: q carries head_dim^-0.5 * log2(e) already (one rounding of q, as the
+ *   encoder's QKV epilogue writes it), the kernel takes exp2 of q.k as stored.  MST_ATTN_OUT_BLOCKED: out is written in the 16-bit
+ *   "blocked" layout (mst_block_fused_s below) with heads*64 columns; allocate whole 32-row groups, ceil(n_seq*N / 32) * 32 rows --
+ *   only rows < n_seq*N are written.
+ * mst_attention_cls: the CLS query's attention output alone, out [n_seq, heads*64] in qkv's type (f32 / f16 / bf16, head_dim 64,
+ *   N <= 12000, n_seq <= 65535), and its probabilities fp32 [n_seq, heads, N] where probs is not NULL: what the last block needs under
+ *   mst_vit_weights.prune_last_block.  log2q as MST_ATTN_LOG2Q.
+ * mst_gemm16_blocked: the QKV projection on blocked rows.  C[M, N] = (A . W^T + bias) * (col < scale_cols ? col_scale : 1) with K = 384,
+ *   A_blocked the rows in the 16-bit blocked layout with 384 columns (whole 32-row groups allocated; rows past M are read, never
+ *   stored), W [N, 384] with row stride ldw, C row-major in the operand type.  Only the weights-in-registers kernel reads blocked rows:
+ *   a shape it does not take (N not a multiple of 384 or more 384-column tiles than an XCD has CUs, scale_cols not a multiple of 384
+ *   below N, M below 8192 rows, ldw / ldc not multiples of 8, a pointer not 16-byte aligned) returns MST_EINVAL.
+ * mst_patch_rows16: mst_patch_embed for E = 384 that also writes xn = (x - mean) * rstd (eps 1e-6, no affine) of every token row in
+ *   the 16-bit compute dtype: x fp32 [n, n_prefix+Np, 384], xn the same rows in `dtype` (MST_BF16 / MST_F16); arguments as
+ *   mst_patch_embed. */
+enum mst_attention_flags {
+    MST_ATTN_LOG2Q = 1,
+    MST_ATTN_OUT_BLOCKED = 2
+};
+int mst_attention_ex(const void* qkv, int dtype, int n_seq, int N, int heads, int head_dim, void* out, int flags,
+                     mst_stream_t stream);
+int mst_attention_cls(const void* qkv, int dtype, int n_seq, int N, int heads, void* out, float* probs, int log2q,
+                      mst_stream_t stream);
+int mst_gemm16_blocked(const void* A_blocked, int dtype, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
+                       int64_t M, int N, float col_scale, int scale_cols, mst_stream_t stream);
+int mst_patch_rows16(const void* vol, int in_dtype, int n, int H, int W, const void* wp, int dtype, const float* bias,
+                     const float* prefix, int n_prefix, const float* pos_patch, float* x, void* xn, mst_stream_t stream);
+
 /* Memory-efficient attention for the mixed-precision TRAINING step (FlashAttention-2 form): no [N, N] tensor in the forward or the
  * backward.  Per-slice encoder blocks only: head_dim == 64, no key mask, any N >= 1.
  *   qkv16  [n_seq*N, 3*heads*64], dtype MST_BF16 or MST_F16: q | k | v head-major, as mst_attention; q carries head_dim^-0.5

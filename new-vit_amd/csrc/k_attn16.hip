@@ -161,11 +161,16 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
     __syncthreads();
 
     // FAST mode.  The reference point only exists to keep exp2 inside the range of its type: when the first tile's maxima are small
-    // (|max| <= TH0 in the log2 domain for every query of the wave) the reference stays 0 and the later tiles run WITHOUT the running
-    // maximum (32 v_max + a cross-half swap) and WITHOUT the reference MFMA of each score chain; the tile's own row sum guards the
+    // (|max| <= TH0 in the log2 domain for every query of the wave; fp16: 0 <= max <= TH0, below) the reference stays 0 and the later
+    // tiles run WITHOUT the running maximum (32 v_max + a cross-half swap) and WITHOUT the reference MFMA of each score chain; the tile's own row sum guards the
     // range instead (one compare: sum < GUARD means every p < GUARD), and a tile that fails it is recomputed the classic way and the
     // wave stays classic from there on.  Softmax is invariant to the reference point, so both modes give the same result up to
     // rounding; bf16 has fp32's exponent range (GUARD 2^100), fp16 needs p <= 65504 (GUARD 2^15, TH0 8 as RT).
+    // fp16's entry test is one-sided, 0 <= max <= TH0: P is rounded to the operand type before P.V, and with the reference point ABOVE
+    // a row's maximum by a every p is at most 2^-a -- keys more than 14 - a below the maximum become fp16 subnormals (a first tile with
+    // maxima near -8 lost everything from 6 below them on: 2.2 times the rounding bound of tests/test_encoder_seam_gpu.py, where the
+    // classic loop, whose reference point never lies above the maximum, stays inside it).  A first-tile maximum >= 0 keeps the fixed
+    // reference point at or below the row maximum, as the classic loop's is.
     constexpr float TH0 = std::is_same<T, f16_t>::value ? 8.0f : 60.0f;
     constexpr float GUARD = std::is_same<T, f16_t>::value ? 32768.0f : 1.2676506e30f;
     bool fast = false;                                   // wave-uniform
@@ -251,7 +256,10 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(ATTN_WAVES_
                     const auto sw = __builtin_amdgcn_permlane32_swap(mu, mu, false, false);
                     mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
                 }
-                if (t == 0 && __all(fabsf(mx) <= TH0)) {
+                bool small;                               // this query's first-tile maximum admits FAST mode
+                if constexpr (std::is_same<T, f16_t>::value) small = mx >= 0.f && mx <= TH0;
+                else small = fabsf(mx) <= TH0;
+                if (t == 0 && __all(small)) {
                     fast = true;                          // the reference point stays 0
                 } else if (t == 0 || !__all(mx <= RT)) {   // rare after the first tiles: move the reference point
                     const bool mv = (t == 0) || (mx > RT);

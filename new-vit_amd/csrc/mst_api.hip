@@ -154,6 +154,45 @@ int mst_attention_probs_full(const void* qkv, int dtype, int n_seq, int N, int h
     return launch_probs_full(qkv, dtype, n_seq, N, heads, head_dim, probs, 0, (hipStream_t)stream);
 }
 
+// ---- the kernels and kernel modes that only mst_vit_encode's fused 16-bit pipeline launches, one entry point each: thin forwards to
+// the launchers the encoder calls, so that each can be checked on its own at small shapes (tests/test_encoder_seam_gpu.py)
+int mst_attention_ex(const void* qkv, int dtype, int n_seq, int N, int heads, int head_dim, void* out, int flags, mst_stream_t stream) {
+    MST_CHECK_ARG(qkv && out, "attention_ex: null pointer");
+    MST_CHECK_ARG(head_dim == 64, "attention_ex: head_dim=%d unsupported (64)", head_dim);
+    MST_CHECK_ARG(dtype == MST_BF16 || dtype == MST_F16, "attention_ex: dtype %d (the log2-domain and blocked forms are 16-bit only)", dtype);
+    MST_CHECK_ARG((flags & ~(MST_ATTN_LOG2Q | MST_ATTN_OUT_BLOCKED)) == 0, "attention_ex: unknown flags %d", flags);
+    return launch_attn16(qkv, dtype, n_seq, N, heads, out, (flags & MST_ATTN_LOG2Q) ? 1 : 0, (hipStream_t)stream,
+                         (flags & MST_ATTN_OUT_BLOCKED) ? 1 : 0);
+}
+
+int mst_attention_cls(const void* qkv, int dtype, int n_seq, int N, int heads, void* out, float* probs, int log2q, mst_stream_t stream) {
+    MST_CHECK_ARG(qkv && out, "attention_cls: null pointer");
+    MST_CHECK_ARG(heads > 0, "attention_cls: heads=%d", heads);
+    MST_CHECK_ARG(dtype == MST_F32 || dtype == MST_BF16 || dtype == MST_F16, "attention_cls: bad dtype %d", dtype);
+    return launch_cls_attn(qkv, dtype, n_seq, N, heads, probs, out, log2q ? 1 : 0, (hipStream_t)stream);
+}
+
+int mst_gemm16_blocked(const void* A_blocked, int dtype, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc, int64_t M,
+                       int N, float col_scale, int scale_cols, mst_stream_t stream) {
+    MST_CHECK_ARG(A_blocked && W && C, "gemm16_blocked: null pointer");
+    MST_CHECK_ARG(dtype == MST_BF16 || dtype == MST_F16, "gemm16_blocked: bad operand dtype %d", dtype);
+    const int K = GEMM16_WREG_TILE.bk;
+    gemm_args g{A_blocked, dtype, K, W, ldw, bias, C, dtype, ldc, M, N, K};
+    g.col_scale = col_scale, g.scale_cols = scale_cols, g.s = (hipStream_t)stream;
+    MST_CHECK_ARG(ldw % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)A_blocked & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0,
+                  "gemm16_blocked: ldw / ldc must be multiples of 8 and A, W, C 16-byte aligned");
+    MST_CHECK_ARG(N > 0 && gemm16_wreg_applicable(g),
+                  "gemm16_blocked: M=%lld N=%d scale_cols=%d is no shape of the weights-in-registers kernel, the only one that reads blocked rows",
+                  (long long)M, N, scale_cols);
+    return launch_gemm16_wreg(g, 1);
+}
+
+int mst_patch_rows16(const void* vol, int in_dtype, int n, int H, int W, const void* wp, int dtype, const float* bias, const float* prefix,
+                     int n_prefix, const float* pos_patch, float* x, void* xn, mst_stream_t stream) {
+    MST_CHECK_ARG(vol && wp && bias && prefix && pos_patch && x && xn, "patch_rows16: null pointer");
+    return launch_patch_rows16(vol, in_dtype, n, H, W, wp, dtype, bias, prefix, n_prefix, pos_patch, x, xn, (hipStream_t)stream);
+}
+
 size_t mst_attention_train_bwd_workspace_bytes(int n_seq, int N, int heads, int head_dim) {
     return head_dim == 64 ? attn_train_workspace_bytes(n_seq, N, heads) : 0;
 }

@@ -66,6 +66,10 @@ SIGNATURES = {
     "mst_gemm_fp8": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _f, _vp, _i, _i64, _i64, _i, _i, _i, _vp, _f, _i, _vp, _vp]),
     "mst_layernorm_fp8": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i, _f, _vp, _vp]),
     "mst_attention": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mst_attention_ex": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "mst_attention_cls": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mst_gemm16_blocked": (_i, [_vp, _i, _vp, _i64, _vp, _vp, _i64, _i64, _i, _f, _i, _vp]),
+    "mst_patch_rows16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mst_attention_cls_probs": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_attention_probs_full": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_attention_train_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -318,11 +322,124 @@ def layernorm_fp8(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional
     return out
 
 
-def attention(qkv: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int = 64) -> torch.Tensor:
-    _dev(qkv, "attention")
-    out = torch.empty((n_seq * N, heads * head_dim), dtype=qkv.dtype, device=qkv.device)
-    _check(load().mst_attention(ptr(qkv), dt_of(qkv), n_seq, N, heads, head_dim, ptr(out), stream_of(qkv)), "mst_attention")
+ATTN_LOG2Q, ATTN_OUT_BLOCKED = 1, 2      # mst_attention_flags
+
+
+def _operand(t, what: str, name: str, dtypes, shape=None):
+    """A tensor of one of `dtypes` and, where given, of `shape`: the first half of what every wrapper of the encoder's seam kernels checks
+    before the library is reached (_resident is the second: types and shapes are refused first, wherever the tensors live)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a tensor")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{what}: {name} is {t.dtype} ({', '.join(str(d).replace('torch.', '') for d in dtypes)})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {list(shape)}, got {list(t.shape)}")
+
+
+def _resident(what: str, **tensors):
+    """Every tensor (None skipped) contiguous and on one HIP device."""
+    first = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} must live on a HIP device (got {t.device}); the MST kernels have no CPU path")
+        first = t if first is None else first
+        if t.device != first.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, not on {first.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+
+
+_T16 = (torch.bfloat16, torch.float16)
+
+
+def attention(qkv: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int = 64, *, log2q: bool = False, out_blocked: bool = False,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mst_attention.  log2q / out_blocked / out given: mst_attention_ex, the 16-bit kernel as mst_vit_encode launches it -- log2q: q is
+    pre-multiplied by head_dim^-0.5 * log2 e; out_blocked: the result comes back in the 16-bit blocked layout, [ceil(n_seq*N / 32) * 32,
+    heads*64] (decode with from_blocked16; rows past n_seq*N are not written).  out: the buffer to write, at least that many rows (more
+    are allowed: tests put guard rows behind it); it is returned as given."""
+    if not (log2q or out_blocked or out is not None):
+        _dev(qkv, "attention")
+        out = torch.empty((n_seq * N, heads * head_dim), dtype=qkv.dtype, device=qkv.device)
+        _check(load().mst_attention(ptr(qkv), dt_of(qkv), n_seq, N, heads, head_dim, ptr(out), stream_of(qkv)), "mst_attention")
+        return out
+    if min(n_seq, N, heads) < 1 or head_dim != 64:
+        raise ValueError(f"attention: n_seq={n_seq} N={N} heads={heads} head_dim={head_dim} (positive sizes, head_dim 64)")
+    _operand(qkv, "attention", "qkv", _T16, (n_seq * N, 3 * heads * 64))
+    rows = (n_seq * N + 31) // 32 * 32 if out_blocked else n_seq * N
+    if out is not None:
+        _operand(out, "attention", "out", (qkv.dtype,))
+        if out.dim() != 2 or out.shape[1] != heads * 64 or out.shape[0] < rows:
+            raise ValueError(f"attention: out must be [>= {rows}, {heads * 64}], got {list(out.shape)}")
+    _resident("attention", qkv=qkv, out=out)
+    if out is None:
+        out = torch.empty((rows, heads * 64), dtype=qkv.dtype, device=qkv.device)
+    flags = (ATTN_LOG2Q if log2q else 0) | (ATTN_OUT_BLOCKED if out_blocked else 0)
+    _check(load().mst_attention_ex(ptr(qkv), dt_of(qkv), n_seq, N, heads, 64, ptr(out), flags, stream_of(qkv)), "mst_attention_ex")
     return out
+
+
+def attention_cls(qkv: torch.Tensor, n_seq: int, N: int, heads: int, *, log2q: bool = False, probs: bool = True):
+    """mst_attention_cls: (out [n_seq, heads*64] in qkv's type, probs fp32 [n_seq, heads, N] or None) of the CLS query (row 0 of every
+    sequence); qkv fp32 / fp16 / bf16, head_dim 64."""
+    if min(n_seq, N, heads) < 1:
+        raise ValueError(f"attention_cls: n_seq={n_seq} N={N} heads={heads}")
+    _operand(qkv, "attention_cls", "qkv", (torch.float32,) + _T16, (n_seq * N, 3 * heads * 64))
+    _resident("attention_cls", qkv=qkv)
+    out = torch.empty((n_seq, heads * 64), dtype=qkv.dtype, device=qkv.device)
+    pr = torch.empty((n_seq, heads, N), dtype=torch.float32, device=qkv.device) if probs else None
+    _check(load().mst_attention_cls(ptr(qkv), dt_of(qkv), n_seq, N, heads, ptr(out), ptr(pr), 1 if log2q else 0, stream_of(qkv)),
+           "mst_attention_cls")
+    return out, pr
+
+
+def gemm_blocked(a_blocked: torch.Tensor, M: int, w: torch.Tensor, bias: Optional[torch.Tensor], *, col_scale: float = 1.0,
+                 scale_cols: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mst_gemm16_blocked: the first M rows of a_blocked (16-bit blocked layout, [>= ceil(M / 32) * 32, 384]) times w [N, 384]^T + bias,
+    columns below scale_cols times col_scale -> row-major [M, N] in the operand type.  Raises where the weights-in-registers kernel
+    does not take the shape (there is no other kernel that reads blocked rows)."""
+    _operand(a_blocked, "gemm_blocked", "a_blocked", _T16)
+    if a_blocked.dim() != 2 or a_blocked.shape[1] != 384 or a_blocked.shape[0] % 32 or not 0 < M <= a_blocked.shape[0]:
+        raise ValueError(f"gemm_blocked: a_blocked must be whole 32-row groups [>= M, 384] with M = {M} > 0, got {list(a_blocked.shape)}")
+    _operand(w, "gemm_blocked", "w", (a_blocked.dtype,))
+    if w.dim() != 2 or w.shape[1] != 384:
+        raise ValueError(f"gemm_blocked: w must be [N, 384], got {list(w.shape)}")
+    N = w.shape[0]
+    if bias is not None:
+        _operand(bias, "gemm_blocked", "bias", (torch.float32,), (N,))
+    if out is not None:
+        _operand(out, "gemm_blocked", "out", (a_blocked.dtype,), (M, N))
+    _resident("gemm_blocked", a_blocked=a_blocked, w=w, bias=bias, out=out)
+    if out is None:
+        out = torch.empty((M, N), dtype=a_blocked.dtype, device=a_blocked.device)
+    _check(load().mst_gemm16_blocked(ptr(a_blocked), dt_of(a_blocked), ptr(w), 384, ptr(bias), ptr(out), N, M, N, col_scale, scale_cols,
+                                     stream_of(a_blocked)), "mst_gemm16_blocked")
+    return out
+
+
+def patch_rows16(vol: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, prefix: torch.Tensor, pos_patch: torch.Tensor):
+    """mst_patch_rows16: patch_embed for E = 384 that also writes the plain LayerNorm of every row -> (x fp32 [n, N, 384], xn [n, N, 384]
+    in wp's 16-bit type).  vol [n, H, W] fp32 / fp16 / bf16, wp [384, 224] bf16 / fp16, bias [384], prefix [1+R, 384], pos_patch [Np, 384]."""
+    _operand(vol, "patch_rows16", "vol", (torch.float32,) + _T16)
+    if vol.dim() != 3 or vol.shape[1] % 14 or vol.shape[2] % 14 or 0 in vol.shape:
+        raise ValueError(f"patch_rows16: vol must be [n, H, W] with H and W multiples of 14, got {list(vol.shape)}")
+    n, H, W = vol.shape
+    Np = (H // 14) * (W // 14)
+    _operand(wp, "patch_rows16", "wp", _T16, (384, 224))
+    _operand(bias, "patch_rows16", "bias", (torch.float32,), (384,))
+    _operand(prefix, "patch_rows16", "prefix", (torch.float32,))
+    if prefix.dim() != 2 or prefix.shape[0] < 1 or prefix.shape[1] != 384:
+        raise ValueError(f"patch_rows16: prefix must be [1+R, 384], got {list(prefix.shape)}")
+    _operand(pos_patch, "patch_rows16", "pos_patch", (torch.float32,), (Np, 384))
+    _resident("patch_rows16", vol=vol, wp=wp, bias=bias, prefix=prefix, pos_patch=pos_patch)
+    n_prefix = prefix.shape[0]
+    x = torch.empty((n, n_prefix + Np, 384), dtype=torch.float32, device=vol.device)
+    xn = torch.empty((n, n_prefix + Np, 384), dtype=wp.dtype, device=vol.device)
+    _check(load().mst_patch_rows16(ptr(vol), dt_of(vol), n, H, W, ptr(wp), dt_of(wp), ptr(bias), ptr(prefix), n_prefix, ptr(pos_patch),
+                                   ptr(x), ptr(xn), stream_of(vol)), "mst_patch_rows16")
+    return x, xn
 
 
 def attention_cls_probs(qkv: torch.Tensor, n_seq: int, N: int, heads: int, head_dim: int = 64) -> torch.Tensor:

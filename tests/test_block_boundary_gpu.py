@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from mst import synth
+from seam_ref import block_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -58,21 +59,7 @@ def operands_and_reference(dt, M, weights):
     if _case.get("key") != (dt, M):
         x = rnd((M, E), 60, 1.5) + 0.3
         att = rnd((M, E), 61, 1.0).to(DT[dt])
-        wp, bp, w1, b1, w2, b2, g, be = (w.double() for w in weights)
-        outs, norms, scale = [], [], 0.0
-        for lo in range(0, M, 16384):       # row chunks bound the memory of the hidden layer
-            xd, ad = x[lo:lo + 16384].double(), att[lo:lo + 16384].double()
-            proj = ad @ wp.t() + bp
-            xmid = xd + proj
-            h = torch.nn.functional.layer_norm(xmid, (E,), g, be, 1e-6)
-            h = h @ w1.t() + b1
-            h = 0.5 * h * (1 + torch.erf(h / math.sqrt(2)))
-            y = h @ w2.t() + b2
-            ref = xmid + y
-            scale = max(scale, float(y.abs().max()), float(proj.abs().max()))
-            outs.append(ref)
-            norms.append(torch.nn.functional.layer_norm(ref, (E,)))
-        _case.update(key=(dt, M), val=(x, att, torch.cat(outs), torch.cat(norms), scale))
+        _case.update(key=(dt, M), val=(x, att, *block_reference(x, att, weights)))   # the arithmetic: tests/seam_ref.py (the chain replay of test_encoder_seam_gpu.py shares it)
     return _case["val"]
 
 
