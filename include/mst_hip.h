@@ -312,7 +312,7 @@ int mst_slices2rgb(const void* vol, int dtype, int B, int D, int H, int W, void*
  *     n(R)      = 32((R>>4)>>1) + 8((R&15)>>2) + 4((R>>4)&1) + (R&3)
  *     phys(c,j) = j<4 ? 4c+j : 16+4c+(j-4)
  *   W1f = fc1_w * ln2_w (columns);  b1f (fp32, 1536+32 padded) = fc1_b + fc1_w . ln2_b;  b2 = fc2 bias.
- * (new-vit_amd/mst/models/dino.py::_pack_mlp builds it.) */
+ * (mst.hip.pack_mlp builds it.) */
 int mst_mlp_fused(float* x, void* xn_out, int dtype, const void* wpack, const float* b1f, const float* b2f,
                   int64_t M, int E, float eps, mst_stream_t stream);
 
@@ -551,16 +551,18 @@ typedef struct mst_vit_layer {
     const void* fc1_w;  const float* fc1_b;       /* mlp.py:28  [4E,E] */
     const void* fc2_w;  const float* fc2_b;       /* mlp.py:30  [E,4E] */
     const float* ls2;
-    /* Optional fused-LayerNorm form (16-bit modes, E = 384).  When mlp_pack != NULL for every layer the
-     * encoder runs  normalise -> QKV(qkv_wf, qkv_bf) -> attention -> proj -> mst_mlp_fused  per block:
-     *   qkv_wf = qkv_w * ln1_w (columns), qkv_bf = qkv_b + qkv_w . ln1_b            (norm1 folded)
-     *   mlp_pack / fc1_bf / fc2_bf: see mst_mlp_fused                        (norm2 and ls2 folded) */
+    /* Optional fused-LayerNorm form (16-bit modes, E = 384, calls of MST_FUSED_MIN_TOKENS tokens and more): the encoder runs
+     * normalise -> QKV(qkv_wf, qkv_bf) -> attention -> one of three fused tails, the first in the order below whose fields are
+     * non-NULL on EVERY layer; with none complete it runs the unfused kernels on the fields above.
+     *   every fused tail: qkv_wf = qkv_w * ln1_w (columns), qkv_bf = qkv_b + qkv_w . ln1_b             (norm1 folded)
+     *                     fc1_bf = fc1_b + fc1_w . ln2_b, fc2_bf = ls2 * fc2_b                   (norm2 and ls2 folded)
+     *   single-role block (mst_block_fused_s, ABI 300): block_seq, proj_bf; fc1_bf of [1536]
+     *   producer/consumer block (mst_block_fused):      mlp_pack, proj_pack, proj_bf; fc1_bf of [1536+32]
+     *   proj, then the fused MLP (mst_mlp_fused):       mlp_pack; fc1_bf of [1536+32] */
     const void* qkv_wf; const float* qkv_bf;
-    const void* mlp_pack; const float* fc1_bf; const float* fc2_bf;
-    /* with proj_pack / proj_bf (see mst_block_fused) also present for every layer the out-projection joins that launch */
-    const void* proj_pack; const float* proj_bf;
-    /* block_seq (see mst_block_fused_s) with fc1_bf / proj_bf / fc2_bf: the single-role launch is taken instead (ABI 300) */
-    const void* block_seq;
+    const void* mlp_pack; const float* fc1_bf; const float* fc2_bf;   /* mlp_pack: the last two tails */
+    const void* proj_pack; const float* proj_bf;                      /* proj_pack: the producer/consumer block; proj_bf: both blocks */
+    const void* block_seq;                                            /* the single-role block */
     /* Optional FP8 form (mst_vit_weights.fp8_linear): the four block weights as e4m3 bytes, same [out,in] layout, with their
      * per-tensor scales w8_scale[] = max|W|/448 in the order qkv, proj, fc1, fc2 (see mst_gemm_fp8) */
     const void* qkv_w8; const void* proj_w8; const void* fc1_w8; const void* fc2_w8;

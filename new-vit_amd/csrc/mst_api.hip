@@ -600,15 +600,17 @@ static vit_plan vit_resolve(const mst_vit_weights* w, int64_t tokens) {
     // persistent kernel of 128-token tiles: below ~one tile per CU it leaves CUs idle (c1 shape, 4k tokens: 90 us per
     // launch on 33 CUs against ~45 us for LN + fc1 + fc2 as three well-filled launches), so small calls take the unfused path.
     static const int64_t fused_min_tokens = getenv("MST_FUSED_MIN_TOKENS") ? atoll(getenv("MST_FUSED_MIN_TOKENS")) : 12288;   // measured crossover (tools/bench_crossover.py): 8k tokens unfused 1.57 vs 1.92 ms, 16k fused 2.34 vs 2.62
-    bool fused = w->compute_dtype != MST_F32 && w->embed_dim == 384 && tokens >= fused_min_tokens, folded = true, single_role = true;
+    // Every fused tail needs the folded QKV and the folded MLP biases on every layer; beyond those each needs exactly what it dereferences.
+    bool fused = w->compute_dtype != MST_F32 && w->embed_dim == 384 && tokens >= fused_min_tokens, single = true, roles = true, mlp = true;
     for (int l = 0; l < w->depth && fused; ++l) {
         const mst_vit_layer* L = &w->layers[l];
-        fused = L->mlp_pack && L->fc1_bf && L->fc2_bf && L->qkv_wf && L->qkv_bf;
-        folded = folded && L->proj_pack && L->proj_bf;
-        single_role = single_role && L->block_seq;
+        fused = L->qkv_wf && L->qkv_bf && L->fc1_bf && L->fc2_bf;
+        single = single && L->block_seq && L->proj_bf;
+        roles = roles && L->mlp_pack && L->proj_pack && L->proj_bf;
+        mlp = mlp && L->mlp_pack;
     }
-    if (!fused) return {TAIL_UNFUSED, false, may_prune};
-    return {!folded ? TAIL_MLP_FUSED : single_role ? TAIL_BLOCK_SINGLE : TAIL_BLOCK_ROLES, true, may_prune};
+    if (!fused || !(single || roles || mlp)) return {TAIL_UNFUSED, false, may_prune};
+    return {single ? TAIL_BLOCK_SINGLE : roles ? TAIL_BLOCK_ROLES : TAIL_MLP_FUSED, true, may_prune};
 }
 
 // One encoder call: what every launch needs, and the pieces of a block.  c, Mc and blocked belong to the current chunk.

@@ -40,6 +40,7 @@ import torch.nn as nn
 from .base_model import BasicClassifier
 from .. import hip, train_mode
 from ..parallel import SliceSharding
+from .prepared import Prepared, bind_slice_fusion, cached_workspace, run_slice_fusion
 
 PATCH = 14
 _VIT_SIZES = {  # reference: extern/dinov2/vision_transformer.py:340-395
@@ -233,6 +234,46 @@ def _check_fp8_supported(embed_dim: int, ffn_layer: str):
         raise NotImplementedError(f"compute_dtype='fp8' stops at embed_dim 1024 (mst_layernorm_fp8); embed_dim={embed_dim}: use bf16, fp16 or fp32")
 
 
+def _fill_layer(L: hip.VitLayer, b: _Block, put, tdt: torch.dtype, form: str) -> int:
+    """One encoder block's weights -> L (mst_vit_layer, include/mst_hip.h).  ``put(t, dtype=fp32)`` hands back t's device image of
+    that type and keeps it alive.  form: 'plain' (the unfused kernels read these fields, in every form but 'swiglu' whose fc* fields
+    are its own) | 'folded' (adds what the fused pipeline reads) | 'fp8' (adds the e4m3 matrices) | 'swiglu'.  Returns the hidden
+    width of the FFN image."""
+    P = hip.ptr
+    attn, mlp = b.attn, b.mlp
+    ls1 = b.ls1.gamma.detach() if hasattr(b, "ls1") else None
+    ls2 = b.ls2.gamma.detach() if hasattr(b, "ls2") else None
+    L.ln1_w, L.ln1_b = P(put(b.norm1.weight)), P(put(b.norm1.bias))
+    L.qkv_w, L.qkv_b = P(put(attn.qkv.weight, tdt)), P(put(attn.qkv.bias))
+    L.proj_w, L.proj_b = P(put(attn.proj.weight, tdt)), P(put(attn.proj.bias))
+    L.ls1 = None if ls1 is None else P(put(ls1))
+    L.ln2_w, L.ln2_b = P(put(b.norm2.weight)), P(put(b.norm2.bias))
+    L.ls2 = None if ls2 is None else P(put(ls2))
+    if form == "swiglu":
+        # SwiGLUFFNFused: w12 as the row-paired image the MST_EPI_BIAS_SWIGLU epilogue reads, w3 zero-padded to its width
+        w12p, b12p, w3p = (put(t, t.dtype) for t in hip.pack_swiglu(mlp.w12.weight.detach(), mlp.w12.bias.detach(), mlp.w3.weight.detach(), tdt))
+        L.fc1_w, L.fc1_b = P(w12p), P(b12p)
+        L.fc2_w, L.fc2_b = P(w3p), P(put(mlp.w3.bias))
+        return w3p.shape[1]
+    L.fc1_w, L.fc1_b = P(put(mlp.fc1.weight, tdt)), P(put(mlp.fc1.bias))
+    L.fc2_w, L.fc2_b = P(put(mlp.fc2.weight, tdt)), P(put(mlp.fc2.bias))
+    if form == "fp8":
+        # BASELINE configs[4]: the four block matrices as OCP e4m3 bytes + per-tensor scales (mst_gemm_fp8)
+        for j, (name, lin) in enumerate((("qkv_w8", attn.qkv), ("proj_w8", attn.proj), ("fc1_w8", mlp.fc1), ("fc2_w8", mlp.fc2))):
+            q8, L.w8_scale[j] = hip.quantize_weight_fp8(lin.weight.detach())
+            setattr(L, name, P(put(q8, q8.dtype)))
+    elif form == "folded":
+        g1, be1, wq = b.norm1.weight.detach().float(), b.norm1.bias.detach().float(), attn.qkv.weight.detach().float()
+        L.qkv_wf = P(put(wq * g1[None, :], tdt))
+        L.qkv_bf = P(put(attn.qkv.bias.detach().float() + (wq * be1[None, :]).sum(dim=1)))   # (no vendor BLAS: an elementwise product + row sums, once per weight version)
+        # the one image the encoder's plan reads (TAIL_BLOCK_SINGLE), with the folded biases that belong to it
+        seq, b1f, pbf, b2f = hip.pack_block_seq(attn.proj.weight.detach(), attn.proj.bias.detach(), ls1, mlp.fc1.weight.detach(),
+                                                mlp.fc1.bias.detach(), mlp.fc2.weight.detach(), mlp.fc2.bias.detach(),
+                                                b.norm2.weight.detach(), b.norm2.bias.detach(), ls2, tdt)
+        L.block_seq, L.fc1_bf, L.proj_bf, L.fc2_bf = P(put(seq, tdt)), P(put(b1f)), P(put(pbf)), P(put(b2f))
+    return mlp.fc1.weight.shape[0]
+
+
 # ------------------------------------------------------------------------------------------------
 class DinoV2ClassifierSlice(BasicClassifier):
     def __init__(self, in_ch, out_ch, spatial_dims=2, pretrained=True, save_attn=False,
@@ -318,24 +359,16 @@ class DinoV2ClassifierSlice(BasicClassifier):
             pass
         self.linear = _lin(out_ch, emb_ch) if enable_linear else nn.Identity()
 
-        self._prep = None       # prepared device-side weights (struct + tensors kept alive)
-        self._prep_sig = None
-        self._param_epoch = 0
-        self._sentinels = None
+        self._prepared = Prepared()      # device-side weight images (structs + the tensors they point into)
         self.profiler: Optional[hip.Profiler] = None   # bench only: set to a hip.Profiler to time this model's launches
         self._cls_last = None
         self._local = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate_prepared())
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate())
         self._pos_cache = {}
         self._ws = {}
         self._sharding: Optional[SliceSharding] = None
         self._warned_grad = False
         self._register_load_state_dict_pre_hook(self._remap_state_dict)
-
-    def _invalidate_prepared(self):
-        self._param_epoch = getattr(self, "_param_epoch", 0) + 1
-        self._prep = self._prep_sig = self._sentinels = None
-        self._graphs = {}                               # captured graphs hold pointers into the prepared weight images
 
     # ---- checkpoint compatibility ---------------------------------------------------------------
     def _remap_state_dict(self, state_dict, prefix, *args):
@@ -398,125 +431,62 @@ class DinoV2ClassifierSlice(BasicClassifier):
         self._fp8_amax = self._fp8_calib = None
         self._fp8_collect = False
 
-    def _signature(self, full: bool):
-        """Identity of everything ``_prepare`` folded into device-side weight images.  With grad enabled (optimiser steps rewrite
-        parameters in place) every parameter's (data_ptr, _version) pair is part of the signature.  With grad disabled the walk
-        is ONE pass over a cached parameter list summing ``_version`` and folding ``data_ptr`` (~15 us for ~200 tensors: a tuple of
-        200 pairs cost ~50 us, 5 % of the 1.1 ms c1 forward): any in-place edit of ANY parameter -- weight surgery on one block,
-        ``model.slice_fusion.load_state_dict(...)``, a partial fine-tune -- changes it (four sentinel tensors did not)."""
-        head = (self.compute_dtype_name, None if self._fp8_amax is None else (self._fp8_amax.data_ptr(), self._fp8_amax._version),
-                self._fp8_collect, self._param_epoch)
-        if self._sentinels is None:
-            self._sentinels = list(self.parameters())       # rebuilt by _invalidate_prepared (``_apply`` / load_state_dict replace tensors)
-        ps = self._sentinels
-        if full:
-            return head + tuple((q.data_ptr(), q._version) for q in ps)
-        acc = 0
-        for q in ps:
-            acc = (acc * 1000003 + q._version + q.data_ptr()) & 0xFFFFFFFFFFFFFFFF
-        return head + (acc, len(ps))
-
     def invalidate(self):
         """Public: drop every prepared device-side weight image (call after editing parameters through ``.data`` views that bypass
         the version counters)."""
-        self._invalidate_prepared()
+        self._prepared.invalidate()
+        self._graphs = {}                               # captured graphs hold pointers into the prepared weight images
 
     def _apply(self, fn, *args, **kwargs):
-        self._invalidate_prepared()
+        self.invalidate()
         return super()._apply(fn, *args, **kwargs)
 
     def _prepare(self):
-        full = torch.is_grad_enabled()
-        sig = self._signature(full)
-        if self._prep is not None and sig == self._prep_sig[full]:
-            return self._prep
+        """The device-side weight images, rebuilt when ANY parameter was edited in place or replaced -- an optimiser step, weight surgery
+        on one block, ``model.slice_fusion.load_state_dict(...)``, a partial fine-tune (four sentinel tensors missed those) --
+        or when the compute type or the fp8 scale table changed."""
+        amax = self._fp8_amax
+        return self._prepared.get(self, "weights", self._build_weights, self.compute_dtype_name,
+                                  None if amax is None else (amax.data_ptr(), amax._version), self._fp8_collect)
+
+    def _build_weights(self):
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError(f"DinoV2ClassifierSlice runs on an MI355X only: parameters are on {dev}; call .to('cuda'). "
                                "There is no CPU fallback.")
+        keep: List[torch.Tensor] = []                   # every tensor a struct below points into
+
+        def put(t, dtype=torch.float32):
+            t = t.detach().to(device=dev, dtype=dtype).contiguous()
+            keep.append(t)
+            return t
+
+        with torch.no_grad():
+            vit, layers, pos, cdt = self._encoder_weights(put)
+            fw = self._fusion_weights(put)
+        self._pos_cache = {}                            # resampled from `pos`
+        return dict(vit=vit, layers=layers, fusion=fw, keep=keep, pos=pos, cdt=cdt)
+
+    def _encoder_weights(self, put):
+        enc = self.encoder
+        E, R = enc.embed_dim, enc.num_register_tokens
         cdt = hip.DT_NAMES[self.compute_dtype_name]
         tdt = hip.TORCH_DT[cdt]
         fp8 = self.compute_dtype_name in hip.FP8_NAMES
-        keep: List[torch.Tensor] = []
-
-        def f32(t):
-            t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            keep.append(t)
-            return t
-
-        def cmp(t):
-            t = t.detach().to(device=dev, dtype=tdt).contiguous()
-            keep.append(t)
-            return t
-
-        enc = self.encoder
-        E, R = enc.embed_dim, enc.num_register_tokens
         swiglu = getattr(enc, "ffn_layer", "mlp") == "swiglufused"
         if fp8:
             _check_fp8_supported(E, "swiglufused" if swiglu else "mlp")
-        with torch.no_grad():
-            w = enc.patch_embed.proj.weight.detach().to(dev, torch.float32)          # [E,3,14,14]
-            wp = torch.zeros(E, PATCH, 16, device=dev, dtype=torch.float32)
-            wp[:, :, :PATCH] = w.sum(dim=1)                                          # RGB copies are identical
-            wp = cmp(wp.reshape(E, PATCH * 16))
-            pos = f32(enc.pos_embed[0])                                              # [1+M*M, E]
-            prefix = (enc.cls_token.detach().to(dev, torch.float32)[0] + pos[:1])
-            if R:
-                prefix = torch.cat([prefix, enc.register_tokens.detach().to(dev, torch.float32)[0]], dim=0)
-            prefix = f32(prefix)
+        # 'folded': the fused-LayerNorm form of 16-bit ViT-S -- norm1 folded into QKV, out-projection + norm2 + MLP as one packed stream
+        form = "swiglu" if swiglu else "fp8" if fp8 else "folded" if (cdt != hip.F32 and E == 384) else "plain"
+        wp = torch.zeros(E, PATCH, 16, device=self.device, dtype=torch.float32)
+        wp[:, :, :PATCH] = enc.patch_embed.proj.weight.detach().float().sum(dim=1)      # [E,3,14,14]: RGB copies are identical
+        pos = put(enc.pos_embed[0])                                                  # [1+M*M, E]
+        prefix = enc.cls_token.detach().float()[0] + pos[:1]
+        if R:
+            prefix = torch.cat([prefix, enc.register_tokens.detach().float()[0]], dim=0)
         layers = (hip.VitLayer * enc.depth)()
-        for i, b in enumerate(enc.block_list()):
-            L = layers[i]
-            L.ln1_w, L.ln1_b = hip.ptr(f32(b.norm1.weight)), hip.ptr(f32(b.norm1.bias))
-            L.qkv_w, L.qkv_b = hip.ptr(cmp(b.attn.qkv.weight)), hip.ptr(f32(b.attn.qkv.bias))
-            L.proj_w, L.proj_b = hip.ptr(cmp(b.attn.proj.weight)), hip.ptr(f32(b.attn.proj.bias))
-            L.ls1 = hip.ptr(f32(b.ls1.gamma)) if hasattr(b, "ls1") else None
-            L.ln2_w, L.ln2_b = hip.ptr(f32(b.norm2.weight)), hip.ptr(f32(b.norm2.bias))
-            L.ls2 = hip.ptr(f32(b.ls2.gamma)) if hasattr(b, "ls2") else None
-            if swiglu:
-                # SwiGLUFFNFused: w12 as the row-paired image the MST_EPI_BIAS_SWIGLU epilogue reads, w3 zero-padded to its width
-                with torch.no_grad():
-                    w12p, b12p, w3p = hip.pack_swiglu(b.mlp.w12.weight.detach().to(dev), b.mlp.w12.bias.detach().to(dev),
-                                                      b.mlp.w3.weight.detach().to(dev), tdt)
-                keep.extend([w12p, b12p, w3p])
-                L.fc1_w, L.fc1_b = hip.ptr(w12p), hip.ptr(b12p)
-                L.fc2_w, L.fc2_b = hip.ptr(w3p), hip.ptr(f32(b.mlp.w3.bias))
-                ffn_hidden = w3p.shape[1]
-                continue
-            L.fc1_w, L.fc1_b = hip.ptr(cmp(b.mlp.fc1.weight)), hip.ptr(f32(b.mlp.fc1.bias))
-            L.fc2_w, L.fc2_b = hip.ptr(cmp(b.mlp.fc2.weight)), hip.ptr(f32(b.mlp.fc2.bias))
-            if fp8:
-                # BASELINE configs[4]: the four block matrices as OCP e4m3 bytes + per-tensor scales (mst_gemm_fp8)
-                for j, (name, lin) in enumerate((("qkv_w8", b.attn.qkv), ("proj_w8", b.attn.proj),
-                                                 ("fc1_w8", b.mlp.fc1), ("fc2_w8", b.mlp.fc2))):
-                    q8, sc = hip.quantize_weight_fp8(lin.weight.to(dev))
-                    keep.append(q8)
-                    setattr(L, name, hip.ptr(q8))
-                    L.w8_scale[j] = sc
-                continue
-            if cdt != hip.F32 and E == 384:
-                # fused-LayerNorm form: norm1 folded into QKV, norm2 folded into the packed MLP (mst_mlp_fused)
-                with torch.no_grad():
-                    g1 = b.norm1.weight.detach().to(dev, torch.float32)
-                    be1 = b.norm1.bias.detach().to(dev, torch.float32)
-                    wq = b.attn.qkv.weight.detach().to(dev, torch.float32)
-                    L.qkv_wf = hip.ptr(cmp(wq * g1[None, :]))
-                    L.qkv_bf = hip.ptr(f32(b.attn.qkv.bias.detach().to(dev, torch.float32) + (wq * be1[None, :]).sum(dim=1)))   # (no vendor BLAS: an elementwise product + row sums, once per weight version)
-                    ls = b.ls2.gamma.detach().to(dev) if hasattr(b, "ls2") else None
-                    wpack, b1p, b2p = hip.pack_mlp(b.mlp.fc1.weight.detach().to(dev), b.mlp.fc1.bias.detach().to(dev),
-                                                   b.mlp.fc2.weight.detach().to(dev), b.mlp.fc2.bias.detach().to(dev),
-                                                   b.norm2.weight.detach().to(dev), b.norm2.bias.detach().to(dev), ls, tdt)
-                    ppack, pbf = hip.pack_proj(b.attn.proj.weight.detach().to(dev), b.attn.proj.bias.detach().to(dev),
-                                               b.ls1.gamma.detach().to(dev) if hasattr(b, "ls1") else None, tdt)
-                    bseq, _, _, _ = hip.pack_block_seq(b.attn.proj.weight.detach().to(dev), b.attn.proj.bias.detach().to(dev),
-                                                       b.ls1.gamma.detach().to(dev) if hasattr(b, "ls1") else None,
-                                                       b.mlp.fc1.weight.detach().to(dev), b.mlp.fc1.bias.detach().to(dev),
-                                                       b.mlp.fc2.weight.detach().to(dev), b.mlp.fc2.bias.detach().to(dev),
-                                                       b.norm2.weight.detach().to(dev), b.norm2.bias.detach().to(dev), ls, tdt)
-                    keep.extend([wpack, b1p, b2p, ppack, pbf, bseq])
-                    L.mlp_pack, L.fc1_bf, L.fc2_bf = hip.ptr(wpack), hip.ptr(b1p), hip.ptr(b2p)
-                    L.proj_pack, L.proj_bf = hip.ptr(ppack), hip.ptr(pbf)
-                    L.block_seq = hip.ptr(bseq)
+        for L, b in zip(layers, enc.block_list()):
+            ffn_hidden = _fill_layer(L, b, put, tdt, form)
         vit = hip.VitWeights()
         vit.embed_dim, vit.depth, vit.num_heads, vit.num_registers = E, enc.depth, enc.num_heads, R
         vit.compute_dtype = cdt
@@ -527,46 +497,35 @@ class DinoV2ClassifierSlice(BasicClassifier):
             vit.fp8_amax = hip.ptr(self._fp8_amax)
         elif fp8 and self._fp8_collect:
             vit.fp8_amax_out = hip.ptr(self._fp8_calib)
-        vit.patch_w, vit.patch_b = hip.ptr(wp), hip.ptr(f32(enc.patch_embed.proj.bias))
-        vit.prefix = hip.ptr(prefix)
+        vit.patch_w, vit.patch_b = hip.ptr(put(wp.reshape(E, PATCH * 16), tdt)), hip.ptr(put(enc.patch_embed.proj.bias))
+        vit.prefix = hip.ptr(put(prefix))
         vit.layers = layers
-        vit.norm_w, vit.norm_b = hip.ptr(f32(enc.norm.weight)), hip.ptr(f32(enc.norm.bias))
+        vit.norm_w, vit.norm_b = hip.ptr(put(enc.norm.weight)), hip.ptr(put(enc.norm.bias))
+        return vit, layers, pos, cdt
 
+    def _fusion_weights(self, put):
         fw = hip.FusionWeights()
-        fw.emb_in, fw.emb, fw.num_heads = E, self.emb_ch, SLICE_HEADS
+        fw.emb_in, fw.emb, fw.num_heads = self.encoder.embed_dim, self.emb_ch, SLICE_HEADS
         fw.fusion_type = {"transformer": hip.FUSION_TRANSFORMER, "linear": hip.FUSION_LINEAR,
                           "average": hip.FUSION_AVERAGE}[self.slice_fusion_type]
         if hasattr(self, "bottleneck"):
-            fw.bottleneck_w, fw.bottleneck_b = hip.ptr(f32(self.bottleneck.weight)), hip.ptr(f32(self.bottleneck.bias))
+            fw.bottleneck_w, fw.bottleneck_b = hip.ptr(put(self.bottleneck.weight)), hip.ptr(put(self.bottleneck.bias))
         if hasattr(self, "slice_pos_emb"):
-            fw.slice_pos_emb = hip.ptr(f32(self.slice_pos_emb.weight))
+            fw.slice_pos_emb = hip.ptr(put(self.slice_pos_emb.weight))
         if self.slice_fusion_type == "transformer":
-            lay = self.slice_fusion.layers[0]
-            fw.cls_token = hip.ptr(f32(self.cls_token.reshape(-1)))
-            fw.ln1_w, fw.ln1_b = hip.ptr(f32(lay.norm1.weight)), hip.ptr(f32(lay.norm1.bias))
-            fw.in_proj_w, fw.in_proj_b = hip.ptr(f32(lay.self_attn.in_proj_weight)), hip.ptr(f32(lay.self_attn.in_proj_bias))
-            fw.out_proj_w, fw.out_proj_b = hip.ptr(f32(lay.self_attn.out_proj.weight)), hip.ptr(f32(lay.self_attn.out_proj.bias))
-            fw.ln2_w, fw.ln2_b = hip.ptr(f32(lay.norm2.weight)), hip.ptr(f32(lay.norm2.bias))
-            fw.lin1_w, fw.lin1_b = hip.ptr(f32(lay.linear1.weight)), hip.ptr(f32(lay.linear1.bias))
-            fw.lin2_w, fw.lin2_b = hip.ptr(f32(lay.linear2.weight)), hip.ptr(f32(lay.linear2.bias))
-            fw.norm_w, fw.norm_b = hip.ptr(f32(self.slice_fusion.norm.weight)), hip.ptr(f32(self.slice_fusion.norm.bias))
-            rot = getattr(lay.self_attn, "rotary_positional_encoding", None)
+            bind_slice_fusion(fw, self.slice_fusion, self.cls_token, put)
+            rot = getattr(self.slice_fusion.layers[0].self_attn, "rotary_positional_encoding", None)
             if rot is not None and hasattr(rot, "freqs"):
-                fw.rope_freqs = hip.ptr(f32(rot.freqs))
+                fw.rope_freqs = hip.ptr(put(rot.freqs))
             elif rot is not None:                      # LieRE: R = block_diag(exp(A_blk)) once per weight version
-                R = hip.liere_rotation(list(rot.vars))
-                keep.append(R)
-                fw.liere_rot = hip.ptr(R)
+                fw.liere_rot = hip.ptr(put(hip.liere_rotation(list(rot.vars))))
         if isinstance(self.linear, nn.Identity):
             fw.out_ch = 0
         else:
             fw.out_ch = self.out_ch
-            fw.head_w, fw.head_b = hip.ptr(f32(self.linear.weight)), hip.ptr(f32(self.linear.bias))
+            fw.head_w, fw.head_b = hip.ptr(put(self.linear.weight)), hip.ptr(put(self.linear.bias))
             fw.head_in = self.linear.weight.shape[1]
-        self._prep = dict(vit=vit, layers=layers, fusion=fw, keep=keep, pos=pos, cdt=cdt)
-        self._prep_sig = {True: self._signature(True), False: self._signature(False)}
-        self._pos_cache = {}
-        return self._prep
+        return fw
 
     def _pos_patch(self, prep, H, W):
         """vision_transformer.py:179-211: stored grid when it matches, bicubic resample otherwise."""
@@ -587,13 +546,6 @@ class DinoV2ClassifierSlice(BasicClassifier):
                 pp = hip.pos_embed_interp(pos[1:].contiguous(), M, gh, gw, 0.0 if reg else 0.1, antialias=reg)
             self._pos_cache[key] = pp
         return self._pos_cache[key]
-
-    def _workspace(self, name, nbytes, dev):
-        t = self._ws.get(name)
-        if t is None or t.numel() < nbytes or t.device != dev:
-            t = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-            self._ws[name] = t
-        return t
 
     def _auto_chunk(self, n, N, E, cdt):
         if self.chunk_slices > 0:
@@ -621,7 +573,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         N = 1 + enc.num_register_tokens + vit.grid_h * vit.grid_w
         dev = slices.device
         chunk = self._auto_chunk(n, N, E, prep["cdt"])
-        ws = self._workspace("vit", hip.vit_workspace_bytes(vit, H, W, chunk), dev)
+        ws = cached_workspace(self._ws, "vit", hip.vit_workspace_bytes(vit, H, W, chunk), dev)
         emb = torch.empty((n, E), dtype=torch.float32, device=dev)
         cls_probs = full_probs = None
         if n_layers_probs:
@@ -633,26 +585,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
 
     def fuse_slices(self, emb: torch.Tensor, B: int, D: int, mask: Optional[torch.Tensor], want_probs: bool,
                     want_logits: bool):
-        prep = self._prepare()
-        fw = prep["fusion"]
-        dev = emb.device
-        F = self.emb_ch * D if self.slice_fusion_type == "linear" else self.emb_ch
-        if want_logits and F != self.linear.weight.shape[1]:     # what nn.Linear raises in the reference (dino.py:166)
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({B}x{F} and "
-                               f"{self.linear.weight.shape[1]}x{self.linear.weight.shape[0]})")
-        features = torch.empty((B, F), dtype=torch.float32, device=dev)
-        logits = torch.empty((B, self.out_ch), dtype=torch.float32, device=dev) if want_logits else None
-        probs = None
-        if want_probs and self.slice_fusion_type == "transformer":
-            probs = torch.empty((B, SLICE_HEADS, D + 1, D + 1), dtype=torch.float32, device=dev)
-        m = None
-        if mask is not None and self.slice_fusion_type == "transformer":
-            m = mask.to(device=dev).to(torch.uint8).contiguous()
-            if tuple(m.shape) != (B, D):
-                raise RuntimeError(f"src_key_padding_mask must be [B, D] = {(B, D)}, got {tuple(m.shape)}")
-        ws = self._workspace("fusion", hip.fusion_workspace_bytes(fw, B, D), dev)
-        hip.slice_fusion(fw, emb.contiguous(), B, D, m, features, logits, probs, ws)
-        return features, logits, probs
+        return run_slice_fusion(self._prepare()["fusion"], emb, B, D, mask, want_logits, want_probs, self._ws)
 
     def forward(self, source, save_attn=False, src_key_padding_mask=None, **kwargs):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -44,6 +44,7 @@ import torch.nn as nn
 
 from .base_model import BasicClassifier
 from .. import hip, train_mode
+from .prepared import Prepared, bind_slice_fusion, run_slice_fusion
 
 _LAYERS = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}
 _WIDTHS = [64, 128, 256, 512]
@@ -195,44 +196,33 @@ class ResNet(BasicClassifier):
         else:
             warnings.warn("ResNet(pretrained=False): the reference builds a MONAI resnet here; this build keeps the torchvision "
                           "parameter layout with torchvision's initialisation")
-        self._prep = None
-        self._prep32 = None
-        self._epoch = 0
+        # device-side weight images, keyed on every parameter AND BatchNorm buffer: an optimiser step, a running-statistics update
+        # or any weight surgery makes them stale (an eval forward after training steps reused the first eval's fold)
+        self._prepared = Prepared()
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
     def _invalidate(self):
-        self._prep = self._prep32 = None
+        self._prepared.invalidate()
 
     def _apply(self, fn, *args, **kwargs):
-        self._prep = self._prep32 = None
+        self._invalidate()
         return super()._apply(fn, *args, **kwargs)
 
     # ---- backbone -------------------------------------------------------------------------------------------------------
-    def _state_version(self):
-        """Sum of the in-place version counters of every parameter and BatchNorm buffer plus their storage addresses: an optimiser
-        step, mst_batchnorm_train's running-statistics update or any weight surgery changes it (the folded weights were
-        keyed on (sum_in, device) only, so an eval forward after training steps reused the backbone folded at the first eval)."""
-        v = 0
-        for t in list(self.model.parameters()) + list(self.model.buffers()):
-            v += t._version + (t.data_ptr() & 0xFFFF)
-        return v
-
     def _prepare(self, sum_in: bool, fp32: bool = False):
-        """The BatchNorm-folded weights in compute_dtype (cached in ``_prep``).  fp32: in fp32 whatever compute_dtype is -- what the
-        eval-mode gradient node runs on; the same cache when compute_dtype is fp32, ``_prep32`` beside it otherwise."""
-        slot = "_prep32" if fp32 and self.compute_dtype_name != "fp32" else "_prep"
+        """The BatchNorm-folded weights in compute_dtype.  fp32: in fp32 whatever compute_dtype is -- what the eval-mode gradient
+        node runs on; the same image when compute_dtype is fp32, one of its own beside it otherwise."""
         name = "fp32" if fp32 else self.compute_dtype_name
+        return self._prepared.get(self, "backbone_" + name, lambda: self._fold_backbone(sum_in, name), sum_in, str(self.device), name)
+
+    def _fold_backbone(self, sum_in: bool, name: str):
         cdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[name]
-        key = (sum_in, str(self.device), self._state_version(), name)
-        cached = getattr(self, slot, None)
-        if cached is not None and cached["key"] == key:
-            return cached
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError(f"ResNet runs on an MI355X only: parameters are on {dev}; call .to('cuda'). There is no CPU fallback.")
         m = self.model
         # 16-bit: the stem's im2col rows are padded to 64 columns so that they are one "pixel" of a 1 x 1 convolution for mst_conv_gemm16
-        prep = {"key": key, "dtype": cdt, "stem": _fold(m.conv1, m.bn1, sum_in, dev, cdt, 16 if cdt == torch.float32 else 64), "blocks": []}
+        prep = {"dtype": cdt, "stem": _fold(m.conv1, m.bn1, sum_in, dev, cdt, 16 if cdt == torch.float32 else 64), "blocks": []}
         for li in range(4):
             for blk in getattr(m, f"layer{li + 1}"):
                 e = {"stride": blk.stride, "c1": _fold(blk.conv1, blk.bn1, False, dev, cdt), "c2": _fold(blk.conv2, blk.bn2, False, dev, cdt)}
@@ -243,7 +233,6 @@ class ResNet(BasicClassifier):
                 prep["blocks"].append(e)
         if not isinstance(m.fc, nn.Identity):
             prep["fc"] = (m.fc.weight.detach().to(dev, torch.float32).contiguous(), m.fc.bias.detach().to(dev, torch.float32).contiguous())
-        setattr(self, slot, prep)
         return prep
 
     def _features(self, x_nhwc: torch.Tensor, sum_in: bool, keep_last: bool = False) -> torch.Tensor:
@@ -348,7 +337,7 @@ class ResNet(BasicClassifier):
             from .. import train_resnet
             return (train_resnet.forward_with_grad if route == "train" else train_resnet.forward_eval_with_grad)(self, x, False)
         feat = self._features(x, False, keep_last=save_attn)
-        p = self._prep
+        p = self._prepare(False)
         out = hip.gemm(feat, p["fc"][0], p["fc"][1], epilogue=hip.EPI_BIAS) if "fc" in p else feat
         if save_attn:
             self._gradcam(out, p["fc"][0] if "fc" in p else None)
@@ -402,57 +391,28 @@ class ResNetSliceTrans(ResNet):
         self.slice_fusion = _SliceFusion(emb_ch)
         self.cls_token = nn.Parameter(torch.randn(1, 1, emb_ch))
         self.linear = _Linear(emb_ch, out_ch)
-        self._fw = None
-
-    def _invalidate(self):
-        self._prep = self._prep32 = None
-        self._fw = None
-
-    def _apply(self, fn, *args, **kwargs):
-        self._fw = None
-        return super()._apply(fn, *args, **kwargs)
+        self._ws = {}
 
     def _fusion_weights(self):
-        # (copies exist only where a parameter is not already fp32 on the device; the version sum catches in-place updates of those too)
-        ver = sum(t._version + (t.data_ptr() & 0xFFFF) for t in [self.cls_token, *self.slice_fusion.parameters(), *self.linear.parameters()])
-        if self._fw is not None and self._fw[2] == ver:
-            return self._fw[:2]
         dev = self.device
-        keep = []
+        keep = []                                        # (copies exist only where a parameter is not already fp32 on the device)
 
         def f32(t):
             t = t.detach().to(dev, torch.float32).contiguous()
             keep.append(t)
-            return hip.ptr(t)
+            return t
 
-        lay = self.slice_fusion.layers[0]
         fw = hip.FusionWeights()
-        fw.emb_in = fw.emb = self.emb_ch
+        fw.emb_in = fw.emb = fw.head_in = self.emb_ch
         fw.num_heads, fw.fusion_type, fw.out_ch = SLICE_HEADS, hip.FUSION_TRANSFORMER, self.out_ch
-        fw.cls_token = f32(self.cls_token.reshape(-1))
-        fw.ln1_w, fw.ln1_b = f32(lay.norm1.weight), f32(lay.norm1.bias)
-        fw.in_proj_w, fw.in_proj_b = f32(lay.self_attn.in_proj_weight), f32(lay.self_attn.in_proj_bias)
-        fw.out_proj_w, fw.out_proj_b = f32(lay.self_attn.out_proj.weight), f32(lay.self_attn.out_proj.bias)
-        fw.ln2_w, fw.ln2_b = f32(lay.norm2.weight), f32(lay.norm2.bias)
-        fw.lin1_w, fw.lin1_b = f32(lay.linear1.weight), f32(lay.linear1.bias)
-        fw.lin2_w, fw.lin2_b = f32(lay.linear2.weight), f32(lay.linear2.bias)
-        fw.norm_w, fw.norm_b = f32(self.slice_fusion.norm.weight), f32(self.slice_fusion.norm.bias)
-        fw.head_w, fw.head_b, fw.head_in = f32(self.linear.weight), f32(self.linear.bias), self.emb_ch
-        self._fw = (fw, keep, ver)
-        return self._fw[:2]
+        bind_slice_fusion(fw, self.slice_fusion, self.cls_token, f32)
+        fw.head_w, fw.head_b = hip.ptr(f32(self.linear.weight)), hip.ptr(f32(self.linear.bias))
+        return fw, keep
 
     def fuse(self, emb: torch.Tensor, B: int, D: int, src_key_padding_mask=None, save_attn: bool = False) -> torch.Tensor:
         """[B*D, 512] slice embeddings -> logits [B, out_ch] (resnet.py:180-191)."""
-        fw, _ = self._fusion_weights()
-        dev = emb.device
-        feats = torch.empty((B, self.emb_ch), dtype=torch.float32, device=dev)
-        logits = torch.empty((B, self.out_ch), dtype=torch.float32, device=dev)
-        probs = torch.empty((B, SLICE_HEADS, D + 1, D + 1), dtype=torch.float32, device=dev) if save_attn else None
-        m = None
-        if src_key_padding_mask is not None:
-            m = src_key_padding_mask.to(dev).to(torch.uint8).contiguous()
-        ws = torch.empty(int(hip.fusion_workspace_bytes(fw, B, D)), dtype=torch.uint8, device=dev)
-        hip.slice_fusion(fw, emb.contiguous(), B, D, m, feats, logits, probs, ws)
+        fw, _ = self._prepared.get(self, "fusion", self._fusion_weights)
+        _, logits, probs = run_slice_fusion(fw, emb, B, D, src_key_padding_mask, True, save_attn, self._ws)
         if save_attn:
             self.attention_maps_slice = [probs]
         return logits
