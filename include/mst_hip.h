@@ -40,7 +40,9 @@ enum mst_epilogue {
     MST_EPI_BIAS_GELU = 1, /* C = gelu_erf(A W^T + b)                     mlp.py:34-36            */
     MST_EPI_BIAS_RELU = 2, /* C = relu(A W^T + b)                         transformer_blocks.py:586 */
     MST_EPI_RESIDUAL = 3,  /* C(f32) += gamma * (A W^T + b)               block.py:90-94,112-113  */
-    MST_EPI_RESIDUAL_RELU = 4, /* C(f32) = relu(C + gamma * (A W^T + b))   resnet BasicBlock / Bottleneck exit; fp32 operands only */
+    MST_EPI_RESIDUAL_RELU = 4, /* C = relu(C + gamma * (A W^T + b))        resnet BasicBlock / Bottleneck exit.  Per entry point: mst_gemm
+                                * (fp32 operands) and mst_conv_gemm take an fp32 C; mst_conv_gemm16 takes a 16-bit C in place (no gamma);
+                                * mst_gemm with 16-bit operands refuses it */
     MST_EPI_BIAS_SWIGLU = 5   /* C[M, N/2] = silu(A Wg^T + bg) o (A Wv^T + bv)   swiglu_ffn.py:54-72; W is the row-paired image, see mst_gemm */
 };
 
@@ -344,7 +346,12 @@ int mst_block_fused(float* x, const void* attn_out, void* xn_out, int dtype, con
  * registers hold them (buffers then cover whole groups of 32 rows: round M up to a multiple of 32 when allocating):
  *   16-bit "blocked" [M/32 groups][24 pieces][64 slots][8]: element (row r, column c) of group g at piece c/16, slot (r%32) + 32*((c/8)%2),
  *     position c%8 (a piece = one contiguous KiB = 32 rows x 16 consecutive columns; natural column order);
- *   fp32 "image"     [M/32 groups][48 pieces][64 slots][4]: element (r, c) at piece c/8, slot (r%32) + 32*((c/4)%2), position c%4. */
+ *   fp32 "image"     [M/32 groups][48 pieces][64 slots][4]: element (r, c) at piece c/8, slot (r%32) + 32*((c/4)%2), position c%4.
+ * REQUIREMENT: a buffer named by a layout flag -- x under either X flag; attn_out and xn_out under ACT_BLOCKED -- must be allocated for
+ * ceil(M / 32) * 32 rows, whatever M is: the kernel reads and writes its last group whole (the rows past M hold nothing meaningful).  The
+ * C entry point sees pointers only and cannot check this; the Python wrapper (mst.hip.block_fused_s) checks the storage behind each
+ * tensor and refuses a short one before any launch.  mst_attention_ex (MST_ATTN_OUT_BLOCKED) and mst_gemm16_blocked state the same size
+ * for their blocked operand; their wrappers take it from the tensor's shape. */
 enum mst_layout_flags {
     MST_LAYOUT_X_IN_IMAGE = 1,   /* x is read in the fp32 image layout  */
     MST_LAYOUT_X_OUT_IMAGE = 2,  /* x is written in the fp32 image layout (in place also when the x flags differ: a 32-row group

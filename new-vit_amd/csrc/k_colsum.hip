@@ -34,8 +34,9 @@ __device__ __forceinline__ void load4(const T* p, float v[4]) {
 // OP_BN_BWD: acc0 = sum_r g (a[r][c] - m[c]) rs[c]  (d gamma; a = z),  acc1 = sum_r g  (d beta);  g = b[r][c] (= dy), times the ReLU mask
 //            (y[r][c] > 0 ? 1 : 0) when a is 16-bit and y is given
 // A 256-thread block: TX = 64 / CW threads x CW columns across and TY = 256 / TX thread rows down the chunk.  CW = 4 (VEC: 16-byte loads of
-// the fp32 a, 16 or 8 bytes of b; the scalar SLAB form: four guarded loads), CW = 1 (the scalar ATOMIC form) or CW = 8 (a 16-bit a: ONE
-// 16-byte load of a and of y, two of the fp32 b and of the per-column vectors; cols % 8 == 0).
+// the fp32 a, 16 or 8 bytes of b; the scalar form, ATOMIC and SLAB alike: four guarded loads -- one geometry, so that "one row block:
+// atomic = ordered" holds for odd column counts too; a one-column-per-thread ATOMIC form had TY = 4 and another row order) or CW = 8
+// (a 16-bit a: ONE 16-byte load of a and of y, two of the fp32 b and of the per-column vectors; cols % 8 == 0).
 // Output j of row block rb.  ATOMIC: o_j[c] by atomicAdd.  SLAB: o_j[rb * ostride + c] (= the slab), or o_j[c] += when `direct`.
 // Argument order: what the atomic column sum reads comes first and fills one 64-byte line of the kernel-argument segment.  Its
 // workgroups live for four loop iterations at the step's shapes, and a second line to fetch showed as +0.1 .. 0.4 us per launch.
@@ -183,12 +184,9 @@ int colreduce_args(const char* what, const void* a, int adt, int64_t as, const v
     const int ty = adt == MST_F32 ? 16 : 32;
     colsum_plan(rows, cols, ty, rpb, rblocks);
     const int64_t cblocks = (cols + 63) / 64;
-    if (!ordered) {
-        MST_CHECK_ARG(cblocks <= 65535, "%s: cols=%d out of range", what, cols);
-        MST_CHECK_ARG(rblocks < (1ll << 31), "%s: rows=%lld out of range", what, (long long)rows);
-        return MST_OK;
-    }
+    // one bound for both forms: SLAB puts rblocks * cblocks on gridDim.x, ATOMIC the row blocks (its column blocks go in pieces, below)
     MST_CHECK_ARG(rblocks * cblocks < (1ll << 31), "%s: rows=%lld cols=%d out of range", what, (long long)rows, cols);
+    if (!ordered) return MST_OK;
     const size_t need = colsum_ordered_workspace_bytes(rows, cols, outputs, ty);
     MST_CHECK_ARG(ws_bytes >= need && (need == 0 || ws), "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
     return MST_OK;
@@ -209,14 +207,31 @@ int colreduce_launch(const char* what, const void* a, int adt, int64_t as, const
     float* slab = (float*)ws;
     float* o0 = (!ordered || direct) ? out0 : slab;
     float* o1 = (!ordered || direct) ? out1 : slab + cols;
-    const dim3 grid = ordered ? dim3((unsigned)(rblocks * cblocks)) : dim3((unsigned)rblocks, cblocks);
+    // ATOMIC: gridDim.y takes 65,535 column blocks, so wider operands (the weight-gradient partials of ViT-L / g: [splits, 4096 * 1024]
+    // and up) go in pieces of PIECE whole blocks -- the kernel sees a [rows, pc] column block of the matrix at column p0, which the row
+    // strides already allow.  The plan (rpb) is that of the full shape; PIECE * 64 columns keep every piece's base 16-byte aligned and
+    // its width = cols (mod 4), so `vec` holds for all pieces or for none.
+    constexpr int PIECE = 65535;
 #define COLREDUCE_AS(AT, BT, CW, VEC, OUT)                                                                                                  \
-    colreduce_kernel<OP, AT, BT, CW, VEC, OUT><<<grid, dim3(256), 0, s>>>((const AT*)a, as, (const BT*)b, bs, rows, rpb, o0, cols, cblocks, m, rs, \
-                                                                          o1, (int64_t)NA * cols, direct, (const AT*)y)
+    do {                                                                                                                                    \
+        if constexpr (OUT == SLAB) {                                                                                                        \
+            colreduce_kernel<OP, AT, BT, CW, VEC, OUT><<<dim3((unsigned)(rblocks * cblocks)), dim3(256), 0, s>>>(                           \
+                (const AT*)a, as, (const BT*)b, bs, rows, rpb, o0, cols, cblocks, m, rs, o1, (int64_t)NA * cols, direct, (const AT*)y);     \
+        } else {                                                                                                                            \
+            for (int cb0 = 0; cb0 < cblocks; cb0 += PIECE) {                                                                                \
+                const int pb = cblocks - cb0 < PIECE ? cblocks - cb0 : PIECE;                                                               \
+                const int64_t p0 = (int64_t)cb0 * 64;                                                                                       \
+                const int pc = (int)(cols - p0 < (int64_t)pb * 64 ? cols - p0 : (int64_t)pb * 64);                                          \
+                colreduce_kernel<OP, AT, BT, CW, VEC, OUT><<<dim3((unsigned)rblocks, pb), dim3(256), 0, s>>>(                               \
+                    (const AT*)a + p0, as, b ? (const BT*)b + p0 : nullptr, bs, rows, rpb, o0 + p0, pc, pb, m ? m + p0 : nullptr,           \
+                    rs ? rs + p0 : nullptr, o1 ? o1 + p0 : nullptr, (int64_t)NA * cols, direct, (const AT*)y);                              \
+            }                                                                                                                               \
+        }                                                                                                                                   \
+    } while (0)
 #define COLREDUCE(BT, VEC)                                        \
     do {                                                          \
         if (ordered) COLREDUCE_AS(float, BT, 4, VEC, SLAB);       \
-        else COLREDUCE_AS(float, BT, (VEC ? 4 : 1), VEC, ATOMIC); \
+        else COLREDUCE_AS(float, BT, 4, VEC, ATOMIC);             \
     } while (0)
     if (adt == MST_BF16) COLREDUCE_AS(bf16_t, float, 8, true, SLAB);
     else if (adt == MST_F16) COLREDUCE_AS(f16_t, float, 8, true, SLAB);

@@ -351,6 +351,22 @@ def _resident(what: str, **tensors):
             raise ValueError(f"{what}: {name} must be contiguous")
 
 
+def storage_rows(t: torch.Tensor, cols: int) -> int:
+    """Whole rows of `cols` elements that t's storage holds from t's first element on (a `buf[:M]` view of a padded buffer counts the
+    padding: what a kernel may touch behind the view is the allocation's, not the view's)."""
+    return (t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()) // cols
+
+
+def _whole_groups(what: str, M: int, cols: int, **tensors):
+    """Operands in the blocked / image layouts (include/mst_hip.h, mst_layout_flags) are read and written as whole 32-row groups: every
+    tensor given (None skipped) must be backed by ceil(M / 32) * 32 rows of storage, or the call is refused before any launch."""
+    need = (M + 31) // 32 * 32
+    for name, t in tensors.items():
+        if t is not None and storage_rows(t, cols) < need:
+            raise ValueError(f"{what}: {name} is backed by {storage_rows(t, cols)} rows of storage, the blocked / image layouts take "
+                             f"whole 32-row groups: {need} rows for M = {M}")
+
+
 _T16 = (torch.bfloat16, torch.float16)
 
 
@@ -582,6 +598,8 @@ def block_fused_s(x: torch.Tensor, attn_out: torch.Tensor, block_seq: torch.Tens
     _dev(x, "block_fused_s")
     _dev(attn_out, "block_fused_s")
     M, E = x.shape
+    _whole_groups("block_fused_s", M, E, x=x if layout & (LAYOUT_X_IN_IMAGE | LAYOUT_X_OUT_IMAGE) else None,
+                  attn_out=attn_out if layout & LAYOUT_ACT_BLOCKED else None, xn_out=xn_out if layout & LAYOUT_ACT_BLOCKED else None)
     _check(load().mst_block_fused_s(ptr(x), ptr(attn_out), ptr(xn_out), dt_of(attn_out), ptr(block_seq), ptr(b1f), ptr(proj_bf),
                                     ptr(b2f), M, E, eps, layout, stream_of(x)), "mst_block_fused_s")
 

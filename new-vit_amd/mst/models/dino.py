@@ -40,7 +40,7 @@ import torch.nn as nn
 from .base_model import BasicClassifier
 from .. import hip, train_mode
 from ..parallel import SliceSharding
-from .prepared import Prepared, bind_slice_fusion, cached_workspace, run_slice_fusion
+from .prepared import Prepared, bind_slice_fusion, cached_workspace, pin_workspaces, run_slice_fusion
 
 PATCH = 14
 _VIT_SIZES = {  # reference: extern/dinov2/vision_transformer.py:340-395
@@ -625,7 +625,8 @@ class DinoV2ClassifierSlice(BasicClassifier):
     def _forward_graph(self, x, save_attn, mask, kwargs):
         """Replay of a captured eager forward.  Key: everything that selects kernels or buffer sizes.  The first TWO calls of a key
         run eagerly (lazy one-time work -- LDS attributes, workspaces, position-grid interpolation -- must not happen inside a
-        capture); the third captures.  Inputs are copied into the graph's static buffers, outputs are cloned out of them."""
+        capture); the third captures.  Inputs are copied into the graph's static buffers, outputs are cloned out of them.  The entry
+        owns the workspaces it was captured with (prepared.pin_workspaces): a larger shape replaces self._ws[...], not the graph's."""
         prep = self._prepare()
         without_linear = bool(kwargs.get("without_linear", False))
         key = (tuple(x.shape), x.dtype, bool(save_attn), mask is not None, without_linear, id(prep), torch.cuda.current_device())
@@ -649,6 +650,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
                 self._graphs[key] = {"graph": None, "calls": -(1 << 30)}     # this key stays eager
                 return self._forward_eager(x, save_attn, mask, kwargs)
             ent.update(graph=g, x=sx, mask=sm, out=sout, state=state)
+            pin_workspaces(ent, self._ws)               # the replay writes into THESE tensors, whatever self._ws holds by then
         ent["x"].copy_(x)
         if ent["mask"] is not None:
             ent["mask"].copy_(mask)

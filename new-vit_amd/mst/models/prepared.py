@@ -67,6 +67,17 @@ def cached_workspace(cache: dict, name: str, nbytes: int, dev) -> torch.Tensor:
     return t
 
 
+def pin_workspaces(entry: dict, cache: dict) -> dict:
+    """A captured graph replays raw pointers into the workspaces of `cache` as they were when it was captured, and cached_workspace
+    REPLACES a tensor as soon as a larger shape arrives.  So the graph's entry takes a reference to every workspace tensor live at its
+    capture: a replaced workspace then stays allocated (the caching allocator cannot hand its memory to anyone else) for exactly as
+    long as the graph that writes into it, and a replay of an earlier, smaller shape keeps working in its own scratch.  Dropping the
+    graphs on growth instead would recapture (two eager calls and a capture per key) every time a batch alternates between volumes of
+    different depth.  Needs no device: `entry` is any dict, the tensors may live anywhere.  Returns the entry."""
+    entry["ws"] = dict(cache)
+    return entry
+
+
 def bind_slice_fusion(fw: hip.FusionWeights, slice_fusion, cls_token: torch.Tensor, f32: Callable[[torch.Tensor], torch.Tensor]):
     """nn.TransformerEncoder(num_layers=1, norm=LayerNorm) + the class token -> fw's transformer fields.  `f32` hands back the fp32
     device image of a parameter and keeps it alive.  Everything else of fw (sizes, bottleneck, slice_pos_emb, rotary tables, the

@@ -24,6 +24,7 @@ import torch
 _VIT = {  # reference: vision_transformer.py:340-365
     "s": dict(embed_dim=384, depth=12, num_heads=6),
     "b": dict(embed_dim=768, depth=12, num_heads=12),
+    "l": dict(embed_dim=1024, depth=24, num_heads=16),
     "g": dict(embed_dim=1536, depth=40, num_heads=24),   # vision_transformer.py:382-396
 }
 

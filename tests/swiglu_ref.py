@@ -64,7 +64,11 @@ class _Lin16(torch.autograd.Function):
 
 
 def block(x, sd, p, heads, round16=None, storage16=False):
-    """block.py:89-114 with the SwiGLU FFN -> (x, attention probabilities)."""
+    """block.py:89-114 with the SwiGLU FFN -> (x, attention probabilities).  A block whose keys are the GELU MLP's (mlp.fc1 / fc2; no
+    16-bit emulation) is the oracle's own vit_block: one encoder loop serves every one-block model of tests/test_swiglu_gpu.py."""
+    if (p + ".mlp.fc1.weight") in sd:
+        assert round16 is None
+        return O.vit_block(x, sd, p, heads)
     if round16 is None:
         lin, keep = F.linear, (lambda t: t)
     else:
@@ -104,11 +108,12 @@ def encode(sd, slices, depth, heads, keep="none", round16=None, storage16=False)
     return O.layer_norm(x, sd["encoder.norm.weight"], sd["encoder.norm.bias"], 1e-6)[:, 0], maps
 
 
-def forward(sd, source, depth, heads, *, src_key_padding_mask=None, keep="none", round16=None, storage16=False):
+def forward(sd, source, depth, heads, *, src_key_padding_mask=None, keep="none", round16=None, storage16=False,
+            slice_fusion_type="transformer"):
     """DinoV2ClassifierSlice.forward (dino.py:110-167) with the SwiGLU encoder: O.forward's dict."""
     B, C, D, H, W = source.shape
     emb, maps = encode(sd, source.permute(0, 2, 1, 3, 4).reshape(B * D * C, H, W), depth, heads, keep, round16, storage16)
-    out = O.fuse(sd, emb, B, D * C, src_key_padding_mask=src_key_padding_mask)
+    out = O.fuse(sd, emb, B, D * C, slice_fusion_type=slice_fusion_type, src_key_padding_mask=src_key_padding_mask)
     out["vit_maps"] = maps
     return out
 

@@ -106,3 +106,42 @@ def test_block_boundary(hip, weights, dt, M, layout, xn_mode):
         assert sent(n_full), "a buffer that was not passed was written"
     if xn_mode != "alias":
         assert torch.equal(a_full[:Mp], ab), "attention rows changed although xn_out is another buffer"
+
+
+@pytest.mark.parametrize("layout", [1, 2, 4, 7])
+def test_blocked_layouts_refuse_buffers_short_of_whole_groups(hip, weights, layout):
+    """in the image / blocked layouts the kernel reads and writes whole 32-row groups (include/mst_hip.h, mst_layout_flags), so
+    M = 300 needs 320 rows behind every operand a flag names.  The wrapper looks at the STORAGE behind each tensor: exactly sized
+    tensors are refused before any launch (nothing is written), `buf[:M]` views of padded buffers -- what test_block_boundary passes --
+    are taken, and the result is the block arithmetic like the row-major call's."""
+    M, Mp, tdt = 300, 320, torch.bfloat16
+    wp, bp, w1, b1, w2, b2, g, be = weights
+    seq, b1f, pbf, b2f = hip.pack_block_seq(wp.cuda(), bp.cuda(), None, w1.cuda(), b1.cuda(), w2.cuda(), b2.cuda(), g.cuda(), be.cuda(),
+                                            None, tdt)
+    x0, att0, ref, refn, scale = operands_and_reference("bf16", M, weights)
+    x = torch.cat([x0.cuda(), torch.zeros(Mp - M, E, device="cuda")])
+    att = torch.cat([att0.cuda(), torch.zeros(Mp - M, E, dtype=tdt, device="cuda")])
+    short = dict(x=x[:M].clone(), attn_out=att[:M].clone(), xn_out=torch.full((M, E), SENTINEL, dtype=tdt, device="cuda"))
+    named = [n for n, flags in (("x", 3), ("attn_out", 4), ("xn_out", 4)) if layout & flags]
+    for name in named:                                   # one short operand at a time, the others padded
+        ops = dict(x=x.clone()[:M], attn_out=att.clone()[:M], xn_out=torch.full((Mp, E), SENTINEL, dtype=tdt, device="cuda")[:M])
+        ops[name] = short[name]
+        before = {k: v.clone() for k, v in ops.items()}
+        with pytest.raises(ValueError, match=f"block_fused_s: {name} is backed by 300 rows.*320 rows for M = 300"):
+            hip.block_fused_s(ops["x"], ops["attn_out"], seq, b1f, pbf, b2f, ops["xn_out"], layout=layout)
+        torch.cuda.synchronize()
+        assert all(torch.equal(ops[k], before[k]) for k in ops), "a refused call launched"
+    # an offset view counts from its own first element: the last 300 rows of a 320-row buffer have 300 rows behind them
+    if layout & 3:
+        with pytest.raises(ValueError, match="x is backed by 300 rows"):
+            hip.block_fused_s(x.clone()[Mp - M:], att.clone()[:M], seq, b1f, pbf, b2f, None, layout=layout)
+    if layout != 7:
+        return
+    # padded buffers: runs, and is the block arithmetic at the bars of test_block_boundary, like the row-major call on the same operands
+    xr, nr = x[:M].clone(), torch.empty((M, E), dtype=tdt, device="cuda")
+    hip.block_fused_s(xr, att[:M].clone(), seq, b1f, pbf, b2f, nr, layout=0)
+    xb, ab, nb = hip.to_image32(x), hip.to_blocked16(att), torch.empty((Mp, E), dtype=tdt, device="cuda")
+    hip.block_fused_s(xb[:M], ab[:M], seq, b1f, pbf, b2f, nb[:M], layout=7)
+    for what, gx, gn in (("row-major", xr, nr), ("blocked", hip.from_image32(xb)[:M], hip.from_blocked16(nb)[:M])):
+        assert float((gx.double().cpu() - ref).abs().max() / scale) < TOL["bf16"], what
+        assert float((gn.double().cpu() - refn).abs().max()) < 4 * TOL["bf16"], what

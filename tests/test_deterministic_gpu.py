@@ -74,7 +74,7 @@ def test_ordered_colsum_at_the_stem_batchnorm_shape(det):
 
 def test_ordered_colsum_past_the_column_block_limit(det):
     a = _cancelling(16, 4194304, 2)                                       # ViT-L fc weight-gradient partials: 65,536 column blocks
-    _colsum_case(a, compare_atomic=False)                                 # (beyond what mst_colsum launches)
+    _colsum_case(a)                                                       # (one more than a gridDim.y: mst_colsum goes in two pieces)
 
 
 def test_ordered_colsum_into_a_nonzero_out_with_b_and_a_strided_view(det):

@@ -254,6 +254,83 @@ def test_colsum_vector_and_scalar_column_blocks(hip, rows, cols, prod):
     assert float((out.cpu() - want).abs().max()) < 1e-5 * max(1.0, float(want.abs().max())) * max(1.0, rows ** 0.5 / 30)
 
 
+# 65,535 column blocks of 64 are what one launch of the atomic form puts on gridDim.y: 4,194,240 columns.  One more column (the scalar
+# path: a single column in block 65,536), four more (the vector path), then the weight-gradient widths of the wide encoders: ViT-L
+# fc1 / fc2 (4096 x 1024), ViT-g w3 (1536 x 4096) and w12 (8192 x 1536).  16 rows = the most `_dw` splits; 4 at the two widest keeps
+# an operand at 200 MB.
+WIDE_COLS = [(c, r) for c in (4194240, 4194241, 4194244, 4194304) for r in (1, 2, 16)] + [(c, r) for c in (6291456, 12582912) for r in (1, 2, 4)]
+
+
+@pytest.mark.parametrize("cols,rows", WIDE_COLS)
+def test_colsum_past_65535_column_blocks(hip, cols, rows):
+    """mst_colsum / mst_colsum_b16 and their ordered forms beyond one gridDim.y of column blocks (the atomic form walks them in pieces:
+    csrc/k_colsum.hip): without b, with an fp32 b and -- cols % 4 == 0 -- a bf16 and an fp16 b, onto a non-zero out, against float64 over
+    EVERY column of operands that differ by column (a piece read or added at the wrong offset is an error of order 1), at the bar of
+    test_colsum_vector_and_scalar_column_blocks.  So many column blocks always plan ONE row block, where the file promises "atomic =
+    ordered": the two flag states give the same bits."""
+    g = torch.Generator(device="cuda").manual_seed(cols % 1000 + rows)
+    a = torch.randn(rows, cols, device="cuda", generator=g)
+    b32 = torch.randn(rows, cols, device="cuda", generator=g)
+    out0 = torch.randn(cols, device="cuda", generator=g)
+    factors = [None, b32] + ([b32.bfloat16(), b32.half()] if cols % 4 == 0 else [])
+    prev, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    try:
+        for b in factors:
+            want = out0.double() + (a.double() if b is None else a.double() * b.double()).sum(0)
+            bar = 1e-5 * max(1.0, float(want.abs().max())) * max(1.0, rows ** 0.5 / 30)
+            got = []
+            for det in (False, True):
+                torch.use_deterministic_algorithms(det)
+                got.append(hip.colsum(a, out0.clone(), b))
+            err = float((got[0].double() - want).abs().max())
+            print(f"colsum [{rows}, {cols}] b={None if b is None else b.dtype}: max error {err:.3e}, {err / bar:.3f} of the bar")
+            assert err < bar, (b is None or b.dtype, err, bar)
+            assert torch.equal(got[0], got[1]), "one row block: the atomic and the ordered form must give the same bits"
+            del want
+    finally:
+        torch.use_deterministic_algorithms(prev, warn_only=warn)
+
+
+def test_colsum_still_refuses_what_it_cannot_launch(hip):
+    """Width is no longer a reason; what stays refused, at a width past one gridDim.y and before any launch: a 16-bit factor on a column
+    count that is no multiple of 4 (it has no scalar path), and an empty operand.  `out` keeps its bits; the size query of the
+    ordered form at the widest weight needs no workspace (one row block)."""
+    cols = 4194241
+    a = torch.ones(2, cols, device="cuda")
+    out = torch.full((cols,), 7.0, device="cuda")
+    lib = hip.load()
+    prev, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    try:
+        for det in (False, True):
+            torch.use_deterministic_algorithms(det)
+            with pytest.raises(RuntimeError, match="multiples of 4"):
+                hip.colsum(a, out, a.bfloat16())
+    finally:
+        torch.use_deterministic_algorithms(prev, warn_only=warn)
+    assert lib.mst_colsum(a.data_ptr(), cols, None, cols, 0, cols, out.data_ptr(), hip.stream_of(a)) != 0
+    assert hip.last_error().startswith("colsum:")
+    assert lib.mst_colsum(a.data_ptr(), cols, None, cols, 2, 0, out.data_ptr(), hip.stream_of(a)) != 0
+    assert hip.last_error().startswith("colsum:")
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
+    assert lib.mst_colsum_ordered_workspace_bytes(4, 12582912) == 0
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+def test_gemm16_rejects_residual_relu(hip, dt):
+    """include/mst_hip.h, MST_EPI_RESIDUAL_RELU per entry point: mst_gemm takes it on fp32 operands only (the 16-bit in-place form is
+    mst_conv_gemm16's) -- 16-bit operands are refused before a launch, whatever the type of C."""
+    a = torch.zeros(64, 128, dtype=DT[dt], device="cuda")
+    w = torch.zeros(128, 128, dtype=DT[dt], device="cuda")
+    for odt in (torch.float32, DT[dt]):
+        out = torch.full((64, 128), 3.0, dtype=odt, device="cuda")
+        with pytest.raises(RuntimeError, match="f32 operands only"):
+            hip.gemm(a, w, torch.zeros(128, device="cuda"), epilogue=4, out=out)
+        assert bool((out == 3.0).all())
+    got = hip.gemm(a.float() + 1, w.float() + 1, torch.zeros(128, device="cuda"), epilogue=4, out=torch.full((64, 128), -200.0, device="cuda"))
+    assert bool((got == 0.0).all())                                       # relu(-200 + 128): the fp32 operands take it
+
+
 def test_gemm_rejects_bad_shapes(hip):
     a = torch.zeros(8, 100, dtype=torch.bfloat16, device="cuda")
     w = torch.zeros(128, 100, dtype=torch.bfloat16, device="cuda")

@@ -339,6 +339,52 @@ def test_graph_replay_equals_eager(mode):
             assert torch.equal(mg(src, src_key_padding_mask=mask), me(src, src_key_padding_mask=mask)), it
 
 
+@pytest.mark.parametrize("mode", ["bf16", "fp32"])
+def test_graph_replay_after_the_workspace_has_grown(mode):
+    """a captured graph holds raw pointers into the encoder's and the fusion's workspaces, and a volume with more slices
+    replaces both tensors.  The graph's entry owns the workspaces of its capture (mst/models/prepared.py, pin_workspaces), so a replay
+    of the earlier shape writes its scratch into memory nobody else can have been given: victim tensors of exactly the replaced sizes,
+    allocated after the growth (where the caching allocator would hand out a freed workspace first), keep every byte -- the replay's own
+    results cannot show this, its scratch is written before it is read -- and both shapes stay the eager model's bit for bit."""
+    g = load_golden("b2_mask")
+    mg = build(CASES["b2_mask"], int(g["seed"]), mode, use_graph="1")
+    me = build(CASES["b2_mask"], int(g["seed"]), mode, use_graph="0")
+    mask_a = torch.from_numpy(g["src_key_padding_mask"])
+    shape_a = tuple(int(v) for v in g["shape"])
+    shape_b = shape_a[:2] + (2 * shape_a[2],) + shape_a[3:]
+    mask_b = torch.cat([mask_a, torch.zeros_like(mask_a)], dim=1)
+    seed = int(g["seed"]) + 300
+
+    def both(shape, mask, it):
+        src = synth.synth_volume(shape, seed + it)
+        a = mg(src, src_key_padding_mask=mask, save_attn=True)
+        b = me(src, src_key_padding_mask=mask, save_attn=True)
+        assert torch.equal(a, b), (shape, it)
+        assert torch.equal(mg.get_attention_maps(), me.get_attention_maps()), (shape, it)
+        assert torch.equal(mg.get_slice_attention(), me.get_slice_attention()), (shape, it)
+        assert torch.equal(torch.stack(mg.attention_maps), torch.stack(me.attention_maps)), (shape, it)
+
+    with torch.no_grad():
+        for it in range(4):                              # calls 1-2 eager, 3 captures and replays, 4 replays
+            both(shape_a, mask_a, it)
+        ent = next(e for e in mg._graphs.values() if e["graph"] is not None)
+        old = dict(mg._ws)
+        assert set(old) == {"vit", "fusion"}
+        sizes = {k: t.numel() * t.element_size() for k, t in old.items()}
+        both(shape_b, mask_b, 4)                         # twice the slices: both workspaces are replaced
+        assert mg._ws["vit"] is not old["vit"] and mg._ws["fusion"] is not old["fusion"]
+        assert mg._ws["vit"].numel() > old["vit"].numel()
+        old = {k: t.data_ptr() for k, t in old.items()}  # (no reference of the test's own keeps the replaced tensors alive)
+        victims = [torch.full((n,), 0xA5, dtype=torch.uint8, device="cuda") for n in sizes.values() for _ in range(4)]
+        for it in (5, 6):                                # replays of A: new inputs
+            both(shape_a, mask_a, it)
+        torch.cuda.synchronize()
+        assert all(bool((v == 0xA5).all()) for v in victims), "a replay wrote into memory the model no longer owns"
+        both(shape_b, mask_b, 7)
+        assert all(bool((v == 0xA5).all()) for v in victims)
+        assert {k: t.data_ptr() for k, t in ent["ws"].items()} == old     # why: the entry still owns the workspaces of its capture
+
+
 def _rccl_worker(port, ret):
     import os
     import torch.distributed as dist

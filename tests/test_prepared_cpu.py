@@ -1,12 +1,14 @@
 """mst/models/prepared.py on CPU tensors (they have ``data_ptr`` and ``_version`` like device tensors): the weight-version key, the
-holder of the images built under it, and the binding of either model file's slice transformer into ``mst_fusion_weights``."""
+holder of the images built under it, the binding of either model file's slice transformer into ``mst_fusion_weights``, and the
+workspace cache with what a captured graph keeps of it."""
 import ctypes as C
+import weakref
 
 import pytest
 import torch
 
 from mst import hip
-from mst.models.prepared import Prepared, bind_slice_fusion, version_key
+from mst.models.prepared import Prepared, bind_slice_fusion, cached_workspace, pin_workspaces, version_key
 
 FORMS = pytest.mark.parametrize("full", [True, False], ids=["pairs", "folded"])
 
@@ -140,3 +142,35 @@ def test_bind_slice_fusion_points_every_owned_field_at_its_tensor(which):
             assert C.cast(value, C.POINTER(C.c_float))[0] == float(want[name].detach().flatten()[0]), name
         else:
             assert not value, name                          # NULL or 0: sizes, bottleneck, position table, rotary tables and head are the model's
+
+
+def test_cached_workspace_keeps_a_large_enough_tensor_and_replaces_a_smaller_one():
+    cache, cpu = {}, torch.device("cpu")
+    a = cached_workspace(cache, "vit", 100, cpu)
+    assert a.dtype == torch.uint8 and a.numel() == 100 and cache["vit"] is a
+    assert cached_workspace(cache, "vit", 100, cpu) is a and cached_workspace(cache, "vit", 7, cpu) is a     # same size, smaller: kept
+    b = cached_workspace(cache, "vit", 101, cpu)                                                            # one byte more: replaced
+    assert b is not a and b.numel() == 101 and cache["vit"] is b
+    assert cached_workspace(cache, "fusion", 0, cpu).numel() == 0 and set(cache) == {"vit", "fusion"}       # names are independent
+    assert cache["vit"] is b
+
+
+def test_a_graph_entry_owns_the_workspaces_of_its_capture():
+    """pin_workspaces: the entry of a captured graph (a stand-in dict here) holds every workspace tensor that was live at its capture,
+    so growth replaces the cache's tensor and leaves the entry's allocated -- for as long as the entry, not longer."""
+    cache, cpu = {}, torch.device("cpu")
+    vit, fusion = cached_workspace(cache, "vit", 64, cpu), cached_workspace(cache, "fusion", 16, cpu)
+    vit.fill_(0xA5)
+    ent = {"graph": object(), "calls": 3}
+    assert pin_workspaces(ent, cache) is ent
+    assert ent["ws"] == {"vit": vit, "fusion": fusion} and ent["ws"] is not cache
+    alive, where = weakref.ref(vit), vit.data_ptr()
+    del vit
+    grown = cached_workspace(cache, "vit", 128, cpu)                     # a larger shape arrives
+    assert cache["vit"] is grown and ent["ws"]["vit"] is not grown
+    assert alive() is not None and alive().data_ptr() == where and alive().numel() == 64 and bool((alive() == 0xA5).all())
+    assert ent["ws"]["fusion"] is cache["fusion"]                        # what did not grow is shared, not copied
+    later = pin_workspaces({"graph": object()}, cache)                   # a graph captured after the growth pins the new tensor
+    assert later["ws"]["vit"] is grown
+    del ent                                                              # the graph goes (invalidate()): so does its workspace
+    assert alive() is None

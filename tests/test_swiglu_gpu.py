@@ -183,7 +183,7 @@ def _model(sd, E, depth, heads, *, ffn="swiglufused", img_size=518, layerscale=T
     from mst.models import DinoV2ClassifierSlice
     from mst.models.dino import _ViT
     with torch.device("meta"):
-        m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, model_size="g" if E == 1536 else "s", ffn_layer=ffn, **kw)
+        m = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, model_size={1536: "g", 1024: "l"}.get(E, "s"), ffn_layer=ffn, **kw)
         m.encoder = _ViT(E, depth, heads, img_size=img_size, layerscale=1.0 if layerscale else None, chunked=chunked, ffn_layer=ffn)
     m = m.to_empty(device="cuda")
     m.load_state_dict(sd, strict=True)
@@ -201,6 +201,14 @@ def sd_g1():
     """The one E = 1536 SwiGLU state dict of this module (its synthesis alone takes seconds): the fixture's, reused by the training tests."""
     return synth.synth_state_dict("g", int(load_golden("swiglu_g1")["seed"]), img_size=518, layerscale=True, chunked=False,
                                   ffn_layer="swiglufused", depth=1)
+
+
+@pytest.fixture(scope="module")
+def sd_l1():
+    """One block of the ViT-L width with the GELU MLP (fc1 / fc2: 4096 x 1024, one column block more than a gridDim.y of mst_colsum),
+    LayerScale and the hub layout like sd_g1.  Slices are averaged: 1024 is no multiple of the Slice Transformer's 12 heads, so the
+    reference has no ViT-L with the transformer fusion either."""
+    return synth.synth_state_dict("l", 71, img_size=518, layerscale=True, chunked=False, ffn_layer="mlp", depth=1, slice_fusion="average")
 
 
 @pytest.mark.parametrize("mode", ["fp32", "fp16", "bf16"])
@@ -296,23 +304,28 @@ def _step(model, src, target, mask=None):
 _REF = {}
 
 
-def _float64_grads(name, sd, src, depth, heads, target):
+def _float64_grads(name, sd, src, depth, heads, target, **kw):
     if name not in _REF:                                                  # computed once, shared by the atomic and the ordered run
-        _REF[name] = R.grads(sd, src, depth, heads, target)
+        _REF[name] = R.grads(sd, src, depth, heads, target, **kw)
     return _REF[name]
 
 
 @pytest.mark.parametrize("det", [False, True], ids=["atomic", "deterministic"])
-@pytest.mark.parametrize("case", ["s2_layerscale", "g1"])
-def test_fp32_step_matches_float64_autograd(case, det, sd_s2, sd_g1):
+@pytest.mark.parametrize("case", ["s2_layerscale", "g1", "g1_m136", "l1"])
+def test_fp32_step_matches_float64_autograd(case, det, sd_s2, sd_g1, sd_l1):
     """Every parameter gradient and d source of the fp32 step against float64 autograd through tests/swiglu_ref.py, at the bar of
     tests/train_parity.py (1e-4 of max |ref| + 1e-9: its derivation -- the reference's own fp32 noise -- applies unchanged); under
-    torch.use_deterministic_algorithms(True) two steps give the same bits."""
-    sd, E, depth, heads, shape = {"s2_layerscale": (sd_s2, 384, 2, 6, (2, 1, 3, 70, 56)), "g1": (sd_g1, 1536, 1, 24, (1, 1, 2, 56, 56))}[case]
+    torch.use_deterministic_algorithms(True) two steps give the same bits.  g1 has 34 token rows: every weight gradient is one product.
+    g1_m136 and l1 (E = 1024, 16 heads, the GELU MLP) have 8 x 17 = 136: `_dw` splits them in two and reduces [2, N K] partials of 4.2 M
+    (fc1 / fc2 of l1) to 12.6 M columns (w12 of g1) with mst_colsum -- atomic with the flag off, ordered with it on."""
+    sd, E, depth, heads, shape, ffn, fusion = {"s2_layerscale": (sd_s2, 384, 2, 6, (2, 1, 3, 70, 56), "swiglufused", "transformer"),
+                                               "g1": (sd_g1, 1536, 1, 24, (1, 1, 2, 56, 56), "swiglufused", "transformer"),
+                                               "g1_m136": (sd_g1, 1536, 1, 24, (1, 1, 8, 56, 56), "swiglufused", "transformer"),
+                                               "l1": (sd_l1, 1024, 1, 16, (1, 1, 8, 56, 56), "mlp", "average")}[case]
     src, target = synth.synth_volume(shape, 171), torch.arange(shape[0]) % 2
-    _, logits_ref, ref = _float64_grads(case, sd, src, depth, heads, target)
+    _, logits_ref, ref = _float64_grads(case, sd, src, depth, heads, target, slice_fusion_type=fusion)
     with _deterministic(det):
-        model = _model(sd, E, depth, heads, compute_dtype="fp32").train()
+        model = _model(sd, E, depth, heads, ffn=ffn, slice_fusion=fusion, compute_dtype="fp32").train()
         logits, got = _step(model, src, target)
         errs = P.scaled_errors(got, ref)
         worst = max(errs, key=errs.get)
