@@ -651,7 +651,12 @@ typedef struct mst_fusion_weights {
  * 29-318), row 0, linear head.  emb fp32 [B*D, emb_in]; key_padding_mask uint8 [B, D]
  * (1 = padded slice; NULL = none) -- the CLS column is prepended inside (dino.py:147-150).
  * features fp32 [B, F] (F = emb; emb*D for 'linear'), logits fp32 [B, out_ch] (nullable),
- * slice_probs fp32 [B, heads, 1+D, 1+D] (nullable; transformer_blocks.py:266-295). */
+ * slice_probs fp32 [B, heads, 1+D, 1+D] (nullable; transformer_blocks.py:266-295).
+ * Supported (head_dim = emb / num_heads, L = 1 + D) of the transformer fusion: head_dim in {4, 8, 16, 32, 64, 128}; the attention keeps
+ * a head's K, V and mask in LDS, (2 L head_dim + L) * 4 bytes <= 160 KiB: L <= 317 at head_dim 64, 630 at 32.  head_dim 128 fits that up
+ * to L = 159 and from there to L = 317 keeps K and the mask in LDS and reads V from global memory, so every width runs the 257 tokens
+ * that slice_pos_emb (256 positions) allows.  Longer sequences return MST_EINVAL ("slice_attn: L=.. head_dim=.. does not fit LDS")
+ * without launching the attention. */
 size_t mst_fusion_workspace_bytes(const mst_fusion_weights* w, int B, int D);
 int mst_slice_fusion(const mst_fusion_weights* w, const float* emb, int B, int D,
                      const uint8_t* key_padding_mask, float* features, float* logits,

@@ -1,6 +1,10 @@
 // Small fp32 kernels of the across-slice stage (dino.py:138-153; transformer_blocks.py:210-295)
-// and of the saliency read-outs (dino.py:173-202).  Sequence length is 1+D <= 257 and the whole
-// stage is ~0.1 GFLOP per volume: these kernels are latency-bound, kept in exact fp32 on the VALU.
+// and of the saliency read-outs (dino.py:173-202).  Sequence length is 1+D <= 257 with slice_pos_emb
+// (256 positions) and the whole stage is ~0.1 GFLOP per volume: these kernels are latency-bound, kept in
+// exact fp32 on the VALU.  Supported (head_dim, L) of the attention, set by LDS (launch_slice_attn):
+//   head_dim <= 64: (2 L hd + L) * 4 B <= 160 KiB, i.e. L <= 317 at 64, 630 at 32, 1241 at 16, ...
+//   head_dim 128:   L <= 159 with K and V in LDS; 160 <= L <= 317 with K in LDS and V read from global memory.
+// Beyond that the launcher refuses with "slice_attn: L=.. head_dim=.. does not fit LDS" (MST_EINVAL); no launch.
 #include "mst_common.h"
 
 namespace {
@@ -26,7 +30,10 @@ __global__ void slice_tokens_kernel(const float* __restrict__ emb, const float* 
 // One workgroup per (batch, head): K and V of the head in LDS (RoPE applied to q and k on the fly:
 // rotary_embedding_torch.py:38-62,159-173), one query row per thread, three passes over the keys
 // (max, sum + PV, optional probability write).  Masked keys score -inf (transformer_blocks.py:244-252).
-template <int HD>
+// VG: only K (the operand that carries the rotation) and the mask are staged; V rows are read from qkv in global
+// memory.  Every lane of a wave reads the same row j at the same time, so a row is one uniform (broadcast) load
+// of an L2-resident line.  Same arithmetic in the same order as the LDS form.
+template <int HD, bool VG>
 __global__ __launch_bounds__(256) void slice_attn_kernel(const float* __restrict__ qkv, int L, int heads,
                                                          const uint8_t* __restrict__ mask,
                                                          const float* __restrict__ rope,
@@ -34,8 +41,8 @@ __global__ __launch_bounds__(256) void slice_attn_kernel(const float* __restrict
                                                          float* __restrict__ out, float* __restrict__ probs) {
     extern __shared__ float sm[];
     float* Ks = sm;                 // [L][HD]
-    float* Vs = sm + (size_t)L * HD;  // [L][HD]
-    float* Mb = Vs + (size_t)L * HD;  // [L] additive mask
+    float* Vs = sm + (size_t)L * HD;  // [L][HD]; absent when VG
+    float* Mb = VG ? Vs : Vs + (size_t)L * HD;  // [L] additive mask
     const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
     const int E = heads * HD, ld = 3 * E;
     const float* base = qkv + (int64_t)b * L * ld;
@@ -52,7 +59,7 @@ __global__ __launch_bounds__(256) void slice_attn_kernel(const float* __restrict
 #pragma unroll 8
             for (int e = 0; e < HD; ++e) a = fmaf(liere[d * HD + e], kp[e], a);
             Ks[i] = a;
-            Vs[i] = base[(int64_t)j * ld + 2 * E + h * HD + d];
+            if (!VG) Vs[i] = base[(int64_t)j * ld + 2 * E + h * HD + d];
         }
     } else
     for (int i = tid; i < L * (HD / 2); i += 256) {
@@ -68,8 +75,10 @@ __global__ __launch_bounds__(256) void slice_attn_kernel(const float* __restrict
         }
         Ks[j * HD + 2 * p] = k0;
         Ks[j * HD + 2 * p + 1] = k1;
-        Vs[j * HD + 2 * p] = kp[E];
-        Vs[j * HD + 2 * p + 1] = kp[E + 1];
+        if (!VG) {
+            Vs[j * HD + 2 * p] = kp[E];
+            Vs[j * HD + 2 * p + 1] = kp[E + 1];
+        }
     }
     for (int j = tid; j < L; j += 256) {
         // column 0 is the CLS token, never padded (dino.py:147-150)
@@ -120,8 +129,14 @@ __global__ __launch_bounds__(256) void slice_attn_kernel(const float* __restrict
             for (int d = 0; d < HD; ++d) a = fmaf(q[d], Ks[j * HD + d], a);
             const float p = expf(a + Mb[j] - mx);
             sum += p;
+            if constexpr (VG) {
+                const float* vp = base + (int64_t)j * ld + 2 * E + h * HD;
 #pragma unroll
-            for (int d = 0; d < HD; ++d) acc[d] = fmaf(p, Vs[j * HD + d], acc[d]);
+                for (int d = 0; d < HD; ++d) acc[d] = fmaf(p, vp[d], acc[d]);
+            } else {
+#pragma unroll
+                for (int d = 0; d < HD; ++d) acc[d] = fmaf(p, Vs[j * HD + d], acc[d]);
+            }
         }
         const float inv = 1.0f / sum;
         float* op = out + ((int64_t)b * L + qi) * E + h * HD;
@@ -267,21 +282,31 @@ int launch_slice_tokens(const float* emb, const float* cls, const float* pos, in
 
 int launch_slice_attn(const float* qkv, int B, int L, int heads, int hd, const uint8_t* mask, const float* rope,
                       const float* liere, float* out, float* probs, hipStream_t s) {
-    const size_t sh = ((size_t)2 * L * hd + L) * sizeof(float);
-    MST_CHECK_ARG(sh <= 160 * 1024, "slice_attn: L=%d head_dim=%d does not fit LDS", L, hd);
+    // LDS rule: K, V and the mask, (2 L hd + L) floats, in at most 160 KiB.  head_dim 128 reaches that at L = 159, short of the
+    // 257 tokens that slice_pos_emb allows, so past it that width stages K and the mask only, (L hd + L) floats, and reads V from
+    // global memory: L <= 317.  Anything larger is refused here, before a launch.
+    const size_t lds_max = 160 * 1024;
+    size_t sh = ((size_t)2 * L * hd + L) * sizeof(float);
+    const bool vg = hd == 128 && sh > lds_max;
+    if (vg) sh = ((size_t)L * hd + L) * sizeof(float);
+    MST_CHECK_ARG(sh <= lds_max, "slice_attn: L=%d head_dim=%d does not fit LDS", L, hd);
     const dim3 grid(B, heads), block(256);
-#define SA_CASE(HD)                                                                                              \
-    case HD: {                                                                                                   \
-        auto kern = slice_attn_kernel<HD>;                                                                       \
+#define SA_LAUNCH(HD, VG)                                                                                        \
+    {                                                                                                            \
+        auto kern = slice_attn_kernel<HD, VG>;                                                                   \
         if (sh > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); \
         kern<<<grid, block, sh, s>>>(qkv, L, heads, mask, rope, liere, out, probs);                                     \
-        break;                                                                                                   \
     }
+#define SA_CASE(HD) case HD: SA_LAUNCH(HD, false) break;
     switch (hd) {
-        SA_CASE(4) SA_CASE(8) SA_CASE(16) SA_CASE(32) SA_CASE(64) SA_CASE(128)     // 128: 16 heads over the 2048-wide embeddings of a bottleneck ResNet
+        SA_CASE(4) SA_CASE(8) SA_CASE(16) SA_CASE(32) SA_CASE(64)
+        case 128:     // ViT-g (1536 / 12 heads); 16 heads over the 2048-wide embeddings of a bottleneck ResNet
+            if (vg) SA_LAUNCH(128, true) else SA_LAUNCH(128, false)
+            break;
         default: mst_set_error("slice_attn: head_dim=%d unsupported (4,8,16,32,64,128)", hd); return MST_EINVAL;
     }
 #undef SA_CASE
+#undef SA_LAUNCH
     return mst_check_launch("slice_attn");
 }
 

@@ -37,7 +37,10 @@ def scaled_err(got, ref):
 
 
 # ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rows,cols", [(1, 384), (7, 384), (1030, 384), (5, 768), (9, 96), (3, 48), (4, 1024)])
+# (5, 1536), (3, 2048): the 16-chunk instance (cols 1025..2048), ViT-g and bottleneck-ResNet widths; (7, 1280): its partial last chunk;
+# (4, 130): a second chunk that holds one lane's pair
+@pytest.mark.parametrize("rows,cols", [(1, 384), (7, 384), (1030, 384), (5, 768), (9, 96), (3, 48), (4, 1024),
+                                       (5, 1536), (3, 2048), (7, 1280), (4, 130)])
 @pytest.mark.parametrize("odt", [torch.float32, torch.float16, torch.bfloat16])
 def test_layernorm(hip, rows, cols, odt):
     x = rnd((rows, cols), 1, 3.0) + 0.5
@@ -46,6 +49,14 @@ def test_layernorm(hip, rows, cols, odt):
     got = hip.layernorm(x.cuda(), g.cuda(), b.cuda(), 1e-6, odt)
     assert got.dtype == odt
     assert scaled_err(got, ref) < OUT_TOL[odt]
+
+
+@pytest.mark.parametrize("cols", [2050, 383])
+def test_layernorm_refuses_wide_and_odd_rows(hip, cols):
+    """more than 2048 columns, or an odd number of them, is an error, not a partial answer."""
+    x = rnd((2, cols), 1).cuda()
+    with pytest.raises(RuntimeError, match=f"cols={cols} must be even and <= 2048"):
+        hip.layernorm(x, torch.ones(cols, device="cuda"), torch.zeros(cols, device="cuda"), 1e-6)
 
 
 def test_layernorm_strided_cls_rows(hip):
@@ -635,19 +646,23 @@ def test_slice_fusion_matches_reference_layer_fixture(hip, tag):
             assert np.abs(probs.cpu().numpy()[0] - ref_w).max() < 5e-6
 
 
-def test_attention_readout(hip):
+@pytest.mark.parametrize("B,D,sheads", [(2, 5, 12), (3, 256, 16), (1, 300, 12)])     # D = 300: a second trip of the 256-thread slice loop
+def test_attention_readout(hip, B, D, sheads):
     from oracle import mst_oracle as O
-    B, D, heads, Np, R = 2, 5, 6, 16, 0
+    heads, Np, R = 6, 16, 0
     N = 1 + R + Np
-    cls = torch.rand(B * D, heads, N).softmax(-1)
-    sp = torch.rand(B, 12, D + 1, D + 1).softmax(-1)
-    plane = torch.empty(B * D, heads, Np, device="cuda")
-    maps = torch.empty_like(plane)
-    sa = torch.empty(B * D, device="cuda")
-    hip.attention_readout(cls.cuda(), sp.cuda(), B, D, heads, N, R, 12, plane, sa, maps)
-    assert rel_l2(plane.cpu(), O.plane_attention(cls[:, :, None, :])) < 1e-6
-    assert rel_l2(sa.cpu(), O.slice_attention(sp).reshape(-1)) < 1e-6
-    assert rel_l2(maps.cpu(), O.attention_maps(cls[:, :, None, :], sp)) < 1e-6
+    gen = torch.Generator().manual_seed(D)
+    cls = torch.rand(B * D, heads, N, generator=gen).softmax(-1)
+    sp = torch.rand(B, sheads, D + 1, D + 1, generator=gen).softmax(-1)
+    plane = torch.full((B * D, heads, Np), float("nan"), device="cuda")
+    maps = torch.full_like(plane, float("nan"))
+    sa = torch.full((B * D,), float("nan"), device="cuda")
+    hip.attention_readout(cls.cuda(), sp.cuda(), B, D, heads, N, R, sheads, plane, sa, maps)
+    cls64, sp64 = cls.double()[:, :, None, :], sp.double()          # the oracle in float64 on the same fp32 probabilities
+    errs = (rel_l2(plane.cpu(), O.plane_attention(cls64)), rel_l2(sa.cpu(), O.slice_attention(sp64).reshape(-1)),
+            rel_l2(maps.cpu(), O.attention_maps(cls64, sp64)))
+    print(f"attention read-out B={B} D={D} sheads={sheads}: rel-L2 plane {errs[0]:.2e} slice {errs[1]:.2e} maps {errs[2]:.2e}")
+    assert max(errs) < 1e-6, errs
     assert torch.allclose(plane.sum(-1).cpu(), torch.ones(B * D, heads), atol=1e-5)
 
 

@@ -280,6 +280,29 @@ def test_g_width_with_the_plain_mlp_matches_the_oracle(mode, monkeypatch):
     assert rel_l2(model.get_attention_maps().cpu(), O.attention_maps(ref["vit_maps"][-1], ref["slice_map"])) < tm
 
 
+def test_g_width_deep_volume_matches_the_oracle(monkeypatch):
+    """The same one-block g model on a 200-slice volume with its last 60 slices masked: the slice transformer at head_dim 128 with 201
+    tokens, more than K and V of a head fill in LDS (159 tokens), so the attention reads V from global memory (csrc/k_slice.hip).
+    One 14 x 14 patch per slice keeps the encoder small; one state dict and one oracle run serve the three compute types."""
+    from oracle import mst_oracle as O
+    monkeypatch.setitem(O.VIT_CFG, "g1", dict(embed_dim=1536, depth=1, num_heads=24))
+    sd = synth.synth_state_dict("g", 61, depth=1)
+    src = synth.synth_volume((1, 1, 200, 14, 14), 162)
+    mask = torch.zeros(1, 200, dtype=torch.bool)
+    mask[0, 140:] = True
+    with torch.no_grad():
+        ref = O.forward(sd, src, model_size="g1", src_key_padding_mask=mask, keep="cls")
+    for mode in ("fp32", "fp16", "bf16"):
+        tl, te, tm = TOL[mode]
+        model = _model(sd, 1536, 1, 24, ffn="mlp", img_size=224, layerscale=False, chunked=True, compute_dtype=mode).eval()
+        with torch.no_grad():
+            logits = model(src, save_attn=True, src_key_padding_mask=mask)
+        err, merr = float((logits.cpu() - ref["logits"]).abs().max()), rel_l2(model.attention_maps_slice[-1].cpu(), ref["slice_map"])
+        print(f"g width, 200 slices, {mode}: logits {err:.3e} slice map {merr:.3e}")
+        assert err < tl and merr < tm, (mode, err, merr)
+        assert torch.equal(model.attention_maps_slice[-1][0, :, :, 141:].cpu(), torch.zeros(12, 201, 60))
+
+
 # ---- training ---------------------------------------------------------------------------------------------------------------------------
 @contextlib.contextmanager
 def _deterministic(on):
