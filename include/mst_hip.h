@@ -298,6 +298,39 @@ int mst_crop_or_pad(const float* src, int s0, int s1, int s2, float* dst, int t0
                     float pad_value, void* ws, size_t ws_bytes, mst_stream_t stream);
 size_t mst_znorm_state_bytes(void);
 int mst_znorm(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, mst_stream_t stream);
+/* mst_crop_or_pad_at: mst_crop_or_pad with the begin offsets given per axis instead of the centre rule -- CropOrPad(random_center=True)
+ *   (augmentations_3d.py:166-195: the crop begin `ini` is uniform in 0..excess, l.170; the leading pad `r` uniform in 0..total pad,
+ *   l.184-188); the caller draws them.  crop_a in 0..max(s_a - t_a, 0), pad_a in 0..max(t_a - s_a, 0), refused otherwise.  With the centre
+ *   values ceil(excess / 2) and ceil(total / 2) it is mst_crop_or_pad.  Same workspace. */
+int mst_crop_or_pad_at(const float* src, int s0, int s1, int s2, float* dst, int t0, int t1, int t2, int crop0, int crop1, int crop2,
+                       int pad0, int pad1, int pad2, int pad_minimum, float pad_value, void* ws, size_t ws_bytes, mst_stream_t stream);
+
+/* Training augmentation of a batch of volumes on the device: what the reference's datasets apply behind ZNormalization on CPU workers
+ * (mst/data/datasets/dataset_3d_duke.py:44-47; the same lines in dataset_3d_lidc.py and dataset_3d_mrnet.py), in their order:
+ *   tio.RandomAffine(scales=0, degrees=(0,0,0,0,0,90), translation=0, default_pad_value='minimum')   l.44  rotation about the slice axis
+ *   tio.RandomFlip((0, 1, 2))                                                                        l.45
+ *   tio.Lambda(lambda x: -x if torch.rand((1,))[0] < 0.5 else x)                                     l.46
+ *   tio.RandomNoise(std=(0.0, 0.25))                                                                 l.47
+ * mst_augment_volumes: in [n, D, H, W] (in_dtype: fp32 / fp16 / bf16) -> out, the same shape (out_dtype likewise; out != in: a gather).
+ *   params [n, 8] fp32 in device memory, one record per volume: cos t, sin t, fill, sign, noise_std, flipD, flipH, flipW (a flip is
+ *   taken when its float is non-zero).  Output voxel (d, h, w) reads the rotated volume at (d', h', w'), a flipped axis reversed
+ *   (d' = D-1-d, ...).  The rotation is in the H-W plane, the same for every slice: c_h = (H-1)/2, c_w = (W-1)/2, y = h' - c_h,
+ *   x = w' - c_w,  s_h = c_h + cos t y - sin t x,  s_w = c_w + sin t y + cos t x;  the sample is bilinear with neighbour indices clamped
+ *   to the grid; it is inside iff -0.5 <= s_h < H-0.5 and -0.5 <= s_w < W-0.5, otherwise the value is `fill`.  cos t == 1 and
+ *   sin t == 0 copies the voxel bit for bit.  The value is then multiplied by sign and noise_std N(0,1) is added (nothing is drawn
+ *   when noise_std == 0).  N(0,1): Philox4x32-10 keyed by `seed`, counter words (g, 0, c_lo, c_hi) with g = (linear voxel index in its
+ *   volume) / 4 and c = counter + volume index, the four output words serving voxels 4g..4g+3 through two Box-Muller pairs
+ *   (u = ((word >> 9) + 0.5) / 2^23; z0, z1 = sqrt(-2 ln u0) (cos, sin)(2 pi u1)): a function of (seed, counter, volume, voxel) alone,
+ *   not of the launch geometry.  A 16-bit output is the fp32 result rounded once.  No floating-point atomics, no workspace.
+ *   NOT pinned against torchio / SimpleITK (neither is part of the reference tree): the rotation's sense, its centre and the edge rule
+ *   are the definition above.
+ * mst_volume_min: out[v * out_stride] = min of volume v of x [n, elems] (dtype), v < n -- the 'minimum' fill (default_pad_value), written
+ *   straight into the records when out = params + 2, out_stride = 8.  min is order-independent: integer atomics on the bit pattern,
+ *   branched on the sign bit (a -0.0 is a negative pattern: it cannot displace a negative minimum), the same bits under both modes of
+ *   torch.use_deterministic_algorithms.  NaNs are skipped. */
+int mst_augment_volumes(const void* in, int in_dtype, void* out, int out_dtype, int n, int D, int H, int W, const float* params,
+                        uint64_t seed, uint64_t counter, mst_stream_t stream);
+int mst_volume_min(const void* x, int dtype, int n, int64_t elems, float* out, int out_stride, mst_stream_t stream);
 
 /* slices2rgb (mst/models/dino.py:10-27; dead code in the reference: its call at dino.py:129 is commented out): three
  * consecutive gray slices become the channels of one image.  vol [B,1,D,H,W] (dtype) -> out [B*Dp/3, 3, H, W] with

@@ -128,13 +128,6 @@ __global__ void z_init_kernel(ZState* st) {
     for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x) (&st->hist[0][0])[i] = 0;
 }
 
-__device__ __forceinline__ void atomic_minf(float* a, float v) {   // bit-pattern trick, both signs
-    if (v >= 0.f) atomicMin((int*)a, __float_as_int(v)); else atomicMax((unsigned*)a, __float_as_uint(v));
-}
-__device__ __forceinline__ void atomic_maxf(float* a, float v) {
-    if (v >= 0.f) atomicMax((int*)a, __float_as_int(v)); else atomicMin((unsigned*)a, __float_as_uint(v));
-}
-
 __global__ void z_minmax_kernel(const float* __restrict__ x, int64_t n, ZState* st) {
     float mn = INFINITY, mx = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -143,7 +136,7 @@ __global__ void z_minmax_kernel(const float* __restrict__ x, int64_t n, ZState* 
         mx = fmaxf(mx, v);
     }
     for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
-    if ((threadIdx.x & 63) == 0) { atomic_minf(&st->mn, mn); atomic_maxf(&st->mx, mx); }
+    if ((threadIdx.x & 63) == 0) { atomic_min_f32(&st->mn, mn); atomic_max_f32(&st->mx, mx); }
 }
 
 __global__ void z_count_kernel(const float* __restrict__ x, int64_t n, ZState* st) {

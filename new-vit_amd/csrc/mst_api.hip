@@ -471,18 +471,19 @@ int mst_gradcampp(const float* act, const float* out, int O, const float* W, int
 }
 
 // ---- input pipeline ------------------------------------------------------------------------------------
-int mst_crop_or_pad(const float* src, int s0, int s1, int s2, float* dst, int t0, int t1, int t2, int pad_minimum,
-                    float pad_value, void* ws, size_t ws_bytes, mst_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    MST_CHECK_ARG(src && dst && s0 > 0 && s1 > 0 && s2 > 0 && t0 > 0 && t1 > 0 && t2 > 0, "crop_or_pad: bad arguments");
-    const int sn[3] = {s0, s1, s2}, tn[3] = {t0, t1, t2};
-    int pad_lo[3], pad_hi[3], crop_lo[3], pn[3];
+// crop begins cb[a] in 0..excess and leading pads pb[a] in 0..total pad, per axis (an axis is either cropped or padded, the other is 0)
+static int crop_or_pad_at(const float* src, const int sn[3], float* dst, const int tn[3], const int cb[3], const int pb[3], int pad_minimum,
+                          float pad_value, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int s0 = sn[0], s1 = sn[1], s2 = sn[2], t0 = tn[0], t1 = tn[1], t2 = tn[2];
+    int pad_lo[3], crop_lo[3], pn[3];
     bool any_pad = false;
-    for (int a = 0; a < 3; ++a) {                       // augmentations_3d.py:164-172: ini = ceil(n / 2), fin = n - ini
+    for (int a = 0; a < 3; ++a) {
         const int d = tn[a] - sn[a];
         const int p = d > 0 ? d : 0, c = d < 0 ? -d : 0;
-        pad_lo[a] = (p + 1) / 2; pad_hi[a] = p - pad_lo[a];
-        crop_lo[a] = (c + 1) / 2;
+        MST_CHECK_ARG(cb[a] >= 0 && cb[a] <= c && pb[a] >= 0 && pb[a] <= p, "crop_or_pad: axis %d: crop begin %d not in 0..%d or pad begin %d not in 0..%d",
+                      a, cb[a], c, pb[a], p);
+        pad_lo[a] = pb[a];
+        crop_lo[a] = cb[a];
         pn[a] = sn[a] + p;
         any_pad = any_pad || p > 0;
     }
@@ -501,6 +502,44 @@ int mst_crop_or_pad(const float* src, int s0, int s1, int s2, float* dst, int t0
     if (pn[2] > s2 && (rc = launch_pad_axis(pad, pn[0], pn[1], pn[2], 2, lo2, hi2, 0, pn[0], 0, pn[1], !pad_minimum, pad_value, s))) return rc;
     if (direct) return MST_OK;
     return launch_copy_block(pad, pn[1], pn[2], crop_lo[0], crop_lo[1], crop_lo[2], dst, t1, t2, 0, 0, 0, t0, t1, t2, s);
+}
+
+int mst_crop_or_pad(const float* src, int s0, int s1, int s2, float* dst, int t0, int t1, int t2, int pad_minimum,
+                    float pad_value, void* ws, size_t ws_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(src && dst && s0 > 0 && s1 > 0 && s2 > 0 && t0 > 0 && t1 > 0 && t2 > 0, "crop_or_pad: bad arguments");
+    const int sn[3] = {s0, s1, s2}, tn[3] = {t0, t1, t2};
+    int cb[3], pb[3];
+    for (int a = 0; a < 3; ++a) {                       // augmentations_3d.py:164-172: ini = ceil(n / 2), fin = n - ini
+        const int d = tn[a] - sn[a];
+        pb[a] = d > 0 ? (d + 1) / 2 : 0;
+        cb[a] = d < 0 ? (-d + 1) / 2 : 0;
+    }
+    return crop_or_pad_at(src, sn, dst, tn, cb, pb, pad_minimum, pad_value, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int mst_crop_or_pad_at(const float* src, int s0, int s1, int s2, float* dst, int t0, int t1, int t2, int crop0, int crop1, int crop2,
+                       int pad0, int pad1, int pad2, int pad_minimum, float pad_value, void* ws, size_t ws_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(src && dst && s0 > 0 && s1 > 0 && s2 > 0 && t0 > 0 && t1 > 0 && t2 > 0, "crop_or_pad_at: bad arguments");
+    const int sn[3] = {s0, s1, s2}, tn[3] = {t0, t1, t2}, cb[3] = {crop0, crop1, crop2}, pb[3] = {pad0, pad1, pad2};
+    return crop_or_pad_at(src, sn, dst, tn, cb, pb, pad_minimum, pad_value, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- training augmentation (k_augment.hip) -----------------------------------------------------------------------------
+static bool aug_dtype(int dt) { return dt == MST_F32 || dt == MST_F16 || dt == MST_BF16; }
+
+int mst_augment_volumes(const void* in, int in_dtype, void* out, int out_dtype, int n, int D, int H, int W, const float* params,
+                        uint64_t seed, uint64_t counter, mst_stream_t stream) {
+    MST_CHECK_ARG(in && out && params && in != out && n > 0 && D > 0 && H > 0 && W > 0, "augment_volumes: bad arguments (the kernel gathers: not in place)");
+    MST_CHECK_ARG(aug_dtype(in_dtype) && aug_dtype(out_dtype), "augment_volumes: bad dtype %d -> %d", in_dtype, out_dtype);
+    MST_CHECK_ARG(n <= 65535 && (int64_t)D * H * W <= 0x7ffffff0ll, "augment_volumes: n=%d volumes of %d x %d x %d (at most 65535 volumes of < 2^31 voxels)",
+                  n, D, H, W);
+    return launch_augment_volumes(in, in_dtype, out, out_dtype, n, D, H, W, params, seed, counter, (hipStream_t)stream);
+}
+
+int mst_volume_min(const void* x, int dtype, int n, int64_t elems, float* out, int out_stride, mst_stream_t stream) {
+    MST_CHECK_ARG(x && out && n > 0 && n <= 65535 && elems > 0 && out_stride > 0, "volume_min: bad arguments");
+    MST_CHECK_ARG(aug_dtype(dtype), "volume_min: bad dtype %d", dtype);
+    return launch_volume_min(x, dtype, n, elems, out, out_stride, (hipStream_t)stream);
 }
 
 size_t mst_znorm_state_bytes(void) { return znorm_state_bytes(); }

@@ -69,6 +69,17 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// min / max of floats across workgroups by INTEGER atomics on the bit pattern (order-independent, so the same bits whatever the arrival
+// order; *a starts at +inf / -inf).  The branch is on the SIGN BIT, not on v >= 0: -0.0 has the pattern 0x80000000 = INT_MIN and, sent
+// down the signed path, would overwrite any negative minimum stored before it (and never raise a maximum above -inf).  Patterns with the sign
+// clear order like signed ints; with it set, a larger unsigned pattern is a smaller float.  NaNs are the caller's to keep out (fminf / fmaxf).
+__device__ __forceinline__ void atomic_min_f32(float* a, float v) {
+    if (__float_as_int(v) >= 0) atomicMin((int*)a, __float_as_int(v)); else atomicMax((unsigned*)a, __float_as_uint(v));
+}
+__device__ __forceinline__ void atomic_max_f32(float* a, float v) {
+    if (__float_as_int(v) >= 0) atomicMax((int*)a, __float_as_int(v)); else atomicMin((unsigned*)a, __float_as_uint(v));
+}
+
 __device__ __forceinline__ float gelu_erf(float v) {  // nn.GELU() exact form (mlp.py:22)
     return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
 }
@@ -456,6 +467,10 @@ int launch_pad_axis(float* v, int n0, int n1, int n2, int axis, int lo, int hi, 
 int launch_copy_block(const float* src, int sn1, int sn2, int s0, int s1, int s2, float* dst, int dn1, int dn2, int d0, int d1,
                       int d2, int c0, int c1, int c2, hipStream_t s);
 int launch_znorm(const float* x, int64_t n, float q_lo, float q_hi, float* y, void* state, hipStream_t s);
+// training augmentation (k_augment.hip): in / out of types idt / odt, params [n, 8] fp32; the per-volume minimum to out[v * stride]
+int launch_augment_volumes(const void* in, int idt, void* out, int odt, int n, int D, int H, int W, const float* params, uint64_t seed,
+                           uint64_t counter, hipStream_t s);
+int launch_volume_min(const void* x, int dt, int n, int64_t elems, float* out, int stride, hipStream_t s);
 // fixed-order reductions (k_colsum.hip, k_ordered.hip, and the ordered forms in k_train.hip / k_bn.hip / k_input.hip): bit-reproducible for fixed
 // shape arguments, no floating-point atomics
 size_t colsum_ordered_workspace_bytes(int64_t rows, int cols, int outputs, int ty = 16);

@@ -136,6 +136,9 @@ SIGNATURES = {
     "mst_crop_or_pad": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "mst_znorm_state_bytes": (_sz, []),
     "mst_znorm": (_i, [_vp, _i64, _f, _f, _vp, _vp, _vp]),
+    "mst_crop_or_pad_at": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "mst_augment_volumes": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, C.c_uint64, _vp]),
+    "mst_volume_min": (_i, [_vp, _i, _i, _i64, _vp, _i, _vp]),
     "mst_slices2rgb": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mst_patch_embed": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "mst_vit_workspace_bytes": (_sz, [C.POINTER(VitWeights), _i, _i, _i]),
@@ -564,6 +567,47 @@ def slices2rgb(vol: torch.Tensor) -> torch.Tensor:
     Dp = (D + 2) // 3 * 3
     out = torch.empty((B * Dp // 3, 3, H, W), dtype=vol.dtype, device=vol.device)
     _check(load().mst_slices2rgb(ptr(vol), dt_of(vol), B, D, H, W, ptr(out), stream_of(vol)), "mst_slices2rgb")
+    return out
+
+
+AUG_COS, AUG_SIN, AUG_FILL, AUG_SIGN, AUG_STD, AUG_FLIP_D, AUG_FLIP_H, AUG_FLIP_W, AUG_REC = 0, 1, 2, 3, 4, 5, 6, 7, 8    # record of mst_augment_volumes
+
+
+def volume_min(x: torch.Tensor, out: Optional[torch.Tensor] = None, column: int = 0) -> torch.Tensor:
+    """mst_volume_min: the minimum of every volume of x [n, ...] (fp32 / fp16 / bf16) as fp32 [n]; or, out fp32 [n, K] given, written into
+    out[:, column] (the fill of mst_augment_volumes' records) and out returned."""
+    _operand(x, "volume_min", "x", (torch.float32,) + _T16)
+    if x.dim() < 2 or 0 in x.shape:
+        raise ValueError(f"volume_min: x must be [n, ...] and not empty, got {list(x.shape)}")
+    n = x.shape[0]
+    if out is not None:
+        _operand(out, "volume_min", "out", (torch.float32,))
+        if out.dim() != 2 or out.shape[0] != n or not 0 <= column < out.shape[1]:
+            raise ValueError(f"volume_min: out must be [{n}, > {column}], got {list(out.shape)}")
+    _resident("volume_min", x=x, out=out)
+    res = out if out is not None else torch.empty((n, 1), dtype=torch.float32, device=x.device)
+    _check(load().mst_volume_min(ptr(x), dt_of(x), n, x.numel() // n, res.data_ptr() + 4 * column, res.shape[1], stream_of(x)), "mst_volume_min")
+    return out if out is not None else res[:, 0]
+
+
+def augment_volumes(x: torch.Tensor, params: torch.Tensor, seed: int = 0, counter: int = 0,
+                    out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """mst_augment_volumes: x [n, D, H, W] (fp32 / fp16 / bf16) rotated in plane, flipped, sign-inverted and noised per its record
+    params [n, 8] fp32 (cos, sin, fill, sign, noise_std, flipD, flipH, flipW; include/mst_hip.h) -> a new tensor of out_dtype (x's own
+    by default).  seed / counter: the 64-bit Philox key and the counter of volume 0 (volume v uses counter + v)."""
+    _operand(x, "augment_volumes", "x", (torch.float32,) + _T16)
+    if x.dim() != 4 or 0 in x.shape:
+        raise ValueError(f"augment_volumes: x must be [n, D, H, W] and not empty, got {list(x.shape)}")
+    n, D, H, W = x.shape
+    _operand(params, "augment_volumes", "params", (torch.float32,), (n, AUG_REC))
+    out_dtype = out_dtype or x.dtype
+    if out_dtype not in _DT:
+        raise TypeError(f"augment_volumes: out_dtype {out_dtype} (float32, float16, bfloat16)")
+    _resident("augment_volumes", x=x, params=params)
+    out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    mask = (1 << 64) - 1
+    _check(load().mst_augment_volumes(ptr(x), dt_of(x), ptr(out), _DT[out_dtype], n, D, H, W, ptr(params), int(seed) & mask, int(counter) & mask,
+                                      stream_of(x)), "mst_augment_volumes")
     return out
 
 

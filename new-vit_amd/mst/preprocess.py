@@ -1,21 +1,35 @@
 """Device-side input pipeline: the two array transforms the reference's datasets apply to a volume before the
-model -- ``CropOrPad`` (deterministic centre) and ``ZNormalization`` of mst/data/datasets/augmentations/augmentations_3d.py
-(l.144-195, l.40-86; e.g. dataset_3d_duke.py:42-43) -- as HIP kernels behind the C ABI (mst_crop_or_pad, mst_znorm), so that a
+model -- ``CropOrPad`` (deterministic or random centre) and ``ZNormalization`` of mst/data/datasets/augmentations/augmentations_3d.py
+(l.144-195, l.40-86; e.g. dataset_3d_duke.py:42-43) -- as HIP kernels behind the C ABI (mst_crop_or_pad, mst_crop_or_pad_at, mst_znorm), so that a
 volume can go loader -> HBM -> encoder without the host round trip.  Same argument meaning as the reference's classes; tensors are
 ``[C, D, H, W]`` (what ``ImageOrSubjectToTensor`` hands to the model), the spatial target in the same axis order."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Sequence, Tuple, Union
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import hip
 
 
-def crop_or_pad(x: torch.Tensor, target_shape: Sequence[int], padding_mode: Union[str, float] = 0) -> torch.Tensor:
-    """CropOrPad(target_shape, padding_mode, random_center=False): centre crop / pad of every channel of ``x`` [C, a0, a1, a2].
-    padding_mode: 'minimum' (numpy.pad 'minimum', the datasets' choice) or a number (constant)."""
+def draw_crop_offsets(source_shape: Sequence[int], target_shape: Sequence[int], generator: Optional[torch.Generator] = None):
+    """The draws of CropOrPad(random_center=True) (augmentations_3d.py:166-195) for one volume: per axis the crop begin, uniform in
+    0..excess (l.170), and the leading pad, uniform in 0..total pad (l.184-188) -> (crop_begin, pad_begin), three ints each.  Six draws from
+    `generator` (torch's default one when None), axis by axis, crop before pad, whatever the shapes."""
+    crop, pad = [], []
+    for s, t in zip(source_shape, target_shape):
+        excess, total = max(int(s) - int(t), 0), max(int(t) - int(s), 0)
+        crop.append(int(torch.randint(0, excess + 1, (1,), generator=generator)))
+        pad.append(int(torch.randint(0, total + 1, (1,), generator=generator)))
+    return crop, pad
+
+
+def crop_or_pad(x: torch.Tensor, target_shape: Sequence[int], padding_mode: Union[str, float] = 0, random_center: bool = False,
+                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """CropOrPad(target_shape, padding_mode, random_center): crop / pad of every channel of ``x`` [C, a0, a1, a2].
+    padding_mode: 'minimum' (numpy.pad 'minimum', the datasets' choice) or a number (constant).  random_center=False: the centre rule;
+    True: the begin offsets of draw_crop_offsets(x.shape[1:], target_shape, generator), one draw for all channels."""
     if x.dim() != 4:
         raise ValueError("crop_or_pad expects [C, D, H, W]")
     if not x.is_cuda:
@@ -29,10 +43,16 @@ def crop_or_pad(x: torch.Tensor, target_shape: Sequence[int], padding_mode: Unio
     pn = [max(a, b) for a, b in zip((s0, s1, s2), t)]
     ws = torch.empty(pn[0] * pn[1] * pn[2], dtype=torch.float32, device=x.device)
     lib = hip.load()
+    mode = (1 if padding_mode == "minimum" else 0, 0.0 if padding_mode == "minimum" else float(padding_mode))
+    if random_center:
+        crop, pad = draw_crop_offsets((s0, s1, s2), t, generator)
     for c in range(Cn):
-        hip._check(lib.mst_crop_or_pad(hip.ptr(x[c]), s0, s1, s2, hip.ptr(out[c]), t[0], t[1], t[2],
-                                       1 if padding_mode == "minimum" else 0, 0.0 if padding_mode == "minimum" else float(padding_mode),
-                                       hip.ptr(ws), ws.numel() * 4, hip.stream_of(x)), "mst_crop_or_pad")
+        if random_center:
+            hip._check(lib.mst_crop_or_pad_at(hip.ptr(x[c]), s0, s1, s2, hip.ptr(out[c]), t[0], t[1], t[2], *crop, *pad, *mode,
+                                              hip.ptr(ws), ws.numel() * 4, hip.stream_of(x)), "mst_crop_or_pad_at")
+        else:
+            hip._check(lib.mst_crop_or_pad(hip.ptr(x[c]), s0, s1, s2, hip.ptr(out[c]), t[0], t[1], t[2], *mode,
+                                           hip.ptr(ws), ws.numel() * 4, hip.stream_of(x)), "mst_crop_or_pad")
     return out
 
 
