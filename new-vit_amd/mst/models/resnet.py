@@ -12,6 +12,9 @@ parameter containers; the arithmetic runs in HIP kernels through the C ABI:
              BatchNorm folded into weight and bias and ReLU / the residual add in the GEMM epilogue; ``mst_maxpool_nhwc``,
              ``mst_avgpool_nhwc``.  Gray -> RGB (``x.repeat(1, 3, ...)``, resnet.py:176) is folded into conv1 (the three input
              channels are identical, so their kernels are summed).
+  units      what a residual unit IS -- its chain of convolutions, which one takes the shortcut, the downsample -- is stated once, by
+             ``_Unit.chain()`` / ``_Unit.shortcut()``; ``_fold_backbone`` turns it into ``Folded`` records that carry their geometry, and
+             ``backbone_chunk`` is the one walk over them: the inference forward and the eval-mode gradient forward are that function.
   fusion     ``mst_slice_fusion`` -- the kernels of DinoV2ClassifierSlice's Slice Transformer with nhead 16, E 512.
 
 torchvision's source is not part of the reference tree: the published resnet architecture is restated, parity of
@@ -37,7 +40,7 @@ from __future__ import annotations
 import math
 import os
 import warnings
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -82,7 +85,16 @@ class _Linear(_P):
         nn.init.uniform_(self.bias, -1 / math.sqrt(cin), 1 / math.sqrt(cin))
 
 
-class _BasicBlock(_P):
+class _Unit(_P):
+    """A residual unit: a chain of convolutions, each (conv, bn, k, stride, pad) with ReLU behind its BatchNorm; the LAST one takes the
+    shortcut before its ReLU.  The shortcut is the identity (None) or a 1 x 1 downsample.  Every pass over the backbone -- the weight
+    fold, the inference / eval-gradient walk, the training step and their backwards -- reads the unit's structure from here."""
+
+    def shortcut(self):
+        return (self.downsample[0], self.downsample[1], 1, self.stride, 0) if hasattr(self, "downsample") else None
+
+
+class _BasicBlock(_Unit):
     def __init__(self, cin, cout, stride):
         super().__init__()
         self.conv1, self.bn1 = _Conv(cin, cout, 3), _BN(cout)
@@ -91,8 +103,11 @@ class _BasicBlock(_P):
         if stride != 1 or cin != cout:
             self.downsample = nn.ModuleList([_Conv(cin, cout, 1), _BN(cout)])       # keys downsample.0.* / downsample.1.*
 
+    def chain(self):
+        return [(self.conv1, self.bn1, 3, self.stride, 1), (self.conv2, self.bn2, 3, 1, 1)]
 
-class _Bottleneck(_P):
+
+class _Bottleneck(_Unit):
     """torchvision Bottleneck (v1.5): 1x1 -> 3x3 (carries the stride) -> 1x1 (x4), each with its BatchNorm (models 50 / 101 / 152:
     reference resnet.py:44-50 takes whichever torchvision model `model` names; emb_ch 2048, resnet.py:152)."""
 
@@ -104,6 +119,9 @@ class _Bottleneck(_P):
         self.stride = stride
         if stride != 1 or cin != 4 * w:
             self.downsample = nn.ModuleList([_Conv(cin, 4 * w, 1), _BN(4 * w)])
+
+    def chain(self):
+        return [(self.conv1, self.bn1, 1, 1, 0), (self.conv2, self.bn2, 3, self.stride, 1), (self.conv3, self.bn3, 1, 1, 0)]
 
 
 class _TVResNet(_P):
@@ -129,6 +147,14 @@ class _TVResNet(_P):
         self.out_features = cin
         self.fc = nn.Identity() if fc_out is None else _Linear(cin, fc_out)
 
+    def units(self):                                     # in forward order
+        return [blk for li in range(4) for blk in getattr(self, f"layer{li + 1}")]
+
+
+def conv_out(size: int, k: int, stride: int, pad: int) -> int:
+    """Output extent of a convolution (or pooling window) along one axis."""
+    return (size + 2 * pad - k) // stride + 1
+
 
 def _conv(x: torch.Tensor, w: torch.Tensor, b, k: int, stride: int, pad: int, kpad: int, epilogue: int, out=None) -> torch.Tensor:
     """One convolution of the backbone on an NHWC activation -> [n*Ho*Wo, Cout]: the implicit GEMM (mst_conv_gemm) when the input
@@ -136,14 +162,24 @@ def _conv(x: torch.Tensor, w: torch.Tensor, b, k: int, stride: int, pad: int, kp
     n, H, W, cin = x.shape
     if x.dtype != torch.float32:                         # compute_dtype bf16 / fp16: the implicit GEMM on 16-bit MFMA operands (Cin % 64 == 0)
         return hip.conv_gemm16(x, w, b, k, k, stride, pad, epilogue=epilogue, out=out)
-    rows = n * ((H + 2 * pad - k) // stride + 1) * ((W + 2 * pad - k) // stride + 1)
+    rows = n * conv_out(H, k, stride, pad) * conv_out(W, k, stride, pad)
     # up to 1,024 output pixels mst_gemm has its 32 x 32-tile kernel (k_gemm32s.hip), which fills the chip where 128 x 128 tiles cannot
     if cin % 16 == 0 and rows > 1024 and os.environ.get("MST_CONV_IM2COL", "0") != "1":
         return hip.conv_gemm(x, w, b, k, k, stride, pad, epilogue=epilogue, out=out)
     return hip.gemm(hip.im2col_nhwc(x, k, k, stride, pad, kpad), w, b, epilogue=epilogue, out=out)
 
 
-def _fold(conv: _Conv, bn: _BN, sum_in: bool, dev, dtype: torch.dtype = torch.float32, kmul: int = 16):
+class Folded(NamedTuple):
+    """One convolution with its eval-mode BatchNorm folded in: the GEMM operands and the geometry every walk needs."""
+    w: torch.Tensor
+    b: torch.Tensor
+    kpad: int
+    k: int
+    stride: int
+    pad: int
+
+
+def _fold(conv: _Conv, bn: _BN, k: int, stride: int, pad: int, sum_in: bool, dev, dtype: torch.dtype = torch.float32, kmul: int = 16) -> Folded:
     """Eval-mode BatchNorm folded into the convolution: GEMM weight [Cout, Kpad] in (ky, kx, c) order (fp32, or rounded to the 16-bit
     compute type AFTER the fold) + bias [Cout] fp32; K padded to a multiple of kmul."""
     w = conv.weight.detach().to(dev, torch.float32)
@@ -156,7 +192,54 @@ def _fold(conv: _Conv, bn: _BN, sum_in: bool, dev, dtype: torch.dtype = torch.fl
     kpad = (K + kmul - 1) // kmul * kmul
     if kpad != K:
         w = torch.cat([w, w.new_zeros(w.shape[0], kpad - K)], dim=1)
-    return w.to(dtype).contiguous(), b.contiguous(), kpad
+    return Folded(w.to(dtype).contiguous(), b.contiguous(), kpad, k, stride, pad)
+
+
+def _conv_folded(x: torch.Tensor, f: Folded, epilogue: int, out=None) -> torch.Tensor:
+    """`_conv` of a folded record -> NHWC [n, Ho, Wo, Cout] (a view of `out` when one is given)."""
+    n, H, W, _ = x.shape
+    y = _conv(x, f.w, f.b, f.k, f.stride, f.pad, f.kpad, epilogue, out)
+    return y.view(n, conv_out(H, f.k, f.stride, f.pad), conv_out(W, f.k, f.stride, f.pad), f.w.shape[0])
+
+
+def backbone_chunk(p, x: torch.Tensor, keep: Optional[list] = None) -> torch.Tensor:
+    """Stem, max pool and every residual unit for one chunk of images [n, H, W, C] fp32 on the prepared weights `p` -> the last ReLU
+    output [n, h, w, C'] in p's activation type.  The ONE walk over the folded backbone: the inference forward (`ResNet._features`) and
+    the eval-mode gradient node (mst/train_resnet.py) both run it, so their bits cannot drift apart.
+
+    keep None: relu(identity + .) of a unit without downsample is formed in place on the unit's input, which is dead after it, and
+    nothing outlives its last reader.  keep a list: the backward needs every ReLU output (its mask), so that sum goes into a copy -- the
+    same kernels on the same operands -- and keep receives the stem's output before the pool, then per unit (input shape, [the ReLU
+    outputs in chain order, the unit's output last])."""
+    st = p["stem"]
+    if p["dtype"] == torch.float32:
+        y = _conv_folded(x, st, hip.EPI_BIAS_RELU)       # Cin 1 or 3: mst_im2col_nhwc + mst_gemm
+    else:
+        # the stem's 49 taps of ONE input channel are no multiple of 64 channels: its im2col rows (padded to 64, rounded on the way out)
+        # are the "pixels" of a 1 x 1 convolution; everything behind it, the max pool included, is 16-bit
+        n, H, W, _ = x.shape
+        Ho, Wo = conv_out(H, st.k, st.stride, st.pad), conv_out(W, st.k, st.stride, st.pad)
+        col = hip.im2col_nhwc(x, st.k, st.k, st.stride, st.pad, st.kpad, out_dtype=p["dtype"]).view(n, Ho, Wo, st.kpad)
+        y = hip.conv_gemm16(col, st.w, st.b, 1, 1, 1, 0, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, 64)
+        del col
+    if keep is not None:
+        keep.append(y)
+    y = hip.maxpool_nhwc(y)
+    for u in p["blocks"]:
+        h, acts = y, []
+        for f in u["chain"][:-1]:
+            h = _conv_folded(h, f, hip.EPI_BIAS_RELU)
+            if keep is not None:
+                acts.append(h)
+        if u["ds"] is not None:
+            idt = _conv_folded(y, u["ds"], hip.EPI_BIAS)
+        else:
+            idt = y if keep is None else y.clone()       # y carries the previous unit's ReLU mask: a backward still reads it
+        shape_in = y.shape
+        y = _conv_folded(h, u["chain"][-1], hip.EPI_RESIDUAL_RELU, out=idt.view(-1, idt.shape[-1]))     # relu(identity + bn(conv(.)))
+        if keep is not None:
+            keep.append((shape_in, acts + [y]))
+    return y
 
 
 class ResNet(BasicClassifier):
@@ -222,15 +305,11 @@ class ResNet(BasicClassifier):
             raise RuntimeError(f"ResNet runs on an MI355X only: parameters are on {dev}; call .to('cuda'). There is no CPU fallback.")
         m = self.model
         # 16-bit: the stem's im2col rows are padded to 64 columns so that they are one "pixel" of a 1 x 1 convolution for mst_conv_gemm16
-        prep = {"dtype": cdt, "stem": _fold(m.conv1, m.bn1, sum_in, dev, cdt, 16 if cdt == torch.float32 else 64), "blocks": []}
-        for li in range(4):
-            for blk in getattr(m, f"layer{li + 1}"):
-                e = {"stride": blk.stride, "c1": _fold(blk.conv1, blk.bn1, False, dev, cdt), "c2": _fold(blk.conv2, blk.bn2, False, dev, cdt)}
-                if hasattr(blk, "conv3"):
-                    e["c3"] = _fold(blk.conv3, blk.bn3, False, dev, cdt)
-                if hasattr(blk, "downsample"):
-                    e["ds"] = _fold(blk.downsample[0], blk.downsample[1], False, dev, cdt)
-                prep["blocks"].append(e)
+        prep = {"dtype": cdt, "stem": _fold(m.conv1, m.bn1, 7, 2, 3, sum_in, dev, cdt, 16 if cdt == torch.float32 else 64), "blocks": []}
+        for blk in m.units():
+            ds = blk.shortcut()
+            prep["blocks"].append({"chain": [_fold(*c, False, dev, cdt) for c in blk.chain()],
+                                   "ds": None if ds is None else _fold(*ds, False, dev, cdt)})
         if not isinstance(m.fc, nn.Identity):
             prep["fc"] = (m.fc.weight.detach().to(dev, torch.float32).contiguous(), m.fc.bias.detach().to(dev, torch.float32).contiguous())
         return prep
@@ -243,46 +322,7 @@ class ResNet(BasicClassifier):
         lasts: List[torch.Tensor] = []
         for i0 in range(0, x_nhwc.shape[0], self.chunk_images):
             x = x_nhwc[i0:i0 + self.chunk_images].contiguous()
-            n, H, W, _ = x.shape
-            w, b, kpad = p["stem"]
-            Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-            if p["dtype"] == torch.float32:
-                y = hip.gemm(hip.im2col_nhwc(x, 7, 7, 2, 3, kpad), w, b, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, 64)
-                y = hip.maxpool_nhwc(y)
-            else:
-                # the stem's 49 taps of ONE input channel are no multiple of 64 channels: its im2col rows (padded to 64, rounded on the way out)
-                # are the "pixels" of a 1 x 1 convolution; everything behind it, the max pool included, is 16-bit
-                col = hip.im2col_nhwc(x, 7, 7, 2, 3, kpad, out_dtype=p["dtype"]).view(n, Ho, Wo, kpad)
-                y = hip.conv_gemm16(col, w, b, 1, 1, 1, 0, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, 64)
-                del col
-                y = hip.maxpool_nhwc(y)
-            for e in p["blocks"]:
-                n, H, W, Cin = y.shape
-                s = e["stride"]
-                Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
-                w1, b1, k1 = e["c1"]
-                if "c3" in e:                            # bottleneck: 1x1 -> 3x3 (stride) -> 1x1, the residual joins after the third
-                    h0 = _conv(x=y, w=w1, b=b1, k=1, stride=1, pad=0, kpad=k1, epilogue=hip.EPI_BIAS_RELU).view(n, H, W, w1.shape[0])
-                    w2, b2, k2 = e["c2"]
-                    h1 = _conv(x=h0, w=w2, b=b2, k=3, stride=s, pad=1, kpad=k2, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, w2.shape[0])
-                    if "ds" in e:
-                        wd, bd, kd = e["ds"]
-                        idt = _conv(x=y, w=wd, b=bd, k=1, stride=s, pad=0, kpad=kd, epilogue=hip.EPI_BIAS)
-                    else:
-                        idt = y.reshape(n * H * W, Cin)          # the unit's input is dead after it: the sum is formed in place
-                    w3, b3, k3 = e["c3"]
-                    _conv(x=h1, w=w3, b=b3, k=1, stride=1, pad=0, kpad=k3, epilogue=hip.EPI_RESIDUAL_RELU, out=idt)
-                    y = idt.view(n, Ho, Wo, w3.shape[0])
-                    continue
-                h1 = _conv(x=y, w=w1, b=b1, k=3, stride=s, pad=1, kpad=k1, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, w1.shape[0])
-                if "ds" in e:
-                    wd, bd, kd = e["ds"]
-                    idt = _conv(x=y, w=wd, b=bd, k=1, stride=s, pad=0, kpad=kd, epilogue=hip.EPI_BIAS)
-                else:
-                    idt = y.reshape(n * H * W, Cin)              # the unit's input is dead after it: the sum is formed in place
-                w2, b2, k2 = e["c2"]
-                _conv(x=h1, w=w2, b=b2, k=3, stride=1, pad=1, kpad=k2, epilogue=hip.EPI_RESIDUAL_RELU, out=idt)  # relu(identity + bn2(conv2(.)))
-                y = idt.view(n, Ho, Wo, w2.shape[0])
+            y = backbone_chunk(p, x)
             if y.dtype != torch.float32:
                 y = hip.cvt32(y)                         # the average pool and Grad-CAM++ read fp32
             outs.append(hip.avgpool_nhwc(y))

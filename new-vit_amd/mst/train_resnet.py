@@ -26,8 +26,12 @@ convolution input beside it).  Checked against torch.autograd of oracle/resnet_o
 Gradient with respect to the input volume: the node returns d x_nhwc when its source requires grad (`backbone_bwd(need_source=True)`),
 and torch carries it through the model's own float() / permute / reshape to the source's shape, dtype and device.  The backward is pruned
 to what is asked for (`_Grads(needed=...)` from needs_input_grad): a frozen model's source-only backward forms no weight gradient.  A frozen
-model in eval mode has its own node on the BatchNorm-folded weights (`_ResNetEvalFunction`, fp32, chunked like the inference forward).
+model in eval mode has its own node on the BatchNorm-folded weights (`_ResNetEvalFunction`, fp32); its forward IS the inference walk
+(mst/models/resnet.py::backbone_chunk, with a keep list), chunked like it.
 Checked against float64 torch.autograd through the oracle (tests/test_resnet_input_grad_gpu.py).
+
+What a residual unit is lives in one place, `_Unit.chain()` / `_Unit.shortcut()` (mst/models/resnet.py): `backbone_fwd` / `backbone_bwd`
+walk that chain over `_conv_bn_fwd` records, `_eval_backbone_bwd` walks it over the `Folded` records, which carry k, stride and pad.
 
 The mode (train_precision, train_storage and the autocast rule) is described, validated and resolved in mst/train_mode.py;
 `forward_train` resolves it once and the saved state and every unit's record carry it to the backward.
@@ -46,7 +50,7 @@ import torch
 import torch.nn as nn
 
 from . import hip, train_mode
-from .models.resnet import _conv
+from .models.resnet import SLICE_HEADS, _conv, backbone_chunk, conv_out
 from .train import _Grads, fp32_device_params, fusion_bwd, fusion_fwd, route_grads
 
 
@@ -74,7 +78,7 @@ def _conv_bn_fwd(x: torch.Tensor, conv, bn, k: int, stride: int, pad: int, sum_i
         train_mode.check(False, "stored", "16bit", needs_flash=False)        # raises: 16-bit storage without a 16-bit type
     n, H, W, Cin = x.shape
     wg = _gemm_weight(conv, sum_in)
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Ho, Wo = conv_out(H, k, stride, pad), conv_out(W, k, stride, pad)
     Cout, K = wg.shape[0], k * k * Cin
     zdt = mp if storage16 else torch.float32
     x16 = col16 = None
@@ -164,7 +168,7 @@ def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool 
         G.put(conv.weight, dw.contiguous())
     if not need_dx:
         return None
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Ho, Wo = conv_out(H, k, stride, pad), conv_out(W, k, stride, pad)
     g = dz if mp is None else dz16
     if Cin < 4 and implicit:
         # the stem (one input channel after the gray fold, or three): mst_conv_dgrad_stem multiplies dz by the FORWARD's GEMM weight (the
@@ -187,32 +191,29 @@ def _conv_bn_bwd(G: _Grads, rec, dy: torch.Tensor, need_dx: bool, mask_dy: bool 
 
 def _shortcut(y: torch.Tensor, blk, mp: Optional[torch.dtype], storage16: bool):
     """The residual operand [rows, C] of the unit that closes `blk`, and the downsample unit's record (None: the identity)."""
-    rd = None
-    if hasattr(blk, "downsample"):
-        y, rd = _conv_bn_fwd(y, blk.downsample[0], blk.downsample[1], 1, blk.stride, 0, False, None, False, mp, storage16)
+    rd, ds = None, blk.shortcut()
+    if ds is not None:
+        y, rd = _conv_bn_fwd(y, *ds, False, None, False, mp, storage16)
     return y.reshape(-1, y.shape[-1]), rd
 
 
 def backbone_fwd(m, x_nhwc: torch.Tensor, sum_in: bool, mp: Optional[torch.dtype] = None, storage16: bool = False):
     """torchvision resnet{18,34,50,101,152} forward in train mode up to the pooled features [n, 512 or 2048].  storage16: every activation
-    between the stem's im2col and the average pool lives in mp (max pool: mst_maxpool_nhwc16, features: mst_avgpool_nhwc16)."""
+    between the stem's im2col and the average pool lives in mp (max pool: mst_maxpool_nhwc16, features: mst_avgpool_nhwc16).
+    sv["units"]: per unit the records of its chain in forward order, then the downsample unit's record (None: the identity)."""
     sv = {"units": [], "mp": mp, "storage": "16bit" if storage16 else "fp32"}
     y, sv["stem"] = _conv_bn_fwd(x_nhwc.contiguous(), m.conv1, m.bn1, 7, 2, 3, sum_in, None, True, mp, storage16)
     sv["pool_in"] = y
     y = hip.maxpool_nhwc(y)
-    for li in range(4):
-        for blk in getattr(m, f"layer{li + 1}"):
-            if hasattr(blk, "conv3"):                                    # bottleneck: 1x1 -> 3x3 (stride) -> 1x1 + residual
-                h0, r0 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 1, 1, 0, False, None, True, mp, storage16)
-                h1, r1 = _conv_bn_fwd(h0, blk.conv2, blk.bn2, 3, blk.stride, 1, False, None, True, mp, storage16)
-                idt, rd = _shortcut(y, blk, mp, storage16)
-                y, r2 = _conv_bn_fwd(h1, blk.conv3, blk.bn3, 1, 1, 0, False, idt, True, mp, storage16)
-                sv["units"].append((r0, r2, rd, r1))
-            else:                                                        # basic: 3x3 (stride) -> 3x3 + residual
-                h1, r1 = _conv_bn_fwd(y, blk.conv1, blk.bn1, 3, blk.stride, 1, False, None, True, mp, storage16)
-                idt, rd = _shortcut(y, blk, mp, storage16)
-                y, r2 = _conv_bn_fwd(h1, blk.conv2, blk.bn2, 3, 1, 1, False, idt, True, mp, storage16)
-                sv["units"].append((r1, r2, rd, None))
+    for blk in m.units():
+        *inner, last = blk.chain()
+        h, recs = y, []
+        for c in inner:
+            h, r = _conv_bn_fwd(h, *c, False, None, True, mp, storage16)
+            recs.append(r)
+        idt, rd = _shortcut(y, blk, mp, storage16)
+        y, r = _conv_bn_fwd(h, *last, False, idt, True, mp, storage16)  # the last convolution takes the residual
+        sv["units"].append((*recs, r, rd))
     sv["last"] = y
     return hip.avgpool_nhwc(y), sv
 
@@ -223,16 +224,15 @@ def backbone_bwd(G: _Grads, sv, dfeat: torch.Tensor, need_source: bool = False) 
     y = sv["last"]
     n, H, W, Cc = y.shape
     dy = hip.avgpool_bwd_nhwc(dfeat.contiguous(), H * W).view(n * H * W, Cc)
-    for r1, r2, rd, rmid in reversed(sv["units"]):
-        dh1 = _conv_bn_bwd(G, r2, dy, True)                               # dy now carries the ReLU mask of the block output
-        if rmid is not None:                                              # bottleneck: through the 3x3 unit to the first 1x1's output
-            dh1 = _conv_bn_bwd(G, rmid, dh1.view(-1, dh1.shape[-1]), True, False)
-        xin = r1["x"]
+    for first, *later, rd in reversed(sv["units"]):
+        d = _conv_bn_bwd(G, later[-1], dy, True)                          # dy now carries the ReLU mask of the block output
+        for r in reversed(later[:-1]):                                    # a three-long chain: through its middle to the first one's output
+            d = _conv_bn_bwd(G, r, d.view(-1, d.shape[-1]), True, False)
         if rd is not None:
             dx = _conv_bn_bwd(G, rd, dy if rd["storage16"] else dy.clone(), True)    # (the 16-bit form leaves a unit without ReLU's dy alone)
         else:
-            dx = dy.view(xin.shape).clone()
-        d1 = _conv_bn_bwd(G, r1, dh1.view(-1, dh1.shape[-1]), True, False)
+            dx = dy.view(first["x"].shape).clone()
+        d1 = _conv_bn_bwd(G, first, d.view(-1, d.shape[-1]), True, False)
         hip.axpby_cols(d1.view(1, -1), dx.view(1, -1))
         dy = dx.view(-1, dx.shape[-1])
     dstem = hip.maxpool_bwd_nhwc(sv["pool_in"], dy.view(sv["units"][0][0]["x"].shape))
@@ -250,25 +250,25 @@ def forward_train(model, x_nhwc: torch.Tensor, sum_in: bool, B: Optional[int], D
         if isinstance(fc, nn.Identity):
             return feat, sv
         return hip.gemm(feat, fc.weight.detach(), fc.bias.detach()), sv
-    from .models.resnet import SLICE_HEADS
-    e = model.emb_ch
-    fused, sv["fusion"] = fusion_fwd(model, feat, B, D, e, SLICE_HEADS, mask)
-    sv["fused"], sv["B"], sv["D"] = fused, B, D
-    return hip.gemm(fused, model.linear.weight.detach(), model.linear.bias.detach()), sv
+    sv["fused"], sv["fusion"] = fusion_fwd(model, feat, B, D, model.emb_ch, SLICE_HEADS, mask)
+    sv["B"], sv["D"] = B, D
+    return hip.gemm(sv["fused"], model.linear.weight.detach(), model.linear.bias.detach()), sv
+
+
+def _head_bwd(G: _Grads, model, sv, dout: torch.Tensor) -> torch.Tensor:
+    """d logits -> d features, through `linear` and the slice fusion (ResNetSliceTrans) or through `fc` / Identity (plain ResNet)."""
+    if "fusion" in sv:
+        dfused = G.lin_bwd(dout, sv["fused"], model.linear)
+        return fusion_bwd(G, model, sv["fusion"], dfused, sv["B"], sv["D"], model.emb_ch, SLICE_HEADS)
+    fc = model.model.fc
+    return dout if isinstance(fc, nn.Identity) else G.lin_bwd(dout, sv["feat"], fc)
 
 
 def backward_train(model, sv, dout: torch.Tensor, needed: Optional[Set[int]] = None, need_source: bool = False):
     """-> ({id(param): grad}, d x_nhwc or None).  needed: ids of the parameters whose gradient is asked for (None: all); the products
     behind the others are skipped, so a frozen model's source-only backward is the d x chain alone."""
     G = _Grads(needed=needed)
-    if "fusion" in sv:
-        from .models.resnet import SLICE_HEADS
-        dfused = G.lin_bwd(dout, sv["fused"], model.linear)
-        dfeat = fusion_bwd(G, model, sv["fusion"], dfused, sv["B"], sv["D"], model.emb_ch, SLICE_HEADS)
-    else:
-        fc = model.model.fc
-        dfeat = dout if isinstance(fc, nn.Identity) else G.lin_bwd(dout, sv["feat"], fc)
-    dx = backbone_bwd(G, sv, dfeat, need_source)
+    dx = backbone_bwd(G, sv, _head_bwd(G, model, sv, dout), need_source)
     return G.by_param, dx
 
 
@@ -300,100 +300,63 @@ def forward_with_grad(model, x_nhwc, sum_in: bool, B=None, D=None, mask=None):
 
 
 # ---- eval mode: the gradient of a frozen model's output with respect to its input volume --------------------------------------------------
-def _folded_dgrad_weight(prep, key, w: torch.Tensor, k: int, Cin: int) -> torch.Tensor:
+def _folded_dgrad_weight(prep, key, f, Cin: int) -> torch.Tensor:
     """The folded GEMM weight [Cout, (ky, kx, c)] re-laid as mst_conv_dgrad's operand [Cin, (ky', kx', co)] (both kernel axes flipped, what
-    hip.conv_dgrad_weight builds from a [Cout, Cin, k, k] weight); cached in the prepared weights beside it."""
+    hip.conv_dgrad_weight builds from a [Cout, Cin, k, k] weight); cached in the prepared weights beside it, by (unit, position)."""
     cache = prep.setdefault("dgrad", {})
     if key not in cache:
-        Cout = w.shape[0]
-        cache[key] = w[:, :k * k * Cin].reshape(Cout, k, k, Cin).flip(1, 2).permute(3, 1, 2, 0).reshape(Cin, k * k * Cout).contiguous()
+        Cout, k = f.w.shape[0], f.k
+        cache[key] = f.w[:, :k * k * Cin].reshape(Cout, k, k, Cin).flip(1, 2).permute(3, 1, 2, 0).reshape(Cin, k * k * Cout).contiguous()
     return cache[key]
 
 
+def _folded_dgrad(prep, key, f, d: torch.Tensor, shape_in) -> torch.Tensor:
+    """d of a folded convolution's output [n, Ho, Wo, Cout] -> d of its input, of shape `shape_in` (mst_conv_dgrad)."""
+    _, H, W, Cin = shape_in
+    return hip.conv_dgrad(d, _folded_dgrad_weight(prep, key, f, Cin), f.k, f.stride, f.pad, H, W)
+
+
 def _eval_backbone_fwd(model, x_nhwc: torch.Tensor, sum_in: bool):
-    """ResNet._features in fp32 on the folded weights, keeping every ReLU output (its mask) per chunk of `chunk_images` images.  The
-    inference forward forms relu(identity + .) in place on the unit's dead input, which would destroy the previous unit's mask: here the
-    sum is formed on a copy, by the same kernels on the same operands -- the features are those of the inference forward bit for bit."""
-    from .models.resnet import _conv
+    """The inference walk itself (`backbone_chunk`) in fp32 on the folded weights, with a keep list per chunk of `chunk_images` images:
+    every ReLU output (its mask) stays for the backward.  The features are those of the fp32 inference forward bit for bit."""
     p = model._prepare(sum_in, fp32=True)
     feats, chunks = [], []
     for i0 in range(0, x_nhwc.shape[0], model.chunk_images):
         x = x_nhwc[i0:i0 + model.chunk_images].contiguous()
-        n, H, W, Cin = x.shape
-        w, b, kpad = p["stem"]
-        Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-        y0 = hip.gemm(hip.im2col_nhwc(x, 7, 7, 2, 3, kpad), w, b, epilogue=hip.EPI_BIAS_RELU).view(n, Ho, Wo, 64)
-        y = hip.maxpool_nhwc(y0)
-        units = []
-        for bi, e in enumerate(p["blocks"]):
-            n, H1, W1, C1 = y.shape
-            s = e["stride"]
-            H2, W2 = (H1 + 2 - 3) // s + 1, (W1 + 2 - 3) // s + 1
-            w1, b1, k1 = e["c1"]
-            w2, b2, k2 = e["c2"]
-            h0 = None
-            if "c3" in e:
-                h0 = _conv(x=y, w=w1, b=b1, k=1, stride=1, pad=0, kpad=k1, epilogue=hip.EPI_BIAS_RELU).view(n, H1, W1, w1.shape[0])
-                h1 = _conv(x=h0, w=w2, b=b2, k=3, stride=s, pad=1, kpad=k2, epilogue=hip.EPI_BIAS_RELU).view(n, H2, W2, w2.shape[0])
-                wl, bl, kl = e["c3"]
-            else:
-                h1 = _conv(x=y, w=w1, b=b1, k=3, stride=s, pad=1, kpad=k1, epilogue=hip.EPI_BIAS_RELU).view(n, H2, W2, w1.shape[0])
-                wl, bl, kl = e["c2"]
-            if "ds" in e:
-                wd, bd, kd = e["ds"]
-                idt = _conv(x=y, w=wd, b=bd, k=1, stride=s, pad=0, kpad=kd, epilogue=hip.EPI_BIAS)
-            else:
-                idt = y.reshape(n * H1 * W1, C1).clone()         # y carries the previous unit's ReLU mask: the sum goes into a copy
-            kl_ = 1 if "c3" in e else 3
-            _conv(x=h1, w=wl, b=bl, k=kl_, stride=1, pad=kl_ // 2, kpad=kl, epilogue=hip.EPI_RESIDUAL_RELU, out=idt)  # relu(identity + .)
-            yo = idt.view(n, H2, W2, wl.shape[0])
-            units.append({"bi": bi, "e": e, "in": (n, H1, W1, C1), "h0": h0, "h1": h1, "y": yo})
-            y = yo
-        feats.append(hip.avgpool_nhwc(y))
-        chunks.append({"x": (n, H, W, Cin), "y0": y0, "units": units})
+        keep = []
+        feats.append(hip.avgpool_nhwc(backbone_chunk(p, x, keep)))
+        chunks.append((x.shape, keep))
     return (torch.cat(feats, dim=0) if len(feats) > 1 else feats[0]), {"prep": p, "chunks": chunks}
 
 
 def _eval_backbone_bwd(sv, dfeat: torch.Tensor) -> torch.Tensor:
-    """d features [n, C] -> d x_nhwc: per unit mst_act_bwd on the saved ReLU output, then mst_conv_dgrad with the folded weight; the
-    shortcut sums; mst_maxpool_bwd_nhwc; the stem through mst_conv_dgrad_stem.  No parameter gradient is formed."""
+    """d features [n, C] -> d x_nhwc, walking each unit's chain in reverse: mst_act_bwd on the saved ReLU output, then mst_conv_dgrad
+    with the folded weight; the shortcut sums; mst_maxpool_bwd_nhwc; the stem through mst_conv_dgrad_stem.  No parameter gradient."""
     p = sv["prep"]
     outs = []
     i0 = 0
-    for ch in sv["chunks"]:
-        n, H, W, Cin = ch["x"]
-        last = ch["units"][-1]["y"]
+    for (n, H, W, Cin), (y0, *units) in sv["chunks"]:
+        last = units[-1][1][-1]
         hw = last.shape[1] * last.shape[2]
         dy = hip.avgpool_bwd_nhwc(dfeat[i0:i0 + n].contiguous(), hw).view(n * hw, last.shape[3])
         i0 += n
-        for u in reversed(ch["units"]):
-            e, bi = u["e"], u["bi"]
-            _, H1, W1, C1 = u["in"]
-            _, H2, W2, C2 = u["y"].shape
-            s = e["stride"]
-            hip.act_bwd(u["y"], dy, 1)
-            dy4 = dy.view(n, H2, W2, C2)
-            if u["h0"] is not None:                          # bottleneck: 1x1 <- 3x3 (stride) <- 1x1
-                wm = u["h1"].shape[3]
-                d = hip.conv_dgrad(dy4, _folded_dgrad_weight(p, (bi, "c3"), e["c3"][0], 1, wm), 1, 1, 0, H2, W2)
-                hip.act_bwd(u["h1"], d, 1)
-                d = hip.conv_dgrad(d, _folded_dgrad_weight(p, (bi, "c2"), e["c2"][0], 3, wm), 3, s, 1, H1, W1)
-                hip.act_bwd(u["h0"], d, 1)
-                d1 = hip.conv_dgrad(d, _folded_dgrad_weight(p, (bi, "c1"), e["c1"][0], 1, C1), 1, 1, 0, H1, W1)
-            else:                                            # basic: 3x3 <- 3x3 (stride)
-                d = hip.conv_dgrad(dy4, _folded_dgrad_weight(p, (bi, "c2"), e["c2"][0], 3, C2), 3, 1, 1, H2, W2)
-                hip.act_bwd(u["h1"], d, 1)
-                d1 = hip.conv_dgrad(d, _folded_dgrad_weight(p, (bi, "c1"), e["c1"][0], 3, C1), 3, s, 1, H1, W1)
-            if "ds" in e:
-                dsx = hip.conv_dgrad(dy4, _folded_dgrad_weight(p, (bi, "ds"), e["ds"][0], 1, C1), 1, s, 0, H1, W1)
-                hip.axpby_cols(dsx.view(1, -1), d1.view(1, -1))
-            else:
-                hip.axpby_cols(dy.view(1, -1), d1.view(1, -1))
-            dy = d1.view(n * H1 * W1, C1)
-        y0 = ch["y0"]
-        dstem = hip.maxpool_bwd_nhwc(y0, dy.view(ch["units"][0]["in"]))
+        for bi in reversed(range(len(units))):
+            shape_in, acts = units[bi]
+            chain, ds = p["blocks"][bi]["chain"], p["blocks"][bi]["ds"]
+            ins = [shape_in] + [a.shape for a in acts[:-1]]  # the input shape of every convolution of the chain
+            hip.act_bwd(acts[-1], dy, 1)
+            dy4 = d = dy.view(acts[-1].shape)
+            for ci in reversed(range(len(chain))):
+                if ci < len(chain) - 1:
+                    hip.act_bwd(acts[ci], d, 1)
+                d = _folded_dgrad(p, (bi, ci), chain[ci], d, ins[ci])
+            # the shortcut: through the downsample, or the masked dy itself
+            hip.axpby_cols((dy if ds is None else _folded_dgrad(p, (bi, "ds"), ds, dy4, shape_in)).view(1, -1), d.view(1, -1))
+            dy = d.view(-1, shape_in[3])
+        st = p["stem"]
+        dstem = hip.maxpool_bwd_nhwc(y0, dy.view(units[0][0]))
         hip.act_bwd(y0, dstem, 1)
-        outs.append(hip.conv_dgrad_stem(dstem, p["stem"][0][:, :49 * Cin].contiguous(), 7, 2, 3, H, W, Cin))
+        outs.append(hip.conv_dgrad_stem(dstem, st.w[:, :st.k * st.k * Cin].contiguous(), st.k, st.stride, st.pad, H, W, Cin))
     return torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
 
 
@@ -408,32 +371,22 @@ class _ResNetEvalFunction(torch.autograd.Function):
     def forward(ctx, model, x_nhwc, sum_in, B, D, mask):
         with torch.no_grad():
             feat, sv = _eval_backbone_fwd(model, x_nhwc, sum_in)
+            sv["feat"] = feat
             if B is None:
                 fc = model.model.fc
                 out = feat if isinstance(fc, nn.Identity) else hip.gemm(feat, sv["prep"]["fc"][0], sv["prep"]["fc"][1], epilogue=hip.EPI_BIAS)
             else:
-                from .models.resnet import SLICE_HEADS
                 out = model.fuse(feat, B, D, mask, False)
                 sv["fused"], sv["fusion"] = fusion_fwd(model, feat, B, D, model.emb_ch, SLICE_HEADS, mask)
-            sv["feat"] = feat
-        ctx.model, ctx.saved, ctx.BD = model, sv, (B, D)
+                sv["B"], sv["D"] = B, D
+        ctx.model, ctx.saved = model, sv
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        model, sv = ctx.model, ctx.saved
-        B, D = ctx.BD
         with torch.no_grad():
             G = _Grads(needed=set())                         # nothing but d x
-            dout = dout.contiguous().float()
-            if B is None:
-                fc = model.model.fc
-                dfeat = dout if isinstance(fc, nn.Identity) else G.lin_bwd(dout, sv["feat"], fc)
-            else:
-                from .models.resnet import SLICE_HEADS
-                dfused = G.lin_bwd(dout, sv["fused"], model.linear)
-                dfeat = fusion_bwd(G, model, sv["fusion"], dfused, B, D, model.emb_ch, SLICE_HEADS)
-            dx = _eval_backbone_bwd(sv, dfeat)
+            dx = _eval_backbone_bwd(ctx.saved, _head_bwd(G, ctx.model, ctx.saved, dout.contiguous().float()))
         ctx.saved = None
         return (None, dx, None, None, None, None)
 

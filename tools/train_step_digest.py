@@ -8,7 +8,8 @@ One configuration per process (a fresh process per configuration is the point: n
 from mst.synth; nothing outside the repository is read.  Hashed: the logits, the loss, every parameter gradient, the source gradient
 where the configuration asks for it, and every floating-point buffer after the step (BatchNorm running statistics).  --deterministic
 sets torch.use_deterministic_algorithms(True): the fixed-order reductions, under which a step is bit-reproducible; without it the atomic
-kernels run and digests differ from run to run.  The unit_* configurations call the ResNet step's convolution + BatchNorm unit directly.
+kernels run and digests differ from run to run.  The unit_* configurations call the ResNet step's convolution + BatchNorm unit directly;
+the resnet*_infer_* and resnet*_frozen_source_grad ones hash the inference forward and the frozen eval-mode source gradient.
 """
 import hashlib
 import json
@@ -47,10 +48,10 @@ def _registers():
     return m.cuda().train()
 
 
-def _resnet34(**kw):
+def _resnet34(model=34, **kw):
     from mst.models import ResNetSliceTrans
-    m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=34, **kw)
-    m.load_state_dict(synth.synth_resnet_state_dict(0, 34, 2), strict=True)
+    m = ResNetSliceTrans(in_ch=1, out_ch=2, pretrained=False, model=model, **kw)
+    m.load_state_dict(synth.synth_resnet_state_dict(0, model, 2), strict=True)
     return m.cuda().train()
 
 
@@ -96,6 +97,27 @@ def _resnet_case(build=_resnet34, env=None, **kw):
         os.environ.update(env or {})
         x = synth.synth_volume(RESNET_SHAPE, 4)
         return step(build(**kw), x[:, 0] if build is _resnet50_plain else x)        # the plain ResNet reads [N, 3, H, W]
+    return run
+
+
+def _resnet_infer_case(build=_resnet34, save_attn=False, **kw):
+    """The inference forward (eval mode, no_grad) through the public API: the logits, with save_attn also get_attention_maps()."""
+    def run():
+        x = synth.synth_volume(RESNET_SHAPE, 4)
+        m = build(**kw).eval()
+        with torch.no_grad():
+            out = {"logits": m((x[:, 0] if build is _resnet50_plain else x).cuda(), save_attn=save_attn)}
+        if save_attn:
+            out["attention_maps"] = m.get_attention_maps()
+        return out
+    return run
+
+
+def _resnet_frozen_case(**kw):
+    """A frozen ResNetSliceTrans in eval mode: the logits and the gradient of the source volume."""
+    def run():
+        m = _resnet34(**kw).eval().requires_grad_(False)
+        return step(m, synth.synth_volume(RESNET_SHAPE, 4), source_grad=True)
     return run
 
 
@@ -152,6 +174,14 @@ CONFIGS = {
     "resnet50_plain_fp16_fp32": _resnet_case(_resnet50_plain, train_precision="fp16"),
     "resnet50_plain_fp16_16bit": _resnet_case(_resnet50_plain, train_precision="fp16", train_storage="16bit"),
     "resnet34_slice_fp32_im2col": _resnet_case(env={"MST_CONV_IM2COL": "1"}, train_precision="fp32"),
+    # ResNet inference forward and frozen eval-mode source gradient at the same shape (6 images: chunk_images=4 leaves a ragged chunk of 2)
+    "resnet34_infer_fp32": _resnet_infer_case(),
+    "resnet34_infer_bf16": _resnet_infer_case(compute_dtype="bf16"),
+    "resnet50_plain_infer_fp16": _resnet_infer_case(_resnet50_plain, compute_dtype="fp16"),
+    "resnet34_infer_save_attn": _resnet_infer_case(save_attn=True),
+    "resnet34_infer_chunk4": _resnet_infer_case(chunk_images=4),
+    "resnet34_frozen_source_grad": _resnet_frozen_case(),
+    "resnet50_frozen_source_grad": _resnet_frozen_case(model=50),
     "unit_stem147_fp16_fp32": _unit_case(False),
     "unit_stem147_fp16_16bit": _unit_case(True),
 }
