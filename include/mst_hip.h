@@ -655,6 +655,36 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
                    float* cls_out, float* cls_probs, float* full_probs, int n_layers_probs,
                    int chunk_slices, void* ws, size_t ws_bytes, mst_stream_t stream);
 
+/* The encoder as DinoVisionTransformer offers it (vision_transformer.py:254-329: forward, forward_features,
+ * get_intermediate_layers): the encoder of mst_vit_encode on grey slices OR true RGB images, with the residual stream behind
+ * chosen blocks ("taps") copied out for every token.  Inference only.  (Additions only: the ABI version stays 300.)
+ * in_channels 1: img [n_images, H, W] of in_dtype, the grey path of mst_vit_encode launch for launch (patch_w_rgb unused, may be
+ *   NULL); with taps == NULL the results have the bits of mst_vit_encode.
+ * in_channels 3: img [n_images, 3, H, W] with three distinct channels; patch_w_rgb is the full Conv2d(3, E, 14, 14) kernel in
+ *   w->compute_dtype as [E][3][14][16] (columns 14, 15 of every kernel row zero: K = 588 padded to 672), 16-byte aligned.  It is
+ *   an argument so that mst_vit_weights keeps its layout.  The token rows start the block pipeline exactly as the grey ones do.
+ * cls_out (nullable) fp32 [n_images, E]: the normalised class tokens, as mst_vit_encode.
+ * taps (nullable): for i < n_taps, out[i][image][token][:] = the residual stream behind block blocks[i] (x_prenorm of that depth)
+ *   for all N = 1 + num_registers + grid_h * grid_w tokens, or with norm = 1 its encoder.norm (eps 1e-6; per row the arithmetic of
+ *   mst_layernorm, so class-token rows of the last block equal cls_out bit for bit).  fp32 plain rows; nothing outside
+ *   [n_taps][n_images][N][E] is written.  blocks: HOST array, strictly ascending, each in [0, depth).
+ * The kernel plan is chosen as in mst_vit_encode, from the token count of the whole call: a tapped call above the fused crossover
+ * stays on the fused, blocked plan (the tap reads the fp32 image layout between two block launches).  A tapped call never prunes
+ * the last block, whatever prune_last_block says (the pruned block has no patch rows); fp8_linear with taps is refused.
+ * Conventions of mst_vit_encode: no allocation, no synchronisation, the caller's stream, chunk_images images per pass, ws of
+ * mst_vit_features_workspace_bytes(...) bytes (MST_EWORKSPACE with a message when short).  With a profiler attached the tap launches
+ * are counted as "layernorm". */
+typedef struct mst_vit_taps {
+    int n_taps;          /* 1..depth */
+    const int* blocks;   /* host array, strictly ascending, each in [0, depth) */
+    int norm;            /* 1: rows pass encoder.norm */
+    float* out;          /* device, fp32 [n_taps][n_images][N][E] */
+} mst_vit_taps;
+size_t mst_vit_features_workspace_bytes(const mst_vit_weights* w, int in_channels, int H, int W, int chunk_images);
+int mst_vit_encode_features(const mst_vit_weights* w, const void* img, int in_dtype, int in_channels, int n_images,
+                            int H, int W, const void* patch_w_rgb, float* cls_out, const mst_vit_taps* taps,
+                            int chunk_images, void* ws, size_t ws_bytes, mst_stream_t stream);
+
 /* Across-slice transformer + head ---------------------------------------------------------- */
 typedef struct mst_fusion_weights {
     int emb_in;      /* E of the encoder */

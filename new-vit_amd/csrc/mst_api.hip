@@ -1,6 +1,6 @@
 // C ABI of libmst_hip.so (include/mst_hip.h): argument checking, dtype dispatch and the two
-// orchestrators -- mst_vit_encode (per-slice DINOv2 ViT) and mst_slice_fusion (across-slice
-// transformer + head).  Nothing here allocates or synchronises: every launch goes to the caller's
+// orchestrators -- mst_vit_encode (per-slice DINOv2 ViT; mst_vit_encode_features: the same with RGB input and
+// taps of the residual stream) and mst_slice_fusion (across-slice transformer + head).  Nothing here allocates or synchronises: every launch goes to the caller's
 // stream, scratch comes from the caller's workspace, so a caller may capture a call into a hipGraph.
 #include <stdarg.h>
 #include <stdio.h>
@@ -797,11 +797,19 @@ struct vit_call {
     }
 };
 
-int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int n_slices, int H, int W,
-                   float* cls_out, float* cls_probs, float* full_probs, int n_layers_probs, int chunk_slices,
-                   void* ws, size_t ws_bytes, mst_stream_t stream) {
+}  // extern "C"
+
+// What mst_vit_encode_features adds to an encoder call: true RGB input and the taps.  All zero: mst_vit_encode, launch for launch.
+struct vit_features {
+    const void* patch_w_rgb;      // non-null: vol is [n, 3, H, W] and this the [E][3][14][16] kernel image
+    const mst_vit_taps* taps;     // nullable
+};
+
+static int vit_encode_run(const mst_vit_weights* w, const void* vol, int in_dtype, int n_slices, int H, int W,
+                          float* cls_out, float* cls_probs, float* full_probs, int n_layers_probs, int chunk_slices,
+                          void* ws, size_t ws_bytes, mst_stream_t stream, const vit_features& f) {
     hipStream_t s = (hipStream_t)stream;
-    MST_CHECK_ARG(w && vol && cls_out && ws, "vit_encode: null pointer");
+    MST_CHECK_ARG(w && vol && ws, "vit_encode: null pointer");
     mst_profiler* const prof = w->profiler;
     MST_CHECK_ARG(w->layers && w->depth > 0, "vit_encode: no layers");
     MST_CHECK_ARG(H > 0 && W > 0 && H % 14 == 0 && W % 14 == 0, "vit_encode: H=%d W=%d must be multiples of 14", H, W);
@@ -834,7 +842,7 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
             MST_CHECK_ARG(w->layers[l].qkv_w8 && w->layers[l].proj_w8 && w->layers[l].fc1_w8 && w->layers[l].fc2_w8,
                           "vit_encode: fp8_linear set but layer %d has no e4m3 weights", l);
     }
-    const size_t in_sz = dt_size(in_dtype);
+    const size_t in_sz = dt_size(in_dtype) * (f.patch_w_rgb ? 3 : 1);     // bytes per pixel position of an image (RGB: three planes)
     // head_dim^-0.5, head_dim = 64 (attention.py:48); the 16-bit attention kernels work in the log2 domain, so log2(e) rides
     // on the same fp32 multiply of the QKV epilogue (one rounding of q, not two)
     const int log2q = dt != MST_F32;
@@ -852,10 +860,14 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
         // the rows stay in the order the registers hold them (include/mst_hip.h, mst_layout_flags): x as the fp32 image from block 0's
         // output to the last block's input, the 16-bit rows (attention output, normalised rows) blocked from block 0's attention on.
         // Needs the QKV kernel that reads blocked rows (weights-in-registers form) and every block on the fused path.
-        const bool prune = plan.may_prune && c <= 65535;
+        const bool prune = plan.may_prune && c <= 65535 && !f.taps;          // the pruned block has no patch rows to tap
         k.blocked = plan.tail == TAIL_BLOCK_SINGLE && !prune && gemm16_wreg_applicable(k.qkv_linear(nullptr, nullptr, nullptr));
         // tokens: in the fused pipeline one kernel writes the residual stream AND block 0's plain-normalised rows (k_patch_rows.hip)
-        if (plan.fused_ln)
+        if (f.patch_w_rgb) {
+            // true RGB (k_features.hip): the same x; the fused pipeline's plain-normalised rows by a LayerNorm launch without affine
+            RUNK(MST_K_PATCH_EMBED, launch_patch_embed_rgb(v, in_dtype, c, H, W, f.patch_w_rgb, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, E, k.x, s));
+            if (plan.fused_ln) RUNK(MST_K_LAYERNORM, launch_layernorm(k.x, E, nullptr, nullptr, k.xn, dt, E, Mc, E, 1e-6f, s));
+        } else if (plan.fused_ln)
             RUNK(MST_K_PATCH_EMBED, launch_patch_rows16(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, k.x, k.xn, s));
         else
             RUNK(MST_K_PATCH_EMBED, launch_patch_embed(v, in_dtype, c, H, W, w->patch_w, dt, w->patch_b, w->prefix, 1 + R, w->pos_patch, E, k.x, s));
@@ -877,12 +889,55 @@ int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int 
             if (dt == MST_F32) RUNK(MST_K_ATTENTION, launch_attn32((const float*)k.big, c, N, heads, (float*)k.xn, s));
             else RUNK(MST_K_ATTENTION, launch_attn16(k.big, dt, c, N, heads, k.xn, 1, s, k.blocked ? 1 : 0));
             RUN(k.tail(plan.tail, l));
+            for (int t = 0; f.taps && t < f.taps->n_taps; ++t) {
+                if (f.taps->blocks[t] != l) continue;
+                // x behind block l: the fp32 image between two single-role block launches of the blocked plan, plain rows otherwise
+                float* const out = f.taps->out + ((int64_t)t * n_slices + s0) * N * E;
+                const bool norm = f.taps->norm != 0;
+                RUNK(MST_K_LAYERNORM, launch_tap_rows(k.x, k.blocked && l + 1 < w->depth, norm ? w->norm_w : nullptr, norm ? w->norm_b : nullptr,
+                                                      out, Mc, E, 1e-6f, s));
+            }
         }
         if (plan.tail == TAIL_FP8_DYNAMIC && w->fp8_amax_out) RUN(launch_amax_merge(w->fp8_amax_out, k.amax, w->depth * 4, s));
         // final norm, CLS rows only (vision_transformer.py:263-265,329)
-        RUN(launch_layernorm(k.x, (int64_t)N * E, w->norm_w, w->norm_b, cls_out + (int64_t)s0 * E, MST_F32, E, c, E, 1e-6f, s));
+        if (cls_out) RUN(launch_layernorm(k.x, (int64_t)N * E, w->norm_w, w->norm_b, cls_out + (int64_t)s0 * E, MST_F32, E, c, E, 1e-6f, s));
     }
     return MST_OK;
+}
+
+extern "C" {
+
+int mst_vit_encode(const mst_vit_weights* w, const void* vol, int in_dtype, int n_slices, int H, int W,
+                   float* cls_out, float* cls_probs, float* full_probs, int n_layers_probs, int chunk_slices,
+                   void* ws, size_t ws_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(cls_out, "vit_encode: null pointer");
+    return vit_encode_run(w, vol, in_dtype, n_slices, H, W, cls_out, cls_probs, full_probs, n_layers_probs, chunk_slices, ws, ws_bytes,
+                          stream, vit_features{nullptr, nullptr});
+}
+
+// ---- encoder API: patch tokens and intermediate layers (vision_transformer.py:254-329) -----------------------------------
+size_t mst_vit_features_workspace_bytes(const mst_vit_weights* w, int in_channels, int H, int W, int chunk_images) {
+    if (in_channels != 1 && in_channels != 3) return 0;
+    return mst_vit_workspace_bytes(w, H, W, chunk_images);      // the RGB kernel and the taps need no scratch of their own
+}
+
+int mst_vit_encode_features(const mst_vit_weights* w, const void* img, int in_dtype, int in_channels, int n_images, int H, int W,
+                            const void* patch_w_rgb, float* cls_out, const mst_vit_taps* taps, int chunk_images, void* ws,
+                            size_t ws_bytes, mst_stream_t stream) {
+    MST_CHECK_ARG(w, "vit_encode_features: null pointer");
+    MST_CHECK_ARG(in_channels == 1 || in_channels == 3, "vit_encode_features: in_channels=%d (1: grey slices, 3: RGB images)", in_channels);
+    MST_CHECK_ARG(in_channels == 1 || patch_w_rgb, "vit_encode_features: RGB input needs patch_w_rgb");
+    MST_CHECK_ARG(in_dtype == MST_F32 || in_dtype == MST_F16 || in_dtype == MST_BF16, "vit_encode_features: bad image dtype %d", in_dtype);
+    if (taps) {
+        MST_CHECK_ARG(!w->fp8_linear, "vit_encode_features: taps are not available with fp8_linear (the e4m3 pipeline is CLS-only): use bf16, fp16 or fp32");
+        MST_CHECK_ARG(taps->blocks && taps->out && taps->n_taps >= 1 && taps->n_taps <= w->depth, "vit_encode_features: taps: n_taps=%d of depth %d, or a null pointer",
+                      taps->n_taps, w->depth);
+        for (int t = 0; t < taps->n_taps; ++t)
+            MST_CHECK_ARG(taps->blocks[t] >= 0 && taps->blocks[t] < w->depth && (t == 0 || taps->blocks[t] > taps->blocks[t - 1]),
+                          "vit_encode_features: taps->blocks[%d]=%d: strictly ascending indices in [0, %d)", t, taps->blocks[t], w->depth);
+    }
+    return vit_encode_run(w, img, in_dtype, n_images, H, W, cls_out, nullptr, nullptr, 0, chunk_images, ws, ws_bytes, stream,
+                          vit_features{in_channels == 3 ? patch_w_rgb : nullptr, taps});
 }
 
 // ---- across-slice transformer + head ----------------------------------------------------------

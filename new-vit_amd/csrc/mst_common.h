@@ -418,6 +418,11 @@ int launch_patch_embed(const void* vol, int idt, int n, int H, int W, const void
                        int E, float* x, hipStream_t s);
 int launch_pos_interp(const float* pos, int M, int E, int gh, int gw, double offset, int antialias, float* out,
                       hipStream_t s);
+// encoder API (k_features.hip): the patch embedding of true RGB images, wp [E][3][14][16] of dt; and the residual stream as fp32 plain
+// rows, read from plain rows or (x_image) from the fp32 image of the blocked layout, through LayerNorm(g, b, eps) unless g is null
+int launch_patch_embed_rgb(const void* img, int idt, int n, int H, int W, const void* wp, int dt, const float* bias, const float* prefix,
+                           int n_prefix, const float* pos_patch, int E, float* x, hipStream_t s);
+int launch_tap_rows(const float* x, int x_image, const float* g, const float* b, float* out, int64_t rows, int cols, float eps, hipStream_t s);
 int launch_slice_tokens(const float* emb, const float* cls, const float* pos, int B, int D, int E,
                         float* xs, hipStream_t s);
 int launch_slice_attn(const float* qkv, int B, int L, int heads, int hd, const uint8_t* mask,

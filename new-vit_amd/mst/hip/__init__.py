@@ -48,6 +48,10 @@ class VitWeights(C.Structure):
                 ("ffn_kind", _i), ("ffn_hidden", _i)]
 
 
+class VitTaps(C.Structure):      # mst_vit_taps: blocks is a HOST array
+    _fields_ = [("n_taps", _i), ("blocks", C.POINTER(_i)), ("norm", _i), ("out", _vp)]
+
+
 class FusionWeights(C.Structure):
     _fields_ = [("emb_in", _i), ("emb", _i), ("out_ch", _i), ("fusion_type", _i), ("num_heads", _i)] + \
                [(n, _vp) for n in ("bottleneck_w", "bottleneck_b", "slice_pos_emb", "cls_token",
@@ -143,6 +147,8 @@ SIGNATURES = {
     "mst_patch_embed": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "mst_vit_workspace_bytes": (_sz, [C.POINTER(VitWeights), _i, _i, _i]),
     "mst_vit_encode": (_i, [C.POINTER(VitWeights), _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "mst_vit_features_workspace_bytes": (_sz, [C.POINTER(VitWeights), _i, _i, _i, _i]),
+    "mst_vit_encode_features": (_i, [C.POINTER(VitWeights), _vp, _i, _i, _i, _i, _i, _vp, _vp, C.POINTER(VitTaps), _i, _vp, _sz, _vp]),
     "mst_fusion_workspace_bytes": (_sz, [C.POINTER(FusionWeights), _i, _i]),
     "mst_slice_fusion": (_i, [C.POINTER(FusionWeights), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mst_attention_readout": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -818,6 +824,47 @@ def vit_encode(w: VitWeights, vol: torch.Tensor, cls_out: torch.Tensor, cls_prob
     _check(load().mst_vit_encode(C.byref(w), ptr(vol), dt_of(vol), n, H, W, ptr(cls_out), ptr(cls_probs),
                                  ptr(full_probs), n_layers_probs, chunk, ptr(ws), ws.numel() * ws.element_size(),
                                  stream_of(vol)), "mst_vit_encode")
+
+
+def vit_features_workspace_bytes(w: VitWeights, in_channels: int, H: int, W: int, chunk: int) -> int:
+    return int(load().mst_vit_features_workspace_bytes(C.byref(w), in_channels, H, W, chunk))
+
+
+def pack_patch_rgb(weight: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Conv2d(3, E, 14, 14).weight -> the [E, 3*14*16] image mst_vit_encode_features reads as patch_w_rgb: every kernel row padded
+    to 16 columns with zeros (K = 588 -> 672), in the compute dtype."""
+    E = weight.shape[0]
+    wp = torch.zeros((E, 3, 14, 16), dtype=torch.float32, device=weight.device)
+    wp[..., :14] = weight.detach().float()
+    return wp.reshape(E, 3 * 14 * 16).to(dtype).contiguous()
+
+
+def vit_encode_features(w: VitWeights, img: torch.Tensor, chunk: int, ws: torch.Tensor, *, patch_w_rgb: Optional[torch.Tensor] = None,
+                        cls_out: Optional[torch.Tensor] = None, blocks: Sequence[int] = (), norm: bool = True,
+                        out: Optional[torch.Tensor] = None):
+    """mst_vit_encode_features.  img [n, H, W] (grey) or [n, 3, H, W] (RGB, with patch_w_rgb from pack_patch_rgb).  cls_out
+    (optional) fp32 [n, E].  blocks (strictly ascending block indices) with out fp32 [len(blocks), n, N, E] contiguous: the residual
+    stream behind those blocks, through encoder.norm when `norm`.  `out` may be a view into a larger tensor; exactly its elements
+    are written."""
+    _dev(img, "vit_encode_features")
+    if img.dim() == 4:
+        n, ch, H, W = img.shape
+    else:
+        (n, H, W), ch = img.shape, 1
+    if ch == 3 and patch_w_rgb is None:
+        raise ValueError("vit_encode_features: RGB input needs patch_w_rgb")
+    taps = None
+    blocks = [int(b) for b in blocks]
+    if blocks:
+        N = 1 + w.num_registers + (H // 14) * (W // 14)
+        if out is None or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() \
+                or tuple(out.shape) != (len(blocks), n, N, w.embed_dim):
+            raise ValueError(f"vit_encode_features: out must be a contiguous fp32 device tensor of shape {(len(blocks), n, N, w.embed_dim)}")
+        idx = (_i * len(blocks))(*blocks)
+        taps = VitTaps(len(blocks), idx, 1 if norm else 0, ptr(out))
+    _check(load().mst_vit_encode_features(C.byref(w), ptr(img), dt_of(img), ch, n, H, W, ptr(patch_w_rgb), ptr(cls_out),
+                                          None if taps is None else C.byref(taps), chunk, ptr(ws), ws.numel() * ws.element_size(),
+                                          stream_of(img)), "mst_vit_encode_features")
 
 
 def fusion_workspace_bytes(w: FusionWeights, B: int, D: int) -> int:

@@ -32,6 +32,7 @@ from __future__ import annotations
 import math
 import os
 import warnings
+import weakref
 from typing import List, Optional
 
 import torch
@@ -150,8 +151,36 @@ class _PatchEmbed(_Params):
         nn.init.kaiming_uniform_(self.proj.weight, a=math.sqrt(5))
 
 
+def _no_cpu_fallback(dev) -> RuntimeError:
+    return RuntimeError(f"DinoV2ClassifierSlice runs on an MI355X only: parameters are on {dev}; call .to('cuda'). "
+                        "There is no CPU fallback.")
+
+
+class _OwnerLink:
+    """Weak link from an encoder to the model that owns it -- the model holds the prepared weight images, the position cache and the
+    workspaces the encoder's own calls run on.  Not a module, not a tensor: no state-dict key, no registered child, no reference
+    cycle.  ``copy.deepcopy(model)`` links the copied encoder to the copied model; a copy of the encoder alone, or an unpickled one,
+    is unlinked until it is assigned to a model (``model.encoder = enc``)."""
+
+    def __init__(self, owner=None):
+        self._ref = None if owner is None else weakref.ref(owner)
+
+    def __call__(self):
+        return None if self._ref is None else self._ref()
+
+    def __deepcopy__(self, memo):
+        return _OwnerLink(memo.get(id(self())))        # the model's copy is in the memo before its members are copied
+
+    def __reduce__(self):
+        return (_OwnerLink, ())
+
+
 class _ViT(_Params):
-    """Parameter tree of DinoVisionTransformer (vision_transformer.py:44-170)."""
+    """Parameter tree of DinoVisionTransformer (vision_transformer.py:44-170) with its inference calls -- ``forward``,
+    ``forward_features``, ``get_intermediate_layers`` (vision_transformer.py:254-329) -- on the HIP path of the owning
+    ``DinoV2ClassifierSlice`` (``encode_features``).  ``x`` is ``[n, 3, H, W]``, the reference's contract, or ``[n, 1, H, W]``: the
+    build's grey fast path with the numbers of ``x.repeat(1, 3, 1, 1)`` and the bits of ``encode_slices``.  Results are fresh fp32
+    tensors on the model's device.  Inference only: the mask-token path (SSL pre-training) and gradients are refused."""
 
     def __init__(self, embed_dim, depth, num_heads, img_size=224, num_register_tokens=0,
                  layerscale: Optional[float] = None, chunked=True, ffn_layer: str = "mlp"):
@@ -169,7 +198,9 @@ class _ViT(_Params):
         if num_register_tokens:
             self.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, embed_dim))
         blocks = [_Block(embed_dim, layerscale, self.ffn_layer) for _ in range(depth)]
-        self.chunked = chunked
+        self.chunked = self.chunked_blocks = chunked
+        self.n_blocks = depth
+        self._owner = _OwnerLink()
         self.blocks = nn.ModuleList([nn.ModuleList(blocks)]) if chunked else nn.ModuleList(blocks)
         self.norm = _ln(embed_dim)
         self.mask_token = nn.Parameter(torch.zeros(1, embed_dim))
@@ -180,6 +211,61 @@ class _ViT(_Params):
 
     def block_list(self) -> List[_Block]:
         return list(self.blocks[0]) if self.chunked else list(self.blocks)
+
+    # ---- the reference's inference calls (vision_transformer.py:254-329) --------------------------------------------------------
+    def _encode(self, x, blocks, norm: bool, want_cls: bool):
+        """(class tokens [n, E] or None, taps [len(blocks), n, N, E] or None) from the owning model.  Refusals in the order the
+        callers rely on: no CPU fallback, then a gradient request."""
+        owner = self._owner()
+        dev = owner.device if owner is not None else self.cls_token.device
+        if dev.type != "cuda":
+            raise _no_cpu_fallback(dev)
+        if owner is None:
+            raise RuntimeError("this encoder is not attached to a DinoV2ClassifierSlice (a copy of the encoder alone?): assign it, "
+                               "`model.encoder = encoder`; the model holds the weight images and workspaces its calls run on")
+        if torch.is_grad_enabled() and ((isinstance(x, torch.Tensor) and x.requires_grad) or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("the encoder API (forward / forward_features / get_intermediate_layers) is inference-only: "
+                                      "call it under torch.no_grad(); gradients run through DinoV2ClassifierSlice.forward")
+        return owner.encode_features(x, blocks, norm, want_cls)
+
+    def forward_features_list(self, x_list, masks_list):
+        raise NotImplementedError("forward_features_list (list input) is the SSL pre-training path of the reference (multi-crop with "
+                                  "mask tokens): not part of the inference build; call forward_features once per tensor")
+
+    def forward_features(self, x, masks=None):
+        if masks is not None:
+            raise NotImplementedError("masks: the mask-token path is SSL pre-training only (vision_transformer.py:216-217); "
+                                      "the inference build has none")
+        if isinstance(x, list):
+            return self.forward_features_list(x, masks)
+        R = self.num_register_tokens
+        _, taps = self._encode(x, (self.depth - 1,), False, False)
+        x_prenorm = taps[0]
+        x_norm = hip.layernorm(x_prenorm, self.norm.weight.detach().float().contiguous(), self.norm.bias.detach().float().contiguous(), 1e-6)
+        return {"x_norm_clstoken": x_norm[:, 0], "x_norm_regtokens": x_norm[:, 1:R + 1], "x_norm_patchtokens": x_norm[:, R + 1:],
+                "x_prenorm": x_prenorm, "masks": masks}                    # views of one fresh tensor, as the reference returns them
+
+    def get_intermediate_layers(self, x, n=1, reshape=False, return_class_token=False, norm=True):
+        total = self.depth
+        take = range(total - n, total) if isinstance(n, int) else n
+        found = sorted({int(i) for i in take if 0 <= int(i) < total})
+        assert len(found) == len(take), f"only {len(found)} / {len(take)} blocks found"
+        _, taps = self._encode(x, found, bool(norm), False)
+        R = self.num_register_tokens
+        class_tokens = [t[:, 0] for t in taps]
+        outputs = [t[:, 1 + R:] for t in taps]
+        if reshape:
+            B, _, w, h = x.shape
+            outputs = [o.reshape(B, w // PATCH, h // PATCH, -1).permute(0, 3, 1, 2).contiguous() for o in outputs]
+        if return_class_token:
+            return tuple(zip(outputs, class_tokens))
+        return tuple(outputs)
+
+    def forward(self, x, masks=None, is_training=False):
+        if is_training or masks is not None or isinstance(x, list):   # the last two raise: the same refusals, in the same order
+            return self.forward_features(x, masks)
+        cls, _ = self._encode(x, (), True, True)
+        return cls                                                    # head = nn.Identity (vision_transformer.py:168)
 
 
 class _SelfAttn(_Params):
@@ -370,6 +456,17 @@ class DinoV2ClassifierSlice(BasicClassifier):
         self._warned_grad = False
         self._register_load_state_dict_pre_hook(self._remap_state_dict)
 
+    # ---- the encoder belongs to this model: its own calls (forward_features, ...) run on this model's weight images ----------
+    def __setattr__(self, name, value):
+        super().__setattr__(name, value)
+        if name == "encoder" and isinstance(value, _ViT):
+            value._owner = _OwnerLink(self)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if isinstance(self._modules.get("encoder"), _ViT):
+            self.encoder._owner = _OwnerLink(self)
+
     # ---- checkpoint compatibility ---------------------------------------------------------------
     def _remap_state_dict(self, state_dict, prefix, *args):
         """Accept the other block layout: hub ``blocks.<i>.`` <-> chunked ``blocks.0.<i>.``."""
@@ -452,8 +549,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
     def _build_weights(self):
         dev = self.device
         if dev.type != "cuda":
-            raise RuntimeError(f"DinoV2ClassifierSlice runs on an MI355X only: parameters are on {dev}; call .to('cuda'). "
-                               "There is no CPU fallback.")
+            raise _no_cpu_fallback(dev)
         keep: List[torch.Tensor] = []                   # every tensor a struct below points into
 
         def put(t, dtype=torch.float32):
@@ -582,6 +678,48 @@ class DinoV2ClassifierSlice(BasicClassifier):
                 full_probs = torch.empty((n_layers_probs, n, heads, N, N), dtype=torch.float32, device=dev)
         hip.vit_encode(vit, slices, emb, cls_probs, n_layers_probs, chunk, ws, full_probs)
         return emb, cls_probs, full_probs
+
+    def encode_features(self, x: torch.Tensor, blocks=(), norm: bool = True, want_cls: bool = False):
+        """The encoder on ``[n, 3, H, W]`` images (three distinct channels) or ``[n, 1, H, W]`` grey ones, for ``self.encoder``'s own
+        calls -> (normalised class tokens ``[n, E]`` or None, ``[len(blocks), n, N, E]`` or None: the residual stream behind the blocks
+        ``blocks`` (ascending), through ``encoder.norm`` when ``norm``).  Local to the rank: slice sharding does not apply.  The kernel
+        plan follows the token count of the call exactly as in ``encode_slices``; a tapped call stays on it."""
+        if self.compute_dtype_name in hip.FP8_NAMES:
+            raise NotImplementedError("compute_dtype='fp8' computes class tokens only (its e4m3 pipeline has no taps): use bf16, fp16 or "
+                                      "fp32 for forward_features / get_intermediate_layers")
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[1] in (1, 3)):
+            raise ValueError(f"the encoder takes [n, 3, H, W] images (or [n, 1, H, W] grey ones); got {tuple(getattr(x, 'shape', ()))}")
+        n, ch, H, W = x.shape
+        assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
+        assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
+        prep = self._prepare()
+        x = x.detach().to(self.device)
+        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            x = x.float()
+        x = x.reshape(n, H, W) if ch == 1 else x
+        x = x.contiguous()
+        wrgb = None
+        if ch == 3:   # the full three-channel kernel image, built on first RGB use and kept like every other weight image
+            tdt = hip.TORCH_DT[prep["cdt"]]
+            wrgb = self._prepared.get(self, "patch_rgb", lambda: hip.pack_patch_rgb(self.encoder.patch_embed.proj.weight.to(self.device), tdt),
+                                      self.compute_dtype_name)
+        vit = prep["vit"]
+        vit.grid_h, vit.grid_w = H // PATCH, W // PATCH
+        pp = self._pos_patch(prep, H, W)
+        vit.pos_patch = hip.ptr(pp)
+        vit.profiler = self.profiler.handle if self.profiler is not None else None
+        vit.prune_last_block = 1 if self.prune_last_block else 0
+        enc = self.encoder
+        E = enc.embed_dim
+        N = 1 + enc.num_register_tokens + vit.grid_h * vit.grid_w
+        dev = x.device
+        chunk = self._auto_chunk(n, N, E, prep["cdt"])
+        ws = cached_workspace(self._ws, "vit", hip.vit_features_workspace_bytes(vit, ch, H, W, chunk), dev)
+        cls = torch.empty((n, E), dtype=torch.float32, device=dev) if want_cls else None
+        blocks = list(blocks)
+        out = torch.empty((len(blocks), n, N, E), dtype=torch.float32, device=dev) if blocks else None
+        hip.vit_encode_features(vit, x, chunk, ws, patch_w_rgb=wrgb, cls_out=cls, blocks=blocks, norm=norm, out=out)
+        return cls, out
 
     def fuse_slices(self, emb: torch.Tensor, B: int, D: int, mask: Optional[torch.Tensor], want_probs: bool,
                     want_logits: bool):

@@ -41,6 +41,10 @@ class Prepared:
         self._tensors = None
         self._slots.clear()
 
+    def __deepcopy__(self, memo):
+        """A copied model builds its own images from its own parameters (the slots hold C structs of raw pointers into this one's)."""
+        return Prepared()
+
     def key(self, module: torch.nn.Module, full: bool, *extra) -> tuple:
         """`extra` (whatever else the image depends on), then version_key of the module's tensors."""
         if self._tensors is None:

@@ -492,6 +492,32 @@ def case_slices2rgb(dino, synth):
     print("wrote slices2rgb.npz")
 
 
+@torch.no_grad()
+def case_encoder_api(dino, synth, seed=0, shape=(2, 3, 56, 70), image_seed=41):
+    """The reference's own DinoVisionTransformer (model.encoder of DinoV2ClassifierSlice(pretrained=False), seed-0 synthetic weights)
+    through its three inference calls on a true RGB image with three different channels: channel c holds the slices of
+    synth_volume((1, 1, n, H, W), image_seed + 17 c), what tests/encoder_ref.py rgb_image rebuilds.  4 x 5 grid: the stored
+    16 x 16 position grid is resampled to a non-square one.  Seeds, shapes and outputs only."""
+    model, _ = build(dino, synth, seed)
+    enc = model.encoder
+    n, c, H, W = shape
+    x = torch.cat([synth.synth_volume((1, 1, n, H, W), image_seed + 17 * ch)[0, 0][:, None] for ch in range(c)], dim=1)
+    out = {"seed": np.array(seed), "image_seed": np.array(image_seed), "shape": np.array(shape)}
+    ff = enc.forward_features(x)
+    assert ff["masks"] is None
+    for k in ("x_norm_clstoken", "x_norm_regtokens", "x_norm_patchtokens", "x_prenorm"):
+        out["ff." + k] = np_(ff[k])
+    out["forward"] = np_(enc(x))
+    out["il_blocks"] = np.array([0, 5, 11])
+    for i, (patch, cls) in enumerate(enc.get_intermediate_layers(x, n=[0, 5, 11], reshape=True, return_class_token=True)):
+        out[f"il_reshape.{i}.patch"] = np_(patch)
+        out[f"il_reshape.{i}.cls"] = np_(cls)
+    for i, patch in enumerate(enc.get_intermediate_layers(x, n=2, norm=False)):
+        out[f"il_last2_prenorm.{i}"] = np_(patch)
+    np.savez_compressed(GOLD / "encoder_api.npz", **out)
+    print("encoder_api", {k: getattr(v, "shape", v) for k, v in out.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -531,6 +557,7 @@ def main():
         "swiglu_s2": lambda: case_swiglu_s2(dino, synth),
         "swiglu_g1": lambda: case_swiglu_g1(synth),
         "hub_vitg14_keys": lambda: case_hub_vitg14_keys(),
+        "encoder_api": lambda: case_encoder_api(dino, synth),
     }
     for name, fn in cases.items():
         if args.only and name not in args.only:
