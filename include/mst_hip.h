@@ -453,6 +453,29 @@ int mst_pos_embed_interp_bwd(const float* dout, int M, int E, int gh, int gw, do
  * dx and wsum 16-byte aligned.  Exact fp32 MFMA, no atomics: bit-reproducible, one entry point for both determinism modes. */
 int mst_patch_embed_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wsum, int n, int H, int W, int E,
                           float* dvol, mst_stream_t stream);
+/* The patch embedding of true three-channel images (the encoder API's [n, 3, H, W] input; extern/dinov2/layers/patch_embed.py:65,75-81:
+ * Conv2d(3, E, 14, stride 14), flatten, transpose) at the op level, all operands fp32 as in the training step's mst_patch_embed.
+ * wp fp32 [E][3][14][16] is the kernel image (Conv2d weight [E, 3, 14, 14], every kernel row padded to 16 with zeros).  H, W multiples
+ * of 14; anything outside the rules below returns MST_EINVAL.
+ * mst_patch_embed_rgb (forward): x[s][n_prefix + py gw + px][e] = sum_{c,i,j} img[s][c][14 py + i][14 px + j] w[e][c][i][j] + bias[e] +
+ *   pos_patch[py gw + px][e];  x[s][r] = prefix[r] for r < n_prefix.  img fp32 [n, 3, H, W] (8-byte aligned), prefix fp32 [n_prefix >= 1, E],
+ *   pos_patch fp32 [Np, E], x fp32 [n, n_prefix + Np, E]; E a multiple of 64; wp, bias, pos_patch, x 16-byte aligned.  The kernel of
+ *   mst_vit_encode_features' RGB input in its fp32 mode (v_mfma_f32_16x16x4_f32).
+ * mst_patch_embed_rgb_dgrad (input gradient):
+ *   dimg[s][c][14 py + i][14 px + j] = sum_e dx[s * tokens_per_image + first_patch_token + py gw + px][e] * w[e][c][i][j]
+ *   dx fp32 [n * tokens_per_image, E] as in mst_patch_embed_dgrad, dimg fp32 [n, 3, H, W], every pixel written once.  E a multiple of 16,
+ *   dx and wp 16-byte aligned.  Exact fp32 MFMA, no atomics: bit-reproducible, one entry point for both determinism modes.
+ * mst_patch_embed_rgb_wgrad (weight gradient), an implicit GEMM over the image in place, split over the patch rows m = s Np + p:
+ *   part[z][e][c][i][j] = sum_{m in [z rows_per_split, (z + 1) rows_per_split)} dx[s * tokens_per_image + first_patch_token + p][e] *
+ *   img[s][c][14 py + i][14 px + j];  dW = sum_z part[z] is the caller's (mst_colsum / mst_colsum_ordered over [splits, E * 588]).
+ *   part fp32 [ceil(n Np / rows_per_split), E, 3, 14, 14], every element written; rows_per_split a positive multiple of 16 with at most
+ *   65535 splits; E a multiple of 64; dx 16-byte, img 8-byte aligned.  Exact fp32 MFMA, no atomics. */
+int mst_patch_embed_rgb(const float* img, int n, int H, int W, const float* wp, const float* bias, const float* prefix, int n_prefix,
+                        const float* pos_patch, int E, float* x, mst_stream_t stream);
+int mst_patch_embed_rgb_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wp, int n, int H, int W, int E,
+                              float* dimg, mst_stream_t stream);
+int mst_patch_embed_rgb_wgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* img, int n, int H, int W, int E,
+                              int rows_per_split, float* part, mst_stream_t stream);
 
 /* 16-bit storage mode of the training step (mst/train.py, train_storage='16bit'): under the reference's Trainer(precision='16-mixed')
  * (scripts/main_train.py:110-123) autocast keeps what a block saves for its backward (block.py:89-114) in the 16-bit type T = dtype

@@ -1,4 +1,4 @@
-// The two kernels behind the encoder API (DinoVisionTransformer.forward_features / get_intermediate_layers,
+// The kernels behind the encoder API (DinoVisionTransformer.forward_features / get_intermediate_layers,
 // vision_transformer.py:254-322; mst_vit_encode_features in mst_api.hip):
 //
 // RGB patch embedding.  Conv2d(3, E, 14, 14) on [n, 3, H, W] with three DISTINCT channels (patch_embed.py:65,75-77) as one
@@ -13,6 +13,9 @@
 // arithmetic is layernorm_kernel's (k_layernorm.hip) statement for statement: one wave per row, two-pass statistics in registers.
 // x is read as plain rows or as the fp32 image of the blocked layout (include/mst_hip.h, mst_layout_flags): in both a lane's
 // two columns 128 j + 2 lane, +1 are one aligned 8-byte access.  No atomics.
+//
+// RGB weight gradient (mst_patch_embed_rgb_wgrad, the training side of the first kernel): see patch_rgb_wgrad_kernel below.  The input
+// gradient (mst_patch_embed_rgb_dgrad) is the grey data-gradient kernel run per channel: k_patch_dgrad.hip.
 #include "mst_common.h"
 
 namespace {
@@ -261,7 +264,121 @@ int launch_tap_t(const float* x, const float* g, const float* b, float* out, int
     return mst_check_launch("tap_rows");
 }
 
+// ---- mst_patch_embed_rgb_wgrad: the weight gradient of the RGB patch embedding (patch_embed.py:65,75-81) as an implicit GEMM that
+// reads the image in place (no three-channel im2col: 64 x 3 x 518^2 would be 206 MB of fp32):
+//   dW[e][c][i][j] = sum over patch rows m = (s, p) of dx[s * tok + first + p][e] * img[s][c][14 py + i][14 px + j]
+// Tile: a 256-thread workgroup owns 64 embedding channels x the 224 (staged as 256: 14 kernel rows x 16) columns of ONE input channel
+// and walks the patch rows of ONE split in K-steps of 16 on the exact fp32 MFMA (v_mfma_f32_32x32x2_f32); wave w owns the 32-channel
+// block w & 1 and four 32-column blocks from 4 (w >> 1) (the eighth block is all padding and skipped), the tile of k_patch_dgrad.hip with
+// the roles of patch rows and channels exchanged.  LDS double-buffered, the next step's operands in registers across the MFMAs.
+// Split: grid.z walks the patch rows `rows_per_split` (a multiple of the K-step; the caller picks max(256, n Np / 16 rounded up to 16): at
+// most 16 partials) at a time; split z writes its own part[z][E][3][14][14] and the caller reduces them (mst_colsum, atomic or ordered).
+// No atomics here.  Rows past the end of a split read as zero on both operands.
+constexpr int GM = 64, GK = 16, GLDA = GM + 4, GLDB = 256 + 4;
+
+__global__ __launch_bounds__(256) void patch_rgb_wgrad_kernel(const float* __restrict__ dx, int tok, int first, const float* __restrict__ img,
+                                                              int64_t rows, int chunk, int Np, int gw, int H, int W, int E,
+                                                              float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float As[2][GK][GLDA];   // As[k][channel]
+    __shared__ __attribute__((aligned(16))) float Bs[2][GK][GLDB];   // Bs[k][16 i + j]  (j = 14, 15 and columns >= 224 never feed a kept result)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rb = wave & 1, cb0 = (wave >> 1) * 4;
+    const int e0 = blockIdx.x * GM, ch = blockIdx.y;
+    const int64_t r0 = (int64_t)blockIdx.z * chunk;
+    const int64_t r1 = r0 + chunk < rows ? r0 + chunk : rows;
+    // thread -> patch row k = tid / 16 of the K-step: four channels 4 (tid % 16) of its gradient row, and the float2 pieces
+    // (tid % 16) + 16 q < 98 (kernel row piece / 7, pixel pair piece % 7) of its 14 x 14 pixels
+    const int k = tid >> 4, t16 = tid & 15;
+    int boff[7], bcol[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        const int piece = t16 + 16 * q, i = piece / 7, j2 = piece % 7;
+        boff[q] = i * W + 2 * j2;
+        bcol[q] = 16 * i + 2 * j2;
+    }
+    float4 ra;
+    float2 rp[7];
+#define LOAD(K0)                                                                                                            \
+    do {                                                                                                                    \
+        const int64_t m = r0 + (K0) + k;                                                                                    \
+        ra = make_float4(0.f, 0.f, 0.f, 0.f);                                                                               \
+        _Pragma("unroll") for (int q = 0; q < 7; ++q) rp[q] = make_float2(0.f, 0.f);                                        \
+        if (m < r1) {                                                                                                       \
+            const int64_t s = m / Np;                                                                                       \
+            const int p = (int)(m - s * Np), py = p / gw, px = p - py * gw;                                                 \
+            ra = *reinterpret_cast<const float4*>(dx + (s * tok + first + p) * (int64_t)E + e0 + 4 * t16);                  \
+            const float* pix = img + ((s * 3 + ch) * H + 14 * py) * (int64_t)W + 14 * px;                                   \
+            _Pragma("unroll") for (int q = 0; q < 7; ++q)                                                                   \
+                if (t16 + 16 * q < 98) rp[q] = *reinterpret_cast<const float2*>(pix + boff[q]);                             \
+        }                                                                                                                   \
+    } while (0)
+#define STORE(BUF)                                                                                                          \
+    do {                                                                                                                    \
+        *reinterpret_cast<float4*>(&As[BUF][k][4 * t16]) = ra;                                                              \
+        _Pragma("unroll") for (int q = 0; q < 7; ++q)                                                                       \
+            if (t16 + 16 * q < 98) *reinterpret_cast<float2*>(&Bs[BUF][k][bcol[q]]) = rp[q];                                \
+    } while (0)
+    f32x16 acc0, acc1, acc2, acc3;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = acc2[r] = acc3[r] = 0.f;
+    const int len = (int)(r1 - r0);
+    LOAD(0);
+    STORE(0);
+    __syncthreads();
+    const bool has3 = cb0 + 3 < 7;                     // wave-uniform: the upper waves' fourth block is padding
+    for (int k0 = 0; k0 < len; k0 += GK) {
+        const int cur = (k0 / GK) & 1;
+        const bool more = k0 + GK < len;
+        if (more) LOAD(k0 + GK);                       // in flight across the MFMAs below
+#pragma unroll
+        for (int kk = 0; kk < GK / 2; ++kk) {
+            const int kq = 2 * kk + (lane >> 5), c = lane & 31;
+            const float a = As[cur][kq][rb * 32 + c];
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[cur][kq][(cb0 + 0) * 32 + c], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[cur][kq][(cb0 + 1) * 32 + c], acc1, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[cur][kq][(cb0 + 2) * 32 + c], acc2, 0, 0, 0);
+            if (has3) acc3 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[cur][kq][(cb0 + 3) * 32 + c], acc3, 0, 0, 0);
+        }
+        if (more) STORE(cur ^ 1);
+        __syncthreads();
+    }
+#undef LOAD
+#undef STORE
+    // epilogue: lane holds column 16 i + j of 16 channels; dW partial [z][e][ch][i][j]
+    float* const out = part + ((int64_t)blockIdx.z * E + e0) * 588 + ch * 196;
+    const int hi = lane >> 5;
+#define PUT(ACC, CB)                                                                                                        \
+    do {                                                                                                                    \
+        const int col = (CB) * 32 + (lane & 31), i = col >> 4, j = col & 15;                                                \
+        if (j < 14 && i < 14) {                                                                                             \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                                  \
+                out[(int64_t)(rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) * 588 + 14 * i + j] = (ACC)[r];                    \
+        }                                                                                                                   \
+    } while (0)
+    PUT(acc0, cb0 + 0);
+    PUT(acc1, cb0 + 1);
+    PUT(acc2, cb0 + 2);
+    if (has3) PUT(acc3, cb0 + 3);
+#undef PUT
+}
+
 }  // namespace
+
+// dx fp32 [n * tok, E] (patch rows from row `first` of every image), img fp32 [n, 3, H, W], part fp32 [ceil(n Np / rows_per_split)][E][3][14][14]
+int launch_patch_embed_rgb_wgrad(const float* dx, int tok, int first, const float* img, int n, int H, int W, int E, int rows_per_split,
+                                 float* part, hipStream_t s) {
+    MST_CHECK_ARG(n > 0 && H > 0 && W > 0 && H % PATCH == 0 && W % PATCH == 0, "patch_embed_rgb_wgrad: n=%d H=%d W=%d (H, W multiples of 14)", n, H, W);
+    MST_CHECK_ARG(E > 0 && E % GM == 0, "patch_embed_rgb_wgrad: E=%d must be a positive multiple of %d", E, GM);
+    const int gw = W / PATCH, Np = (H / PATCH) * gw;
+    MST_CHECK_ARG(first >= 0 && tok >= first + Np, "patch_embed_rgb_wgrad: %d tokens per image cannot hold %d patch rows from row %d", tok, Np, first);
+    MST_CHECK_ARG(rows_per_split > 0 && rows_per_split % GK == 0, "patch_embed_rgb_wgrad: rows_per_split=%d must be a positive multiple of %d",
+                  rows_per_split, GK);
+    MST_CHECK_ARG(aligned(dx, 16) && aligned(img, 8) && aligned(part, 4), "patch_embed_rgb_wgrad: dx must be 16-byte, img 8-byte aligned");
+    const int64_t rows = (int64_t)n * Np, splits = (rows + rows_per_split - 1) / rows_per_split;
+    MST_CHECK_ARG(splits <= 65535, "patch_embed_rgb_wgrad: %lld splits of %d patch rows (at most 65535)", (long long)splits, rows_per_split);
+    patch_rgb_wgrad_kernel<<<dim3(E / GM, 3, (unsigned)splits), dim3(256), 0, s>>>(dx, tok, first, img, rows, rows_per_split, Np, gw, H, W, E, part);
+    return mst_check_launch("patch_embed_rgb_wgrad");
+}
 
 // img [n, 3, H, W] of idt; wp [E][3][14][16] of dt (columns 14, 15 of every kernel row zero); x fp32 [n * (n_prefix + Np), E]
 int launch_patch_embed_rgb(const void* img, int idt, int n, int H, int W, const void* wp, int dt, const float* bias, const float* prefix,

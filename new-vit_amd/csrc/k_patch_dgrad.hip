@@ -10,6 +10,11 @@
 // double-buffered, the next step's operands in registers across the current step's MFMAs (one barrier per step, as gemm_ex).  Epilogue:
 // the 64 x 196 tile goes through LDS (aliasing the operand buffers) and leaves as 14-float patch rows, consecutive threads on
 // consecutive pixels of one image row.  No atomics: the result does not depend on scheduling.
+//
+// mst_patch_embed_rgb_dgrad is the same kernel over three DISTINCT channels (the encoder API's [n, 3, H, W] input, patch_embed.py:65,75-81):
+// blockIdx.y is the channel, whose 224 columns of the [E][3][14][16] kernel image (ldw = 672) play wsum and whose plane of dimg is written:
+//   dimg[s, c, 14 py + i, 14 px + j] = sum_e dx[s, first + py gw + px, e] * w[e, c, i, j]
+// The grey call is C = 1, ldw = 224: the same instructions on the same operands as before.
 #include "mst_common.h"
 
 namespace {
@@ -22,12 +27,13 @@ constexpr int LDB = 256 + 4;           // Bs[k][col], 256 staged columns (224..2
 constexpr int LDO = 200;               // Os[row][14 i + j]: rows r and r + 4 (the two half-waves of an MFMA result) 32 banks apart
 constexpr int SMEM = (2 * TK * LDA + 2 * TK * LDB) > TM * LDO ? (2 * TK * LDA + 2 * TK * LDB) : TM * LDO;
 
-__device__ __forceinline__ float4 wtile(const float* __restrict__ wsum, int k0, int idx) {
+__device__ __forceinline__ float4 wtile(const float* __restrict__ wsum, int ldw, int k0, int idx) {
     const int k = idx >> 6, c = (idx & 63) * 4;
-    return c < KP ? *reinterpret_cast<const float4*>(wsum + (int64_t)(k0 + k) * KP + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    return c < KP ? *reinterpret_cast<const float4*>(wsum + (int64_t)(k0 + k) * ldw + c) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __global__ __launch_bounds__(256) void patch_dgrad_kernel(const float* __restrict__ dx, int tok, int first, const float* __restrict__ wsum,
+                                                          int ldw, int C,
                                                           int64_t rows, int Np, int gw, int H, int W, int E, float* __restrict__ dvol) {
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
     __shared__ int64_t rbase[TM];
@@ -36,6 +42,8 @@ __global__ __launch_bounds__(256) void patch_dgrad_kernel(const float* __restric
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rb = wave & 1, cb0 = (wave >> 1) * 4;
     const int64_t m0 = (int64_t)blockIdx.x * TM;
+    const int ch = blockIdx.y;                         // channel plane of the output; its 224 columns of the kernel image
+    wsum += ch * KP;
     // A operand (the patch-row gradients): thread -> (row tid / 4, four channels 4 (tid % 4)) of the K-step, one float4
     const int ar = tid >> 2, ak = (tid & 3) * 4;
     const bool a_ok = m0 + ar < rows;
@@ -51,7 +59,7 @@ __global__ __launch_bounds__(256) void patch_dgrad_kernel(const float* __restric
         if (m < rows) {
             const int64_t s = m / Np;
             const int p = (int)(m - s * Np), py = p / gw, px = p - py * gw;
-            b = (s * H + 14 * py) * (int64_t)W + 14 * px;
+            b = ((s * C + ch) * H + 14 * py) * (int64_t)W + 14 * px;
         }
         rbase[tid] = b;
     }
@@ -60,8 +68,8 @@ __global__ __launch_bounds__(256) void patch_dgrad_kernel(const float* __restric
 #define LOAD(K0)                                                                                                            \
     do {                                                                                                                    \
         ra = a_ok ? *reinterpret_cast<const float4*>(arow + (K0) + ak) : make_float4(0.f, 0.f, 0.f, 0.f);                  \
-        rw0 = wtile(wsum, (K0), tid); rw1 = wtile(wsum, (K0), tid + 256);                                                   \
-        rw2 = wtile(wsum, (K0), tid + 512); rw3 = wtile(wsum, (K0), tid + 768);                                             \
+        rw0 = wtile(wsum, ldw, (K0), tid); rw1 = wtile(wsum, ldw, (K0), tid + 256);                                                   \
+        rw2 = wtile(wsum, ldw, (K0), tid + 512); rw3 = wtile(wsum, ldw, (K0), tid + 768);                                             \
     } while (0)
 #define STORE(BUF)                                                                                                          \
     do {                                                                                                                    \
@@ -123,7 +131,10 @@ __global__ __launch_bounds__(256) void patch_dgrad_kernel(const float* __restric
 
 }  // namespace
 
-int launch_patch_embed_dgrad(const float* dx, int tok, int first, const float* wsum, int n, int H, int W, int E, float* dvol, hipStream_t s) {
+// C = 1: wsum [E][224], dvol [n, H, W];  C = 3: wsum = the kernel image [E][3][224], dvol [n, 3, H, W]
+int launch_patch_embed_dgrad(const float* dx, int tok, int first, const float* wsum, int C, int n, int H, int W, int E, float* dvol,
+                             hipStream_t s) {
+    MST_CHECK_ARG(C == 1 || C == 3, "patch_embed_dgrad: %d channels (1 or 3)", C);
     MST_CHECK_ARG(n > 0 && H > 0 && W > 0 && H % 14 == 0 && W % 14 == 0, "patch_embed_dgrad: n=%d H=%d W=%d (H, W multiples of 14)", n, H, W);
     MST_CHECK_ARG(E > 0 && E % TK == 0, "patch_embed_dgrad: E=%d must be a positive multiple of %d", E, TK);
     const int gw = W / 14, Np = (H / 14) * gw;
@@ -132,6 +143,6 @@ int launch_patch_embed_dgrad(const float* dx, int tok, int first, const float* w
                   "patch_embed_dgrad: dx and wsum must be 16-byte aligned");
     const int64_t rows = (int64_t)n * Np, blocks = (rows + TM - 1) / TM;
     MST_CHECK_ARG(blocks < (1ll << 31), "patch_embed_dgrad: %lld patch rows out of range", (long long)rows);
-    patch_dgrad_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(dx, tok, first, wsum, rows, Np, gw, H, W, E, dvol);
+    patch_dgrad_kernel<<<dim3((unsigned)blocks, C), dim3(256), 0, s>>>(dx, tok, first, wsum, C * KP, C, rows, Np, gw, H, W, E, dvol);
     return mst_check_launch("patch_embed_dgrad");
 }

@@ -353,7 +353,22 @@ int mst_pos_embed_interp_bwd(const float* dout, int M, int E, int gh, int gw, do
 int mst_patch_embed_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wsum, int n, int H, int W, int E,
                           float* dvol, mst_stream_t stream) {
     MST_CHECK_ARG(dx && wsum && dvol, "patch_embed_dgrad: null pointer");
-    return launch_patch_embed_dgrad(dx, tokens_per_image, first_patch_token, wsum, n, H, W, E, dvol, (hipStream_t)stream);
+    return launch_patch_embed_dgrad(dx, tokens_per_image, first_patch_token, wsum, 1, n, H, W, E, dvol, (hipStream_t)stream);
+}
+int mst_patch_embed_rgb(const float* img, int n, int H, int W, const float* wp, const float* bias, const float* prefix, int n_prefix,
+                        const float* pos_patch, int E, float* x, mst_stream_t stream) {
+    MST_CHECK_ARG(img && wp && bias && prefix && pos_patch && x, "patch_embed_rgb: null pointer");
+    return launch_patch_embed_rgb(img, MST_F32, n, H, W, wp, MST_F32, bias, prefix, n_prefix, pos_patch, E, x, (hipStream_t)stream);
+}
+int mst_patch_embed_rgb_dgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* wp, int n, int H, int W, int E,
+                              float* dimg, mst_stream_t stream) {
+    MST_CHECK_ARG(dx && wp && dimg, "patch_embed_rgb_dgrad: null pointer");
+    return launch_patch_embed_dgrad(dx, tokens_per_image, first_patch_token, wp, 3, n, H, W, E, dimg, (hipStream_t)stream);
+}
+int mst_patch_embed_rgb_wgrad(const float* dx, int tokens_per_image, int first_patch_token, const float* img, int n, int H, int W, int E,
+                              int rows_per_split, float* part, mst_stream_t stream) {
+    MST_CHECK_ARG(dx && img && part, "patch_embed_rgb_wgrad: null pointer");
+    return launch_patch_embed_rgb_wgrad(dx, tokens_per_image, first_patch_token, img, n, H, W, E, rows_per_split, part, (hipStream_t)stream);
 }
 
 // ---- convolutional backbone of the ResNet models ------------------------------------------------------------

@@ -452,8 +452,11 @@ int launch_axpby_cols(const float* x, int64_t xs, const float* g, float alpha, f
                       int cols, hipStream_t s);
 int launch_im2col14(const void* vol, int dt, int n, int H, int W, float* col, hipStream_t s);
 int launch_pos_interp_bwd(const float* dout, int M, int E, int gh, int gw, double offset, float* dpos, hipStream_t s);
-int launch_patch_embed_dgrad(const float* dx, int tok, int first, const float* wsum, int n, int H, int W, int E, float* dvol,
-                             hipStream_t s);   // k_patch_dgrad.hip
+int launch_patch_embed_dgrad(const float* dx, int tok, int first, const float* wsum, int C, int n, int H, int W, int E, float* dvol,
+                             hipStream_t s);   // k_patch_dgrad.hip: C = 1 grey (wsum [E][224]), C = 3 RGB (the kernel image [E][3][224])
+// k_features.hip: partial weight gradients of the RGB patch embedding, part [ceil(n Np / rows_per_split)][E][3][14][14]
+int launch_patch_embed_rgb_wgrad(const float* dx, int tok, int first, const float* img, int n, int H, int W, int E, int rows_per_split,
+                                 float* part, hipStream_t s);
 // convolutional backbone (k_conv.hip)
 int launch_im2col_nhwc(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad, int Kpad, float* col,
                        hipStream_t s);

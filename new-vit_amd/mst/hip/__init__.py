@@ -99,6 +99,10 @@ SIGNATURES = {
     "mst_im2col14": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mst_pos_embed_interp_bwd": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp]),
     "mst_patch_embed_dgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # the three-channel patch embedding at the op level: forward, input gradient, split weight gradient (csrc/k_features.hip, k_patch_dgrad.hip)
+    "mst_patch_embed_rgb": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "mst_patch_embed_rgb_dgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mst_patch_embed_rgb_wgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     # 16-bit storage mode of the training step (csrc/k_train16.hip; act / swiglu in k_train.hip, the column sums in k_colsum.hip)
     "mst_residual_layernorm16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "mst_act_fwd16": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
@@ -1175,6 +1179,72 @@ def patch_embed_dgrad(dx: torch.Tensor, wsum: torch.Tensor, n: int, H: int, W: i
         raise ValueError(f"patch_embed_dgrad: out must be contiguous fp32 [{n}, {H}, {W}] on dx's device")
     _check(load().mst_patch_embed_dgrad(ptr(dx), tokens, first, ptr(wsum), n, H, W, E, ptr(out), stream_of(dx)), "mst_patch_embed_dgrad")
     return out
+
+
+def _rgb_rows(what: str, dx: torch.Tensor, n: int, H: int, W: int, E: int, tokens: Optional[int]) -> int:
+    """Tokens per image of the [n * tokens, E] gradient rows `dx` of an RGB patch-embedding gradient (default: the patch rows alone)."""
+    _dev(dx, what)
+    tokens = (H // 14) * (W // 14) if tokens is None else tokens
+    if dx.dtype != torch.float32 or dx.numel() != n * tokens * E:
+        raise ValueError(f"{what}: dx must be contiguous fp32 [{n} * {tokens}, {E}]")
+    return tokens
+
+
+def patch_embed_rgb(img: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, prefix: torch.Tensor, pos_patch: torch.Tensor) -> torch.Tensor:
+    """mst_patch_embed_rgb: tokens x fp32 [n, n_prefix + Np, E] of fp32 images [n, 3, H, W]; wp = pack_patch_rgb(weight, torch.float32)."""
+    _dev(img, "patch_embed_rgb")
+    n, C, H, W = img.shape
+    E = wp.shape[0]
+    if C != 3 or img.dtype != torch.float32 or wp.dtype != torch.float32 or tuple(wp.shape) != (E, 672) or not wp.is_contiguous():
+        raise ValueError("patch_embed_rgb: img must be fp32 [n, 3, H, W], wp the contiguous fp32 [E, 672] image of pack_patch_rgb")
+    n_prefix = prefix.shape[0]
+    x = torch.empty((n, n_prefix + (H // 14) * (W // 14), E), dtype=torch.float32, device=img.device)
+    _check(load().mst_patch_embed_rgb(ptr(img), n, H, W, ptr(wp), ptr(bias), ptr(prefix), n_prefix, ptr(pos_patch), E, ptr(x), stream_of(img)),
+           "mst_patch_embed_rgb")
+    return x
+
+
+def patch_embed_rgb_dgrad(dx: torch.Tensor, wp: torch.Tensor, n: int, H: int, W: int, tokens: Optional[int] = None, first: int = 0,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mst_patch_embed_rgb_dgrad: the gradient with respect to the images [n, 3, H, W] (fp32) from the patch-row gradients in dx (rows as
+    in `patch_embed_dgrad`); wp is the fp32 [E, 672] kernel image of pack_patch_rgb.  Every pixel of `out` is written once."""
+    E = wp.shape[0]
+    tokens = _rgb_rows("patch_embed_rgb_dgrad", dx, n, H, W, E, tokens)
+    if wp.dtype != torch.float32 or not wp.is_contiguous() or tuple(wp.shape) != (E, 672) or wp.device != dx.device:
+        raise ValueError("patch_embed_rgb_dgrad: wp must be the contiguous fp32 [E, 672] image of pack_patch_rgb on dx's device")
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dx.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, 3, H, W) or out.device != dx.device:
+        raise ValueError(f"patch_embed_rgb_dgrad: out must be contiguous fp32 [{n}, 3, {H}, {W}] on dx's device")
+    _check(load().mst_patch_embed_rgb_dgrad(ptr(dx), tokens, first, ptr(wp), n, H, W, E, ptr(out), stream_of(dx)), "mst_patch_embed_rgb_dgrad")
+    return out
+
+
+def rgb_wgrad_split_rows(rows: int) -> int:
+    """Patch rows per partial of mst_patch_embed_rgb_wgrad: 256, or what keeps the partials at 16 (a multiple of the kernel's K-step)."""
+    return max(256, -(-rows // (16 * 16)) * 16)
+
+
+def patch_embed_rgb_wgrad(dx: torch.Tensor, img: torch.Tensor, E: int, tokens: Optional[int] = None, first: int = 0,
+                          part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d weight [E, 3, 14, 14] of the RGB patch embedding from the patch-row gradients in dx and the fp32 images [n, 3, H, W], read in
+    place: mst_patch_embed_rgb_wgrad's partials over `rgb_wgrad_split_rows` patch rows each, reduced by `colsum` (atomic, or in fixed
+    order under the deterministic flag).  part: the caller's [splits, E * 588] buffer for the partials."""
+    _dev(img, "patch_embed_rgb_wgrad")
+    n, C, H, W = img.shape
+    tokens = _rgb_rows("patch_embed_rgb_wgrad", dx, n, H, W, E, tokens)
+    if C != 3 or img.dtype != torch.float32 or img.device != dx.device:
+        raise ValueError("patch_embed_rgb_wgrad: img must be fp32 [n, 3, H, W] on dx's device")
+    rows = n * (H // 14) * (W // 14)
+    chunk = rgb_wgrad_split_rows(rows)
+    splits = -(-rows // chunk)
+    if part is None:
+        part = torch.empty((splits, E * 588), dtype=torch.float32, device=dx.device)
+    elif part.dtype != torch.float32 or not part.is_contiguous() or tuple(part.shape) != (splits, E * 588) or part.device != dx.device:
+        raise ValueError(f"patch_embed_rgb_wgrad: part must be contiguous fp32 [{splits}, {E * 588}] on dx's device")
+    _check(load().mst_patch_embed_rgb_wgrad(ptr(dx), tokens, first, ptr(img), n, H, W, E, chunk, ptr(part), stream_of(dx)),
+           "mst_patch_embed_rgb_wgrad")
+    return colsum(part, torch.zeros(E * 588, dtype=torch.float32, device=dx.device)).view(E, 3, 14, 14)
 
 
 def pos_embed_interp_bwd(dout: torch.Tensor, M: int, gh: int, gw: int, offset: float, dpos: torch.Tensor):

@@ -20,6 +20,15 @@ Build-specific (keyword-only, all optional) controls -- none changes the maths o
                   slice-sharded or not.  Its backward yields every asked-for parameter gradient and d ``source`` (source's shape,
                   dtype and device).  Such a call computes its logits on the TRAINING forward (fp32, or ``train_precision``'s linear
                   products), not on ``compute_dtype``.
+  encoder_grad    False (default) | True: ``encoder.forward`` / ``forward_features`` / ``get_intermediate_layers`` under grad mode with a
+                  trainable encoder parameter or an ``x`` that requires grad.  False: they refuse (NotImplementedError: a feature loop that
+                  forgot ``torch.no_grad()`` must not silently start keeping every block's state).  True: the call returns tensors of ONE
+                  autograd node whose backward runs on the HIP kernels -- gradients enter at every token row and behind any block -- and,
+                  as for ``source.grad`` above, its numbers come from the TRAINING forward (fp32, or ``train_precision`` /
+                  ``train_attention`` / ``train_storage``, autocast included), not from ``compute_dtype``.  Also the attribute
+                  ``model.encoder_grad``, read at every call.  ``train_chunk_slices`` and slice sharding do not apply to these calls
+                  (all tokens of local images).  Under ``torch.no_grad()``, or with a frozen encoder and an ``x`` that needs no
+                  gradient, the calls are the inference path whatever the switch says and keep nothing.
   ffn_layer       None (default) | 'mlp' | 'swiglufused' | 'swiglu' (the alias the reference accepts, vision_transformer.py:124): the blocks'
                   feed-forward network.  None is what the reference builds: the plain GELU MLP, but SwiGLUFFNFused for the hub's
                   dinov2_vitg14 (``pretrained=True, model_size='g'``).  State-dict keys follow: ``mlp.fc1/fc2`` or ``mlp.w12/w3``.
@@ -180,7 +189,8 @@ class _ViT(_Params):
     ``forward_features``, ``get_intermediate_layers`` (vision_transformer.py:254-329) -- on the HIP path of the owning
     ``DinoV2ClassifierSlice`` (``encode_features``).  ``x`` is ``[n, 3, H, W]``, the reference's contract, or ``[n, 1, H, W]``: the
     build's grey fast path with the numbers of ``x.repeat(1, 3, 1, 1)`` and the bits of ``encode_slices``.  Results are fresh fp32
-    tensors on the model's device.  Inference only: the mask-token path (SSL pre-training) and gradients are refused."""
+    tensors on the model's device.  The mask-token path (SSL pre-training) is refused; so are gradients unless the owner's ``encoder_grad``
+    is on (then one autograd node per call on the training path: mst/train.py `encoder_forward_with_grad`)."""
 
     def __init__(self, embed_dim, depth, num_heads, img_size=224, num_register_tokens=0,
                  layerscale: Optional[float] = None, chunked=True, ffn_layer: str = "mlp"):
@@ -213,9 +223,10 @@ class _ViT(_Params):
         return list(self.blocks[0]) if self.chunked else list(self.blocks)
 
     # ---- the reference's inference calls (vision_transformer.py:254-329) --------------------------------------------------------
-    def _encode(self, x, blocks, norm: bool, want_cls: bool):
-        """(class tokens [n, E] or None, taps [len(blocks), n, N, E] or None) from the owning model.  Refusals in the order the
-        callers rely on: no CPU fallback, then a gradient request."""
+    def _encode(self, x, blocks, norm: bool, want_cls: bool, prenorm: bool = False):
+        """(class tokens [n, E] or None, taps [len(blocks), n, N, E] or None, with `prenorm` (and `norm`) the same taps un-normalised, else
+        None) from the owning model.  Refusals in the order the callers rely on: no CPU fallback, then a gradient request -- unless the
+        owner's ``encoder_grad`` is on: then the three come from one autograd node of the training path (mst/train.py)."""
         owner = self._owner()
         dev = owner.device if owner is not None else self.cls_token.device
         if dev.type != "cuda":
@@ -224,9 +235,16 @@ class _ViT(_Params):
             raise RuntimeError("this encoder is not attached to a DinoV2ClassifierSlice (a copy of the encoder alone?): assign it, "
                                "`model.encoder = encoder`; the model holds the weight images and workspaces its calls run on")
         if torch.is_grad_enabled() and ((isinstance(x, torch.Tensor) and x.requires_grad) or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("the encoder API (forward / forward_features / get_intermediate_layers) is inference-only: "
-                                      "call it under torch.no_grad(); gradients run through DinoV2ClassifierSlice.forward")
-        return owner.encode_features(x, blocks, norm, want_cls)
+            if not getattr(owner, "encoder_grad", False):
+                raise NotImplementedError("the encoder API (forward / forward_features / get_intermediate_layers) is inference-only: "
+                                          "call it under torch.no_grad(); gradients run through DinoV2ClassifierSlice.forward")
+            owner.check_features_input(x)
+            from .. import train
+            return train.encoder_forward_with_grad(owner, x, blocks, norm, want_cls, prenorm)
+        if not (norm and prenorm):
+            return (*owner.encode_features(x, blocks, norm, want_cls), None)
+        cls, raw = owner.encode_features(x, blocks, False, want_cls)
+        return cls, hip.layernorm(raw, self.norm.weight.detach().float().contiguous(), self.norm.bias.detach().float().contiguous(), 1e-6), raw
 
     def forward_features_list(self, x_list, masks_list):
         raise NotImplementedError("forward_features_list (list input) is the SSL pre-training path of the reference (multi-crop with "
@@ -239,9 +257,8 @@ class _ViT(_Params):
         if isinstance(x, list):
             return self.forward_features_list(x, masks)
         R = self.num_register_tokens
-        _, taps = self._encode(x, (self.depth - 1,), False, False)
-        x_prenorm = taps[0]
-        x_norm = hip.layernorm(x_prenorm, self.norm.weight.detach().float().contiguous(), self.norm.bias.detach().float().contiguous(), 1e-6)
+        _, taps, raw = self._encode(x, (self.depth - 1,), True, False, prenorm=True)
+        x_norm, x_prenorm = taps[0], raw[0]
         return {"x_norm_clstoken": x_norm[:, 0], "x_norm_regtokens": x_norm[:, 1:R + 1], "x_norm_patchtokens": x_norm[:, R + 1:],
                 "x_prenorm": x_prenorm, "masks": masks}                    # views of one fresh tensor, as the reference returns them
 
@@ -250,7 +267,7 @@ class _ViT(_Params):
         take = range(total - n, total) if isinstance(n, int) else n
         found = sorted({int(i) for i in take if 0 <= int(i) < total})
         assert len(found) == len(take), f"only {len(found)} / {len(take)} blocks found"
-        _, taps = self._encode(x, found, bool(norm), False)
+        _, taps, _ = self._encode(x, found, bool(norm), False)
         R = self.num_register_tokens
         class_tokens = [t[:, 0] for t in taps]
         outputs = [t[:, 1 + R:] for t in taps]
@@ -264,7 +281,7 @@ class _ViT(_Params):
     def forward(self, x, masks=None, is_training=False):
         if is_training or masks is not None or isinstance(x, list):   # the last two raise: the same refusals, in the same order
             return self.forward_features(x, masks)
-        cls, _ = self._encode(x, (), True, True)
+        cls, _, _ = self._encode(x, (), True, True)
         return cls                                                    # head = nn.Identity (vision_transformer.py:168)
 
 
@@ -383,6 +400,8 @@ class DinoV2ClassifierSlice(BasicClassifier):
         train_precision, train_attention, train_storage, _precision_given = train_mode.from_kwargs(
             kwargs, storage_env="MST_TRAIN_STORAGE", attention=True)
         train_chunk_slices = train_mode.chunk_from_kwargs(kwargs)
+        # opt-in: encoder.forward / forward_features / get_intermediate_layers carry gradients (mst/train.py `encoder_forward_with_grad`)
+        encoder_grad = bool(kwargs.pop("encoder_grad", False))
         if compute_dtype not in hip.DT_NAMES:
             raise ValueError(f"compute_dtype must be one of {sorted(hip.DT_NAMES)}")
         super().__init__(in_ch, out_ch, spatial_dims=spatial_dims, optimizer_kwargs=optimizer_kwargs, **kwargs)
@@ -397,6 +416,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         self.train_attention = train_attention
         self.train_storage = train_storage
         self.train_chunk_slices = train_chunk_slices
+        self.encoder_grad = encoder_grad                # a plain attribute: may be changed between calls
         self._train_precision_given = _precision_given
         self._graphs = {}
         self.save_attn = save_attn
@@ -684,14 +704,7 @@ class DinoV2ClassifierSlice(BasicClassifier):
         calls -> (normalised class tokens ``[n, E]`` or None, ``[len(blocks), n, N, E]`` or None: the residual stream behind the blocks
         ``blocks`` (ascending), through ``encoder.norm`` when ``norm``).  Local to the rank: slice sharding does not apply.  The kernel
         plan follows the token count of the call exactly as in ``encode_slices``; a tapped call stays on it."""
-        if self.compute_dtype_name in hip.FP8_NAMES:
-            raise NotImplementedError("compute_dtype='fp8' computes class tokens only (its e4m3 pipeline has no taps): use bf16, fp16 or "
-                                      "fp32 for forward_features / get_intermediate_layers")
-        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[1] in (1, 3)):
-            raise ValueError(f"the encoder takes [n, 3, H, W] images (or [n, 1, H, W] grey ones); got {tuple(getattr(x, 'shape', ()))}")
-        n, ch, H, W = x.shape
-        assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
-        assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
+        n, ch, H, W = self.check_features_input(x)
         prep = self._prepare()
         x = x.detach().to(self.device)
         if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -720,6 +733,18 @@ class DinoV2ClassifierSlice(BasicClassifier):
         out = torch.empty((len(blocks), n, N, E), dtype=torch.float32, device=dev) if blocks else None
         hip.vit_encode_features(vit, x, chunk, ws, patch_w_rgb=wrgb, cls_out=cls, blocks=blocks, norm=norm, out=out)
         return cls, out
+
+    def check_features_input(self, x):
+        """The refusals every encoder API call starts with, inference or grad mode -> x's (n, channels, H, W)."""
+        if self.compute_dtype_name in hip.FP8_NAMES:
+            raise NotImplementedError("compute_dtype='fp8' computes class tokens only (its e4m3 pipeline has no taps): use bf16, fp16 or "
+                                      "fp32 for forward_features / get_intermediate_layers")
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[1] in (1, 3)):
+            raise ValueError(f"the encoder takes [n, 3, H, W] images (or [n, 1, H, W] grey ones); got {tuple(getattr(x, 'shape', ()))}")
+        n, ch, H, W = x.shape
+        assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
+        assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
+        return n, ch, H, W
 
     def fuse_slices(self, emb: torch.Tensor, B: int, D: int, mask: Optional[torch.Tensor], want_probs: bool,
                     want_logits: bool):

@@ -55,6 +55,13 @@ which on model_size='s' makes the host the bound (measured: DESIGN.md 4b, profil
 the same, an empty shard still launches nothing.  The ResNet step (mst/train_resnet.py) has no such mode: BatchNorm's batch statistics couple
 the slices of a batch.
 
+The encoder API in grad mode (``encoder_grad=True``; models/dino.py `_ViT._encode`): `encoder_forward_with_grad` is one node per call over
+x [n, 3, H, W] (the RGB patch embedding and its own data / weight gradients, csrc/k_features.hip) or [n, 1, H, W] and the parameters, on
+`_encoder_fwd` / `_encoder_bwd` in the resolved mode.  Its outputs are the class tokens and the streams behind the asked-for blocks (saved
+block inputs: a tap keeps nothing of its own), so gradients enter `_encoder_bwd` at every token row and behind any block; the forward
+stops behind the highest block asked for, the backward starts at the highest block a gradient enters behind.  train_chunk_slices and slice
+sharding do not apply to these calls (all tokens of local images).
+
 A frozen encoder keeps nothing: when no encoder parameter and not ``source`` needs a gradient (the node's needs_input_grad; `forward_train`'s
 ``encoder_state``), the forward drops the block state as soon as the embeddings exist, whatever k is -- the backward returns before the
 encoder anyway.  Outputs and the remaining gradients are the same bits.
@@ -371,13 +378,7 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
     D = D0 * C
     assert H % PATCH == 0, f"Input image height {H} is not a multiple of patch height {PATCH}"
     assert W % PATCH == 0, f"Input image width {W} is not a multiple of patch width: {PATCH}"
-    n_stored = enc.pos_embed.shape[1] - 1
-    interp = not ((H // PATCH) * (W // PATCH) == n_stored and H == W)
-    if interp and int(enc.num_register_tokens):
-        # register encoders are the hub's dinov2_vit*14_reg (anti-aliased, size-based resampling: models/dino.py::_pos_patch); the
-        # adjoint of that filter is not built -- train them at the stored grid (518 x 518 for the hub weights)
-        raise NotImplementedError("training step: register-token encoders train at their stored position grid only (the adjoint of the "
-                                  "anti-aliased position resampling is not on the HIP backward)")
+    interp = _pos_resampled(enc, H, W)
     d0, d1, dpad = sh.shard_range(D) if sh is not None else (0, D, D)
     dl = d1 - d0                                         # this rank's slices [d0, d1) of every volume: all of them without sharding
     vol = (x.reshape(B, D, H, W)[:, d0:d1].to(dev) if sh is not None else x).reshape(B * dl, H, W).float().contiguous()
@@ -402,6 +403,18 @@ def forward_train(model, source: torch.Tensor, mask: Optional[torch.Tensor], wit
         emb = sh.all_gather_slices(emb_l, D).reshape(B * D, E)
     sv["emb"] = emb
     return _fusion_head_fwd(model, sv, emb, B, D, mask, without_linear)
+
+
+def _pos_resampled(enc, H: int, W: int) -> bool:
+    """Whether an H x W input resamples the stored position grid; NotImplementedError for a register-token encoder that would."""
+    n_stored = enc.pos_embed.shape[1] - 1
+    interp = not ((H // PATCH) * (W // PATCH) == n_stored and H == W)
+    if interp and int(enc.num_register_tokens):
+        # register encoders are the hub's dinov2_vit*14_reg (anti-aliased, size-based resampling: models/dino.py::_pos_patch); the
+        # adjoint of that filter is not built -- train them at the stored grid (518 x 518 for the hub weights)
+        raise NotImplementedError("training step: register-token encoders train at their stored position grid only (the adjoint of the "
+                                  "anti-aliased position resampling is not on the HIP backward)")
+    return interp
 
 
 def _sharding_of(model):
@@ -449,9 +462,13 @@ def _encoder_consts(enc, interp: bool, H: int, W: int, dev) -> Tuple[torch.Tenso
     return pos_patch, prefix, wsum
 
 
-def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, W: int, consts=None) -> torch.Tensor:
+def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, W: int, consts=None, n_blocks: Optional[int] = None,
+                 want_cls: bool = True) -> Optional[torch.Tensor]:
     """Tokens, blocks and the final LayerNorm's CLS rows of the n slices in `vol`; what the backward needs goes into sv.  Returns the slice
-    embeddings [n, E].  consts: `_encoder_consts` of this shape if the caller has them (a chunk of several), else they are made here."""
+    embeddings [n, E].  consts: `_encoder_consts` of this shape if the caller has them (a chunk of several), else they are made here.
+    The encoder API's calls (`encoder_forward_train`) also bring: vol [n, 3, H, W], three distinct channels through the RGB patch embedding
+    (mst_patch_embed_rgb on the fp32 kernel image, kept as sv["wrgb"] for its data gradient); n_blocks, the forward stops behind block
+    n_blocks - 1 (sv["xL"] is the stream there); want_cls False, no CLS rows (returns None)."""
     enc = model.encoder
     R = int(enc.num_register_tokens)
     E, heads = enc.embed_dim, enc.num_heads
@@ -460,9 +477,13 @@ def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, 
     sv["R"] = R
     pos_patch, prefix, wsum = consts if consts is not None else _encoder_consts(enc, sv["interp"], H, W, vol.device)
     sv["wsum"] = wsum                                    # the source gradient's kernel (mst_patch_embed_dgrad) reads the same sum
-    xt = hip.patch_embed(vol, wsum, enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
+    if vol.dim() == 4:
+        sv["wrgb"] = hip.pack_patch_rgb(enc.patch_embed.proj.weight.detach(), torch.float32)
+        xt = hip.patch_embed_rgb(vol, sv["wrgb"], enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
+    else:
+        xt = hip.patch_embed(vol, wsum, enc.patch_embed.proj.bias.detach(), prefix, pos_patch).view(M, E)
     # ---- blocks (block.py:89-114)
-    blist = list(enc.block_list())
+    blist = list(enc.block_list())[:n_blocks]
     block_fwd = _block_fwd_16 if mode.storage16 else _block_fwd
     xn = hip.layernorm(xt, blist[0].norm1.weight.detach(), blist[0].norm1.bias.detach(), 1e-6, out_dtype=mode.mp) if mode.storage16 else None
     blocks = []
@@ -470,6 +491,8 @@ def _encoder_fwd(model, sv, mode: TrainMode, vol: torch.Tensor, n: int, H: int, 
         s, xt, xn = block_fwd(blk, nxt, xt, xn, mode, n, N, heads, E)
         blocks.append(s)
     sv["blocks"], sv["xL"] = blocks, xt
+    if not want_cls:
+        return None
     return hip.layernorm_rows(xt, N * E, n, E, enc.norm.weight.detach(), enc.norm.bias.detach(), 1e-6)     # CLS rows
 
 
@@ -582,11 +605,29 @@ def _encoder_bwd_chunked(G: "_Grads", model, sv, demb: torch.Tensor, n: int, nee
     return dvol
 
 
-def _encoder_bwd(G: "_Grads", model, sv, demb: torch.Tensor, n: int, need_src: bool, dvol: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+def _tap_bwd(G: "_Grads", enc, stream: torch.Tensor, dx: Optional[torch.Tensor], dnorm: Optional[torch.Tensor], draw: Optional[torch.Tensor],
+             M: int, E: int) -> torch.Tensor:
+    """The gradient of a tap joins the running d x where the walk arrives behind its block: `draw` [M, E], the gradient of the stream itself,
+    is added; `dnorm`, the gradient of encoder.norm(stream), goes through the dense LayerNorm backward with the running d x as its residual
+    input (encoder.norm's d weight / d bias of several taps sum in G, in walk order).  dx None: nothing has arrived from above."""
+    if draw is not None:
+        dx = draw.clone() if dx is None else hip.axpby_cols(draw, dx)
+    if dnorm is not None:
+        out = torch.empty((M, E), dtype=torch.float32, device=dnorm.device)
+        G.ln_bwd(stream, E, enc.norm, dnorm, E, dx, E if dx is not None else 0, out, E, M, E, 1e-6)
+        dx = out
+    return dx
+
+
+def _encoder_bwd(G: "_Grads", model, sv, demb: Optional[torch.Tensor], n: int, need_src: bool, dvol: Optional[torch.Tensor] = None,
+                 taps: Optional[Dict[int, Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]] = None) -> Optional[torch.Tensor]:
     """Backward of `_encoder_fwd` over its n slices from the gradient of their embeddings [n, E]: parameter gradients into G; returns d volume
-    ([n, H, W] fp32; written into `dvol` if the caller brings it) with `need_src`."""
+    ([n, H, W] fp32, or [n, 3, H, W] of an RGB forward; written into `dvol` if the caller brings it) with `need_src`.
+    The encoder API's node also brings taps = {block: (d encoder.norm(stream), d stream)} over all N rows of the stream behind that block
+    (either may be None), and demb may be None: the walk starts at the highest block a gradient enters behind; the blocks above it are not
+    walked and their parameters get no gradient.  Without taps the launches are the classifier's: CLS rows into d x, then every block."""
     enc = model.encoder
-    dev = demb.device
+    dev = sv["xL"].device
     H, W = sv["H"], sv["W"]
     G.mp = sv["mp"]                                      # the blocks' nn.Linear products on 16-bit operands, as the forward resolved them
     E, heads = enc.embed_dim, enc.num_heads
@@ -595,9 +636,15 @@ def _encoder_bwd(G: "_Grads", model, sv, demb: torch.Tensor, n: int, need_src: b
     R = sv["R"]
     N = 1 + R + Np
     M = n * N
-    dx = torch.zeros((M, E), dtype=torch.float32, device=dev)
-    G.ln_bwd(sv["xL"], N * E, enc.norm, demb, E, None, 0, dx, N * E, n, E, 1e-6)                         # CLS rows only
-    for blk, s in zip(reversed(enc.block_list()), reversed(sv["blocks"])):
+    blist, taps = enc.block_list(), taps or {}
+    dx = None
+    if demb is not None:
+        dx = torch.zeros((M, E), dtype=torch.float32, device=dev)
+        G.ln_bwd(sv["xL"], N * E, enc.norm, demb, E, None, 0, dx, N * E, n, E, 1e-6)                     # CLS rows only
+    for i in range(len(blist) - 1 if demb is not None else max(taps), -1, -1):
+        blk, s = blist[i], sv["blocks"][i]
+        if i in taps:                                    # the stream behind block i is block i + 1's input (the last one: xL)
+            dx = _tap_bwd(G, enc, sv["blocks"][i + 1]["x0"] if i + 1 < len(sv["blocks"]) else sv["xL"], dx, *taps[i], M, E)
         # x2 = x1 + ls2 * fc2(gelu(fc1(norm2 x1)))
         dbr = dx
         if hasattr(blk, "ls2"):
@@ -635,7 +682,10 @@ def _encoder_bwd(G: "_Grads", model, sv, demb: torch.Tensor, n: int, need_src: b
     # ---- tokens
     dsrc = None
     if need_src:                                         # d volume straight from the patch rows of dx (adjoint of the grey -> RGB patch embedding)
-        dsrc = hip.patch_embed_dgrad(dx, sv["wsum"], n, H, W, tokens=N, first=1 + R, out=dvol)
+        if "wrgb" in sv:
+            dsrc = hip.patch_embed_rgb_dgrad(dx, sv["wrgb"], n, H, W, tokens=N, first=1 + R, out=dvol)
+        else:
+            dsrc = hip.patch_embed_dgrad(dx, sv["wsum"], n, H, W, tokens=N, first=1 + R, out=dvol)
     pe = enc.patch_embed.proj
     if G.need(enc.cls_token) or G.need(enc.pos_embed):
         dcls = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -662,7 +712,9 @@ def _encoder_bwd(G: "_Grads", model, sv, demb: torch.Tensor, n: int, need_src: b
         G.put(enc.pos_embed, dpos)
     if G.need(pe.bias):
         G.put(pe.bias, hip.colsum(dpatch, torch.zeros(E, dtype=torch.float32, device=dev)))
-    if G.need(pe.weight):
+    if G.need(pe.weight) and "wrgb" in sv:               # three distinct channels: the implicit GEMM over the image in place
+        G.put(pe.weight, hip.patch_embed_rgb_wgrad(dx, sv["vol"], E, tokens=N, first=1 + R))
+    elif G.need(pe.weight):
         col = hip.im2col14(sv["vol"])
         dW = torch.empty((E, 196), dtype=torch.float32, device=dev)
         hip.gemm_ex(dpatch, col, dW, E, 196, n * Np, sa=(1, E), sb=(196, 1), sc=(196, 1))
@@ -722,3 +774,93 @@ class _MSTFunction(torch.autograd.Function):
 def forward_with_grad(model, source, mask, without_linear: bool):
     params = fp32_device_params(model)
     return _MSTFunction.apply(model, source, mask, without_linear, *params)
+
+
+# ---- the encoder API in grad mode (models/dino.py `_ViT._encode` with the owner's ``encoder_grad``) ---------------------------------------
+def encoder_forward_train(model, x: torch.Tensor, blocks, norm: bool, want_cls: bool, prenorm: bool = False, encoder_state: bool = True):
+    """`_encoder_fwd` for encoder.forward / forward_features / get_intermediate_layers on x [n, 3, H, W] or [n, 1, H, W] (the grey path:
+    mst_patch_embed on the channel sum) in the resolved training mode -> ((class tokens [n, E] or None, taps [len(blocks), n, N, E] or None:
+    the stream behind the blocks `blocks` (ascending), through encoder.norm when `norm`, the same streams un-normalised when `norm` and
+    `prenorm`, else None), the state `encoder_backward_train` reads).  The stream behind block i is block i + 1's saved input, so a tap
+    keeps nothing of its own; without class tokens the forward stops behind the highest block asked for.  All tokens of local images:
+    train_chunk_slices and slice sharding do not apply here."""
+    enc = model.encoder
+    dev = model.device
+    n, C, H, W = x.shape
+    interp = _pos_resampled(enc, H, W)
+    mode = train_mode.resolve(model)
+    vol = x.detach().to(dev).float()
+    vol = (vol.reshape(n, H, W) if C == 1 else vol).contiguous()
+    blocks = list(blocks)
+    sv = {"H": H, "W": W, "interp": interp, "mp": mode.mp, "vol": vol, "taps": blocks, "norm": bool(norm), "n": n}
+    E = enc.embed_dim
+    st = sv if encoder_state else {"interp": interp}
+    cls = _encoder_fwd(model, st, mode, vol, n, H, W, n_blocks=None if want_cls else max(blocks) + 1, want_cls=want_cls)
+    taps = raw = None
+    if blocks:
+        N = st["xL"].shape[0] // n
+        streams = [st["blocks"][i + 1]["x0"] if i + 1 < len(st["blocks"]) else st["xL"] for i in blocks]
+        if norm:
+            taps = torch.stack([hip.layernorm(t, enc.norm.weight.detach(), enc.norm.bias.detach(), 1e-6) for t in streams]).view(len(blocks), n, N, E)
+        if prenorm or not norm:
+            raw = torch.stack(streams).view(len(blocks), n, N, E)
+        if not norm:
+            taps, raw = raw, None
+    return (cls, taps, raw), sv
+
+
+def encoder_backward_train(model, sv, dcls, dtaps, draw, needed: Optional[Set[int]] = None, need_src: bool = False):
+    """Gradients of `encoder_forward_train`'s three results (each may be None: nobody used it) -> ({id(param): grad}, d x or None)."""
+    G = _Grads(needed=needed)
+    n = sv["n"]
+    if not sv["norm"]:
+        dtaps, draw = None, dtaps
+    taps = {}
+    for k, i in enumerate(sv["taps"]):
+        dn = dtaps[k].reshape(-1, dtaps.shape[-1]).contiguous().float() if dtaps is not None else None
+        dr = draw[k].reshape(-1, draw.shape[-1]).contiguous().float() if draw is not None else None
+        if dn is not None or dr is not None:
+            taps[i] = (dn, dr)
+    if dcls is None and not taps:
+        return {}, None
+    dsrc = _encoder_bwd(G, model, sv, dcls.contiguous().float() if dcls is not None else None, n, need_src, taps=taps)
+    return G.by_param, dsrc
+
+
+class _EncoderFunction(torch.autograd.Function):
+    """One autograd node per encoder API call: inputs are x and the model's parameters, outputs the dense tensors of the inference path
+    (class tokens, taps, and for forward_features the un-normalised last stream beside the normalised one).  Slicing, reshape and permutes
+    stay torch ops behind the node, so an unused row or tap arrives as zeros and an unused output as None."""
+
+    @staticmethod
+    def forward(ctx, model, x, blocks, norm, want_cls, prenorm, *params):
+        ctx.set_materialize_grads(False)
+        enc_ids = {id(p) for p in model.encoder.parameters()}
+        state = bool(ctx.needs_input_grad[1]) or any(need and id(p) in enc_ids for p, need in zip(params, ctx.needs_input_grad[6:]))
+        with torch.no_grad():
+            outs, saved = encoder_forward_train(model, x, blocks, norm, want_cls, prenorm, state)
+        ctx.model, ctx.saved, ctx.params = model, (saved if state else False), params         # False: no backward can reach the encoder, nothing kept
+        ctx.x_meta = (x.shape, x.dtype, x.device)
+        return outs
+
+    @staticmethod
+    def backward(ctx, dcls, dtaps, draw):
+        if ctx.saved is False:
+            return (None,) * (6 + len(ctx.params))
+        if ctx.saved is None:
+            raise RuntimeError("encoder API: the state of this call is gone (a second backward through the same call)")
+        needed = {id(p) for p, need in zip(ctx.params, ctx.needs_input_grad[6:]) if need}
+        need_src = bool(ctx.needs_input_grad[1])
+        with torch.no_grad():
+            grads, dsrc = encoder_backward_train(ctx.model, ctx.saved, dcls, dtaps, draw, needed, need_src)
+            if dsrc is not None:
+                shape, dtype, device = ctx.x_meta
+                dsrc = dsrc.view(shape).to(device=device, dtype=dtype)
+        ctx.saved = None
+        return (None, dsrc, None, None, None, None, *route_grads(grads, ctx.params, ctx.needs_input_grad[6:]))
+
+
+def encoder_forward_with_grad(model, x, blocks, norm: bool, want_cls: bool, prenorm: bool = False):
+    """(class tokens or None, taps or None, un-normalised taps or None) of one encoder API call, attached to one `_EncoderFunction` node."""
+    params = fp32_device_params(model)
+    return _EncoderFunction.apply(model, x, tuple(blocks), bool(norm), bool(want_cls), bool(prenorm), *params)

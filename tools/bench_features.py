@@ -10,6 +10,16 @@ at 4 x 64 x 518 x 518 (350,720 tokens) and 1 x 32 x 224 x 224 (8,224 tokens), bf
 One JSON line per shape and arm; `bytes_out` is what the arm returns (fp32), computed from the shapes.
 
     python tools/bench_features.py [--rounds 7] [--reps 5] [--out profiles/encoder_features.jsonl]
+
+--grad: what a TRAINING call of the API costs (``encoder_grad=True``).  forward_features on [n, 3, H, W], a loss over the patch tokens,
+``backward()`` with every encoder parameter and x asking for a gradient: forward + backward ms (device events, median of --rounds rounds of
+--reps calls) and the peak allocated bytes of one call above what is allocated before it, at 8 x 3 x 224^2 and 2 x 3 x 518^2, in fp32 and
+in bf16 / flash / 16bit; one JSON line each into profiles/encoder_features_grad.jsonl.  --classifier FILE: JSON lines of the classifier's
+training step at the same slice count and size (1 x 1 x 8 x 224^2, 1 x 1 x 2 x 518^2), taken with tools/bench_train.py's `train_case` on
+the parent commit; the line whose "shape" and "mode" match goes beside each record as "classifier_step".  No time is promised and
+nothing is gated on one: the lines are the record.
+
+    python tools/bench_features.py --grad [--classifier FILE] [--out profiles/encoder_features_grad.jsonl]
 """
 import argparse
 import json
@@ -37,14 +47,63 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+GRAD_SHAPES = ((8, 3, 224, 224), (2, 3, 518, 518))
+GRAD_MODES = (("fp32", {}), ("bf16/flash/16bit", dict(train_precision="bf16", train_attention="flash", train_storage="16bit")))
+
+
+def grad_lines(args):
+    beside = [json.loads(ln) for ln in Path(args.classifier).read_text().splitlines() if ln.strip()] if args.classifier else []
+    lines = []
+    for mode, kw in GRAD_MODES:
+        model = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, compute_dtype="fp32", encoder_grad=True, **kw)
+        model.load_state_dict(synth.synth_state_dict("s", 0), strict=True)
+        model = model.cuda().train()
+        enc = model.encoder
+        for shape in GRAD_SHAPES:
+            n, _, H, W = shape
+            x = torch.randn(shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(n)).requires_grad_()
+
+            def call():
+                enc.forward_features(x)["x_norm_patchtokens"].square().mean().backward()
+            for _ in range(2):
+                call()
+            model.zero_grad(set_to_none=True)
+            x.grad = None
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            call()
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - base
+            t = [timed(call, args.reps) for _ in range(args.rounds)]
+            rec = dict(bench="encoder_features_grad", device=torch.cuda.get_device_name(0), mode=mode, shape=list(shape),
+                       tokens=n * (1 + (H // 14) * (W // 14)), call="forward_features -> patch-token loss -> backward (all encoder parameters, x)",
+                       fwd_bwd_ms_median=round(statistics.median(t), 3), fwd_bwd_ms_min=round(min(t), 3), fwd_bwd_ms_max=round(max(t), 3),
+                       rounds=args.rounds, reps=args.reps, peak_allocated_bytes_above_start=int(peak),
+                       classifier_step=next((b for b in beside if b.get("shape") == [1, 1, n, H, W] and b.get("mode") == mode), None))
+            print(json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+            del x
+            model.zero_grad(set_to_none=True)
+            torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--mode", default="bf16")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "encoder_features.jsonl"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--grad", action="store_true")
+    ap.add_argument("--classifier", default=None)
     args = ap.parse_args()
+    args.out = args.out or str(ROOT / "profiles" / ("encoder_features_grad.jsonl" if args.grad else "encoder_features.jsonl"))
     assert torch.cuda.is_available(), "bench_features needs an MI355X"
+    if args.grad:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text("\n".join(grad_lines(args)) + "\n")
+        return
     model = DinoV2ClassifierSlice(in_ch=1, out_ch=2, pretrained=False, compute_dtype=args.mode)
     model.load_state_dict(synth.synth_state_dict("s", 0), strict=True)
     model = model.cuda().eval()
