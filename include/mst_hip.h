@@ -766,6 +766,22 @@ int mst_saliency_accumulate(const float* maps, const float* slice_attn, int D, i
 int mst_saliency_upsample(const float* lowres, int D, int gh, int gw, float scale, int Dout, int H, int W, float* out,
                           mst_stream_t stream);
 
+/* Folded test-time augmentation (scripts/main_predict.py:147-158: the identity and the flips (2,), (3,), (4,), (2,3), (2,4), (3,4),
+ * (2,3,4) of one volume, predictions and saliency averaged).  The encoder is per slice, so a flip along the depth only permutes slice
+ * embeddings and CLS attention rows: the eight variants need the slices of four in-plane flips.
+ * mst_tta_inplane_flips: x [n, H, W] (fp32 / fp16 / bf16) -> out [4, n, H, W] of the same type, not in place: x, x mirrored along H,
+ * along W, along both.  Every input row is read once and written four times in whole contiguous rows (the W mirror is reversed in LDS);
+ * any W whose row fits 64 KiB, any element-aligned pointers.
+ * mst_saliency_accumulate_tta: plane fp32 [4, D, heads, Np] (mst_attention_readout's `plane` of those 4*D slices, in that order) and
+ * slice_attn fp32 [8, D] (its `slice_attn` of the eight fused variants in the script's order above, positions as the variant saw them)
+ * -> lowres[D, gh, gw] = sum over the variants of head-mean(plane[f][d])[y_f][x_f] * slice_attn[v][r ? D-1-d : d], with f the variant's
+ * in-plane flip, (y_f, x_f) mirrored as f says and r its depth flip; slice_acc[D] = the same sum of slice_attn alone (nullable).  Both
+ * are overwritten, summed in the script's order by one thread per element: no atomics, identical bits at every call.  Columns >= gh*gw
+ * are ignored as in mst_saliency_accumulate (l.94-96); scale by 1/8 in mst_saliency_upsample. */
+int mst_tta_inplane_flips(const void* x, int dtype, int n, int H, int W, void* out, mst_stream_t stream);
+int mst_saliency_accumulate_tta(const float* plane, const float* slice_attn, int D, int heads, int gh, int gw, int Np,
+                                float* lowres, float* slice_acc, mst_stream_t stream);
+
 /* LieRE rotation of the slice transformer (AttentionLiereRotator, rotary_embedding_torch.py:319-372;
  * transformer_blocks.py:350-357): vars fp32 [n_blocks, block(block-1)/2, axes_length] (the module's ParameterList
  * stacked; spacial_dims = 1) -> R fp32 [n_blocks*block, n_blocks*block], block-diagonal, R_blk = exp(A_blk) with the

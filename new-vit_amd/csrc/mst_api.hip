@@ -1080,6 +1080,21 @@ int mst_saliency_upsample(const float* lowres, int D, int gh, int gw, float scal
     return launch_saliency_upsample(lowres, D, gh, gw, scale, Dout, H, W, out, (hipStream_t)stream);
 }
 
+int mst_tta_inplane_flips(const void* x, int dtype, int n, int H, int W, void* out, mst_stream_t stream) {
+    MST_CHECK_ARG(x && out && x != out, "tta_inplane_flips: null pointer, or out is x");
+    MST_CHECK_ARG(dtype == MST_F32 || dtype == MST_F16 || dtype == MST_BF16, "tta_inplane_flips: bad dtype %d", dtype);
+    MST_CHECK_ARG(n > 0 && H > 0 && W > 0, "tta_inplane_flips: bad sizes %d x %d x %d", n, H, W);
+    MST_CHECK_ARG(aligned(x, dtype == MST_F32 ? 4 : 2) && aligned(out, dtype == MST_F32 ? 4 : 2), "tta_inplane_flips: x and out must be aligned to their element");
+    return launch_tta_inplane_flips(x, dtype, n, H, W, out, (hipStream_t)stream);
+}
+
+int mst_saliency_accumulate_tta(const float* plane, const float* slice_attn, int D, int heads, int gh, int gw, int Np,
+                                float* lowres, float* slice_acc, mst_stream_t stream) {
+    MST_CHECK_ARG(plane && slice_attn && lowres, "saliency_accumulate_tta: null pointer");
+    MST_CHECK_ARG(D > 0 && heads > 0 && gh > 0 && gw > 0 && gh * gw <= Np, "saliency_accumulate_tta: grid %d x %d does not fit %d map columns", gh, gw, Np);
+    return launch_saliency_accumulate_tta(plane, slice_attn, D, heads, gh, gw, Np, lowres, slice_acc, (hipStream_t)stream);
+}
+
 int mst_liere_rotation(const float* vars, int n_blocks, int block, int axes_length, float* R, mst_stream_t stream) {
     MST_CHECK_ARG(vars && R, "liere_rotation: null pointer");
     return launch_liere_rotation(vars, n_blocks, block, axes_length, R, (hipStream_t)stream);

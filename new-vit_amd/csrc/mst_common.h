@@ -434,6 +434,10 @@ int launch_saliency_accumulate(const float* maps, const float* slice_attn, int D
                                int flip_mask, int accumulate, float* low, float* slice_acc, hipStream_t s);
 int launch_saliency_upsample(const float* low, int D, int gh, int gw, float scale, int Dout, int H, int W, float* out,
                              hipStream_t s);
+// folded test-time augmentation (k_tta.hip)
+int launch_tta_inplane_flips(const void* x, int dt, int n, int H, int W, void* out, hipStream_t s);
+int launch_saliency_accumulate_tta(const float* plane, const float* slice_attn, int D, int heads, int gh, int gw, int Np,
+                                   float* low, float* slice_acc, hipStream_t s);
 int launch_bmm32_nn(const float* A, const float* B, float* C, int64_t batch, int M, int N, int K, hipStream_t s);
 // training step (k_train.hip)
 int launch_gemm_ex(const float* A, const float* B, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,

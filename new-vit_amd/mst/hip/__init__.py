@@ -158,6 +158,9 @@ SIGNATURES = {
     "mst_attention_readout": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mst_saliency_accumulate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mst_saliency_upsample": (_i, [_vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
+    # folded test-time augmentation (csrc/k_tta.hip)
+    "mst_tta_inplane_flips": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "mst_saliency_accumulate_tta": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mst_liere_rotation": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mst_attention_rollout": (_i, [C.POINTER(_vp), _i, _i64, _i, _vp, _vp, _vp]),
     # fixed-order forms (torch.use_deterministic_algorithms): no floating-point atomics, caller-given workspace
@@ -909,6 +912,38 @@ def saliency_upsample(lowres: torch.Tensor, size, scale: float = 1.0) -> torch.T
     _check(load().mst_saliency_upsample(ptr(lowres), D, gh, gw, float(scale), Dout, H, W, ptr(out), stream_of(lowres)),
            "mst_saliency_upsample")
     return out
+
+
+def tta_inplane_flips(x: torch.Tensor) -> torch.Tensor:
+    """mst_tta_inplane_flips: slices x [n, H, W] (fp32 / fp16 / bf16) -> [4, n, H, W] of x's type: x, torch.flip(x, (1,)),
+    torch.flip(x, (2,)), torch.flip(x, (1, 2)) -- the in-plane halves of the script's eight TTA flips (main_predict.py:147-158)."""
+    _operand(x, "tta_inplane_flips", "x", (torch.float32,) + _T16)
+    if x.dim() != 3 or 0 in x.shape:
+        raise ValueError(f"tta_inplane_flips: x must be [n, H, W] and not empty, got {list(x.shape)}")
+    _resident("tta_inplane_flips", x=x)
+    n, H, W = x.shape
+    out = torch.empty((4, n, H, W), dtype=x.dtype, device=x.device)
+    _check(load().mst_tta_inplane_flips(ptr(x), dt_of(x), n, H, W, ptr(out), stream_of(x)), "mst_tta_inplane_flips")
+    return out
+
+
+def saliency_accumulate_tta(plane: torch.Tensor, slice_attn: torch.Tensor, gh: int, gw: int, lowres: torch.Tensor,
+                            slice_acc: Optional[torch.Tensor]):
+    """mst_saliency_accumulate_tta: lowres [D,gh,gw] = the eight-variant TTA sum of head-mean(plane [4,D,heads,Np]) * slice_attn [8,D],
+    flips mirrored back; slice_acc [D] (optional) = the sum of slice_attn alone.  Overwrites; fixed summation order."""
+    _operand(plane, "saliency_accumulate_tta", "plane", (torch.float32,))
+    if plane.dim() != 4 or plane.shape[0] != 4 or 0 in plane.shape:
+        raise ValueError(f"saliency_accumulate_tta: plane must be [4, D, heads, Np] and not empty, got {list(plane.shape)}")
+    _, D, heads, Np = plane.shape
+    if gh < 1 or gw < 1 or gh * gw > Np:
+        raise ValueError(f"saliency_accumulate_tta: grid {gh} x {gw} does not fit {Np} map columns")
+    _operand(slice_attn, "saliency_accumulate_tta", "slice_attn", (torch.float32,), (8, D))
+    _operand(lowres, "saliency_accumulate_tta", "lowres", (torch.float32,), (D, gh, gw))
+    if slice_acc is not None:
+        _operand(slice_acc, "saliency_accumulate_tta", "slice_acc", (torch.float32,), (D,))
+    _resident("saliency_accumulate_tta", plane=plane, slice_attn=slice_attn, lowres=lowres, slice_acc=slice_acc)
+    _check(load().mst_saliency_accumulate_tta(ptr(plane), ptr(slice_attn), D, heads, gh, gw, Np, ptr(lowres), ptr(slice_acc),
+                                              stream_of(plane)), "mst_saliency_accumulate_tta")
 
 
 def liere_rotation(vars_: Sequence[torch.Tensor]) -> torch.Tensor:
