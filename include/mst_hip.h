@@ -169,6 +169,21 @@ int mst_patch_rows16(const void* vol, int in_dtype, int n, int H, int W, const v
  *   the stored q times dq_scale (pass the epilogue's factor, 0.125, for the gradient of the un-scaled projection output).
  *   workspace: device memory of at least mst_attention_train_bwd_workspace_bytes(n_seq, N, heads, 64) bytes (a 16-bit image of dout
  *   and the row sums D = rowsum(dout o out)).  Deterministic (no atomics): identical calls return identical bits.
+ *   The envelope of dout.  Each (sequence, head) is scaled on its own by a power of two c = 2^min(6 - e, 126), with max |dout| in
+ *   [2^(e-1), 2^e) over that head's N x 64 block, and the results are multiplied by 1 / c: the gradients are homogeneous in powers of
+ *   two, bit for bit, and a head does not see its neighbours' magnitudes.
+ *     - max |dout| from 2^-121 (3.8e-37) to 3e38: c max |dout| in [32, 64), the same relative accuracy at every magnitude, as long as
+ *       the gradients themselves stay normal fp32 numbers.
+ *     - below 2^-121, denormals included: c = 2^126 (c and 1 / c stay finite normal numbers).  The gradients are finite; they are fp32
+ *       denormals and D = c rowsum(dout o out) is formed from denormal products, so they lose accuracy gradually with the magnitude
+ *       and reach zero where fp32 ends (about 1e-45).  tests/test_attn_train_range_gpu.py holds heads at 2^-124 and at 1e-40 to the
+ *       same kind of bar as every other head.
+ *     - a head that is all zero returns exact zeros; a head that holds an inf or a NaN (or exceeds 3e38) returns unspecified values
+ *       in ITS dQ, dK, dV and leaves every other (sequence, head) untouched, bit for bit.
+ *     - fp16 headroom of dS: the 16-bit MFMA operand dS = P o (c dP - c D), dP = dout v^T, carries c max |dout| < 64, so in fp16 (largest
+ *       number 65504) it overflows when P |dP - D| / max |dout| exceeds about 1000 for some (query, key) -- v and dout large and
+ *       aligned along one direction with a probability near 1 beside it.  Tested with |dP - D| / max |dout| beyond 1000 and dS up to
+ *       2^13 (a ratio of 190); the training step is orders of magnitude inside.  bf16 has fp32's range and no such limit.
  * Unsupported arguments (head_dim != 64, a dtype other than bf16 / fp16, N < 1, a short workspace) return MST_EINVAL. */
 size_t mst_attention_train_bwd_workspace_bytes(int n_seq, int N, int heads, int head_dim);
 int mst_attention_train_fwd(const void* qkv16, int dtype, int n_seq, int N, int heads, int head_dim, float* out, float* lse,

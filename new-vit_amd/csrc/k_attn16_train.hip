@@ -214,7 +214,8 @@ __global__ __launch_bounds__(WGT) void attn_train_fwd_kernel(const T* __restrict
     }
 }
 
-// ---- backward preprocess: one workgroup per (sequence, head).  Pass 1: m = max |dO| -> scale c = 2^(6 - e), m in [2^(e-1), 2^e).
+// ---- backward preprocess: one workgroup per (sequence, head).  Pass 1: m = max |dO| -> scale c = 2^min(6 - e, 126), m in [2^(e-1), 2^e):
+// c m in [32, 64) down to m = 2^-121; below (denormals included) c stays 2^126, where 2^(6 - e) would be inf and every gradient NaN.
 // Pass 2 (8 lanes per row): Dv[seq][h][q] = c sum_d dO o O (fp32 products; O fp32, or T as the 16-bit storage mode keeps it), do16 =
 // 16-bit image of c dO; cs[seq][h] = c.
 template <typename T, typename OT>
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(256) void attn_train_pre_kernel(const OT* __restric
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     int e = 0;
     (void)frexpf(m, &e);
-    const float c = (m > 0.f && m <= 3.0e38f) ? ldexpf(1.0f, 6 - e) : 1.0f;
+    const float c = (m > 0.f && m <= 3.0e38f) ? ldexpf(1.0f, min(6 - e, 126)) : 1.0f;   // c, 1 / c finite and normal: 2^-122 .. 2^126
     const int sub = tid & 7;
     for (int q = tid >> 3; q < N; q += 32) {
         const int64_t off = (row0 + q) * E + h * 64 + sub * 8;
